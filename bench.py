@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- whole-job throughput of the viet-asr hot path on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}] [--gemm ...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}] [--gemm ...] [--dump-outputs DIR]
 
 One *step* = one pass of the hot path over one batch of synthetic audio per GPU (input already resident in HBM),
 then the gather of the collapsed id sequences to every rank (the reference's _infer gathers each returned tensor with
@@ -30,6 +30,9 @@ lengths U[L/2, L]), a "latency" block (batch 1 / 8 of 15x5, and the reference's 
 `python bench.py --gpus N` with N > 1 starts its own N ranks (re-executes itself under torch.distributed.run on a free
 port of 127.0.0.1); launched by torchrun / the driver it uses the ranks it is given.  One process per GPU, backend
 "nccl" = RCCL over xGMI.
+
+`--dump-outputs DIR` writes what the last timed step returned on rank 0 as float32 DIR/<name>.npy (ids, -1 past id_len;
+id_len; enc_len; score under --config 4).  Inputs and weights are seeded, so two builds can be compared file by file.
 
 Prints ONE JSON line on rank 0 with the driver contract keys plus
   roofline      -- dominant kernel family (1x1-conv GEMMs, incl. the fused depthwise + pointwise launches): executed MFMA
@@ -332,6 +335,34 @@ def side_workload(cfg_id, dev, gemm, steps, warmup, a, ragged=False):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, parts):
+    """--dump-outputs: what the timed path returned in its last step, one float32 .npy per returned array, rows of all the
+    step's passes concatenated in order.  ids are defined up to id_len only (the kernels leave the rest of a row unwritten):
+    the tail is set to -1 so that two runs on the same inputs give the same files.  Past DUMP_MAX_BYTES a fixed seeded sample
+    of rows is written, with their indices in sample_rows.npy."""
+    width = max(int(q["ids"].shape[1]) for q in parts)
+    ids = np.concatenate([np.pad(q["ids"].cpu().numpy(), ((0, 0), (0, width - int(q["ids"].shape[1])))) for q in parts])
+    n = np.concatenate([q["id_len"].cpu().numpy() for q in parts])
+    ids[np.arange(width)[None, :] >= np.maximum(n, 0)[:, None]] = -1
+    arrays = {"ids": ids, "id_len": n}
+    for k in ("enc_len", "score"):
+        if parts[0].get(k) is not None:
+            arrays[k] = np.concatenate([q[k].cpu().numpy() for q in parts])
+    rows = len(n)
+    row_bytes = sum(4 * v[0].size for v in arrays.values())
+    if rows * row_bytes > DUMP_MAX_BYTES:
+        pick = np.sort(np.random.RandomState(0).choice(rows, DUMP_MAX_BYTES // (row_bytes + 4), replace=False))
+        arrays = {k: v[pick] for k, v in arrays.items()}
+        arrays["sample_rows"] = pick
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+    sys.stderr.write(f"bench.py: wrote {', '.join(sorted(arrays))} ({rows} rows) to {out_dir}\n")
+
+
 def timed_ms(fn, n):
     """Mean milliseconds of n back-to-back calls on the current stream (one untimed call first)."""
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -537,7 +568,11 @@ def main():
     ap.add_argument("--spawn", action="store_true", help="go through the self-launcher even for --gpus 1 (RCCL world of 1)")
     ap.add_argument("--gemm", choices=sorted(GEMM_MODES), default=None,
                     help="arithmetic of the 1x1-conv GEMMs (default: the library's default mode)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0's clips) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if not launched and (a.gpus > 1 or a.spawn):
@@ -636,10 +671,7 @@ def main():
         return r
 
     def step():
-        r, parts = None, []
-        for p in passes:
-            r = one_pass(p)
-            parts.append(r)
+        parts = [one_pass(p) for p in passes]
         if dist is not None and job and a.ragged:
             # ragged job: the ranks' passes differ in number and shape, so ONE gather per step of all of this rank's id
             # rows through the shape-exchanging gather of the product path (dist.gather_id_sequences: all_gather(shape)
@@ -648,7 +680,7 @@ def main():
             width = max(q["ids"].shape[1] for q in parts)
             ids = torch.cat([torch.nn.functional.pad(q["ids"], (0, width - q["ids"].shape[1])) for q in parts])
             vdist.gather_id_sequences(ids, torch.cat([q["id_len"] for q in parts]))
-        return r
+        return parts
 
     def sync():
         if dist is not None:
@@ -661,11 +693,14 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        r = step()
+        parts = step()
     torch.cuda.synchronize()
     own_elapsed = time.perf_counter() - t0        # this rank's own work, before it waits for the others
     sync()
     elapsed = time.perf_counter() - t0
+    r = parts[-1]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, parts)
     rccl = None
     if dist is not None:
         if not (job and a.ragged):

@@ -342,3 +342,30 @@ def test_bench_rate_arithmetic_and_core_count_without_a_gpu():
     n, how = bench.usable_cores()
     assert 1 <= n <= len(os.sched_getaffinity(0)) and "affinity" in how
     assert set(bench.WORKLOADS) == {2, 3, 4, 5} and bench.WORKLOADS[5][1] * 8 == bench.JOB_CLIPS
+
+
+def test_bench_dump_outputs_without_a_gpu(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the passes of a step concatenated row-wise, ids past id_len (never written by the kernels)
+    set to -1, every file float32; past the size bound a seeded row sample, the same one every time."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("vasr_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    ids = torch.tensor([[5, 6, 777], [9, 888, 999]], dtype=torch.int32)
+    parts = [dict(ids=ids, id_len=torch.tensor([2, 1], dtype=torch.int32), enc_len=torch.tensor([3.0, 2.0]), pred=None),
+             dict(ids=torch.tensor([[4, 4]], dtype=torch.int32), id_len=torch.tensor([2], dtype=torch.int32),
+                  enc_len=torch.tensor([2.0]), pred=None)]
+    bench.dump_outputs(str(tmp_path / "a"), parts)
+    got = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"ids", "id_len", "enc_len"} and all(v.dtype == np.float32 for v in got.values())
+    assert got["ids"].tolist() == [[5, 6, -1], [9, -1, -1], [4, 4, -1]] and got["id_len"].tolist() == [2, 1, 2]
+    assert got["enc_len"].tolist() == [3.0, 2.0, 2.0]
+    big = [dict(ids=torch.zeros((40, 100), dtype=torch.int32), id_len=torch.full((40,), 100, dtype=torch.int32),
+                score=torch.arange(40, dtype=torch.float32))]
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10 * 412)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    sizes = sum(os.path.getsize(str(tmp_path / "b" / f)) - 128 for f in os.listdir(tmp_path / "b"))   # 128: .npy header
+    rows = np.load(str(tmp_path / "b" / "sample_rows.npy"))
+    assert sizes <= 10 * 412 and len(rows) == 10 and np.array_equal(np.load(str(tmp_path / "b" / "score.npy")), rows)
+    assert np.array_equal(rows, np.load(str(tmp_path / "c" / "sample_rows.npy")))
