@@ -41,8 +41,9 @@ extern "C" {
  * a caller built against the four-class form would be written past its arrays; 5: vasr_lm_create takes 16-byte table
  * entries with power-of-two capacities; 6: vasr_lm_create takes the character trie of pyctcdecode's unigram set, the
  * vocabulary entries carry a set-membership flag, vasr_resample_f32 emits ceil(len * ratio) samples,
- * vasr_frontend_desc ends in log_guard_clamp and knows normalize = 2; 7: + vasr_transcribe_greedy_pcm16). */
-#define VASR_ABI_VERSION 7
+ * vasr_frontend_desc ends in log_guard_clamp and knows normalize = 2; 7: + vasr_transcribe_greedy_pcm16; 8: vasr_block_desc
+ * ends in residual_dense, and non-separable blocks take any kernel / stride / dilation). */
+#define VASR_ABI_VERSION 8
 
 typedef struct vasr_handle vasr_handle;
 typedef void* vasr_stream; /* hipStream_t */
@@ -57,7 +58,8 @@ typedef enum {
 } vasr_status;
 
 /* One JasperBlock (nemo/collections/asr/parts/jasper.py:175-288), as the YAML spells it
- * (configs/quartznet12x1_vi.yaml:25-165). */
+ * (configs/quartznet12x1_vi.yaml:25-165).  A non-separable block of kernel > 1 (Jasper) runs as an implicit GEMM over
+ * (tap, input channel) and needs an input channel count that is a multiple of 64. */
 typedef struct {
   int32_t filters;
   int32_t repeat;
@@ -66,6 +68,12 @@ typedef struct {
   int32_t dilation;
   int32_t residual;  /* 0/1 */
   int32_t separable; /* 0/1 */
+  int32_t residual_dense; /* 0/1: JasperEncoder's residual_dense (jasper.py:152-161, parts/jasper.py:264-288, :428-448): the
+                             residual sums a 1x1 conv + BN of every pane -- the block input and the outputs of the earlier
+                             blocks of the contiguous dense run (the encoder input when the run starts at block 0); weights
+                             encoder.{i}.res.{p}.{0.conv.weight,1.*}.  vasr_create refuses the layouts the reference cannot
+                             run: a dense block after a non-dense one that followed a dense run, a dense block without
+                             residual followed by a dense block, a strided dense block with residual.  (ABI 8: appended) */
 } vasr_block_desc;
 
 /* Front end = FilterbankFeatures.__init__ (parts/features.py:113-236) with the knobs the

@@ -38,6 +38,10 @@ VASR_API int vasr_bench_depthwise_mfma(const float* d_x, const uint32_t* d_taps,
 /* Host helper: [cout][cin] row-major weights -> the MFMA fragment order the pointwise kernel streams
  * ([m_pad/32][cin/8][64 lanes][4], rows past cout zero); h_out holds m_pad*cin floats. */
 VASR_API int vasr_pack_pointwise(const float* h_w, int cout, int cin, int m_pad, float* h_out);
+/* Host helper: a non-separable conv's [cout][cin][kernel] weights -> the [cout][kernel * cin] matrix of its implicit GEMM
+ * (reduction index k = tap * cin + c, input channel inner), which the vasr_pack_pointwise* packers then take with
+ * cin' = kernel * cin -- the layout vasr_finalize packs K-tap convolutions in. */
+VASR_API int vasr_conv_gemm_weights(const float* h_w, int cout, int cin, int kernel, float* h_out);
 VASR_API int vasr_bench_pointwise(const float* d_x, const float* d_wt, const float* d_scale, const float* d_shift,
                          int batch, int cin, int cout, int64_t frames, float* d_y, vasr_stream stream);
 

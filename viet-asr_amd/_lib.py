@@ -24,7 +24,7 @@ class VasrError(RuntimeError):
 
 class BlockDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in
-                ("filters", "repeat", "kernel", "stride", "dilation", "residual", "separable")]
+                ("filters", "repeat", "kernel", "stride", "dilation", "residual", "separable", "residual_dense")]
 
 
 class FrontendDesc(C.Structure):
@@ -97,6 +97,7 @@ DEV_SIGNATURES = {
     "vasr_profile_bracket_overhead": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
     "vasr_fused_tile_choice": (C.c_int, [C.c_int64, C.c_int]),
     "vasr_pack_pointwise": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
+    "vasr_conv_gemm_weights": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "vasr_pack_pointwise_bf16x3": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "vasr_bench_pointwise_bf16x3": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P]),
     "vasr_bench_mfma_sustained": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_double), _P]),
@@ -104,7 +105,7 @@ DEV_SIGNATURES = {
     "vasr_bench_pointwise": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P]),
 }
 
-ABI_VERSION = 7          # VASR_ABI_VERSION of the include/vasr.h these signatures were written against
+ABI_VERSION = 8          # VASR_ABI_VERSION of the include/vasr.h these signatures were written against
 
 _lib = None
 _dev = None
@@ -189,8 +190,9 @@ class Handle:
         if blocks:
             arr = (BlockDesc * len(blocks))()
             for i, b in enumerate(blocks):
-                arr[i] = BlockDesc(*[int(b[k]) for k in
-                                     ("filters", "repeat", "kernel", "stride", "dilation", "residual", "separable")])
+                arr[i] = BlockDesc(*[int(b.get(k, 0)) for k in
+                                     ("filters", "repeat", "kernel", "stride", "dilation", "residual", "separable",
+                                      "residual_dense")])
             self._keep.append(arr)
             md.blocks, md.n_blocks, md.feat_in = arr, len(blocks), int(feat_in)
         md.dec_feat_in, md.num_classes = int(dec_feat_in), int(num_classes)

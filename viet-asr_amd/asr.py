@@ -16,7 +16,7 @@ from . import _lib, stages
 from .core import (AcousticEncodedRepresentation, AudioSignal, DataLayerNM, DeviceType, LengthsType,
                    LogprobsType, MelSpectrogramType, NeuralType, NonTrainableNM, PredictionsType,
                    SpectrogramType, TrainableNM)
-from .engine import blocks_from_config
+from .engine import blocks_from_config, check_dense_layout
 from .frontend_tables import frontend_description
 
 __all__ = ["AudioToMelSpectrogramPreprocessor", "JasperEncoder", "JasperDecoderForCTC", "GreedyCTCDecoder",
@@ -111,7 +111,7 @@ class _MaskedConvParams(nn.Module):
 class _JasperBlockParams(nn.Module):
     """ModuleList skeleton of one JasperBlock (parts/jasper.py:214-288): same indices, parameters only."""
 
-    def __init__(self, inplanes, planes, repeat, kernel, separable, residual):
+    def __init__(self, inplanes, planes, repeat, kernel, separable, residual, residual_panes=()):
         super().__init__()
         layers, c = [], inplanes
         for r in range(repeat):
@@ -125,9 +125,10 @@ class _JasperBlockParams(nn.Module):
             c = planes
         self.mconv = nn.ModuleList(layers)
         self.res = None
-        if residual:
-            self.res = nn.ModuleList([nn.ModuleList([_MaskedConvParams(inplanes, planes, 1),
-                                                     nn.BatchNorm1d(planes, eps=1e-3, momentum=0.1)])])
+        if residual:   # one 1x1 conv + BN per pane (parts/jasper.py:264-288); no dense panes: the block input alone
+            self.res = nn.ModuleList([nn.ModuleList([_MaskedConvParams(ip, planes, 1),
+                                                     nn.BatchNorm1d(planes, eps=1e-3, momentum=0.1)])
+                                      for ip in (list(residual_panes) or [inplanes])])
 
 
 def _init_weights(m, mode="xavier_uniform"):
@@ -184,13 +185,20 @@ class JasperEncoder(_HipWeights, TrainableNM):
                                       "residual_mode='add', conv_mask=True, frame_splicing=1")
         self._blocks = blocks_from_config(jasper)
         self._feat_in = feat_in * frame_splicing
+        check_dense_layout(self._blocks, self._feat_in)
         for b in self._blocks:
             if b["stride"] > 1 and b["dilation"] > 1:
                 raise ValueError("Only stride OR dilation may be greater than 1")   # parts/jasper.py:61-62
         layers, c = [], self._feat_in
+        residual_panes = []     # ONE list shared by the dense blocks, copied by each (jasper.py:152-161, parts/jasper.py:264)
         for b in self._blocks:
             k = b["kernel"] + (1 if b["kernel"] % 2 == 0 else 0)
-            layers.append(_JasperBlockParams(c, b["filters"], b["repeat"], k, bool(b["separable"]), bool(b["residual"])))
+            dense_res = []
+            if b["residual_dense"]:
+                residual_panes.append(c)
+                dense_res = residual_panes
+            layers.append(_JasperBlockParams(c, b["filters"], b["repeat"], k, bool(b["separable"]), bool(b["residual"]),
+                                             list(dense_res)))
             c = b["filters"]
         self.encoder = nn.Sequential(*layers)
         self._c_out = c

@@ -20,12 +20,26 @@ _PRE = dict(sample_rate=16000, window_size=0.02, window_stride=0.01, window="han
             n_fft=512, features=64, dither=0.00001, pad_to=16, stft_conv=False)
 
 
-def _blk(filters, repeat, kernel, stride=1, dilation=1, residual=True, separable=True):
+def _blk(filters, repeat, kernel, stride=1, dilation=1, residual=True, separable=True, residual_dense=False):
     d = dict(filters=filters, repeat=repeat, kernel=[kernel], stride=[stride], dilation=[dilation],
              dropout=0.0, residual=residual)
     if separable:
         d["separable"] = True
+    if residual_dense:
+        d["residual_dense"] = True
     return d
+
+
+def _jasper10x5dr():
+    """Jasper 10x5 with dense residuals (Jasper paper, table 1 and section 2.2): a K 11 stride-2 prologue, B1-B5 x2 of five
+    non-separable sub-blocks each (256 / K 11, 384 / 13, 512 / 17, 640 / 21, 768 / 25), every one residual and dense, then a
+    K 29 dilation-2 and a K 1 epilogue block, as NeMo's jasper10x5dr.yaml of this generation spells it."""
+    blocks = [_blk(256, 1, 11, stride=2, residual=False, separable=False)]
+    for ch, k in ((256, 11), (384, 13), (512, 17), (640, 21), (768, 25)):
+        blocks += [_blk(ch, 5, k, separable=False, residual_dense=True) for _ in range(2)]
+    blocks += [_blk(896, 1, 29, dilation=2, residual=False, separable=False),
+               _blk(1024, 1, 1, residual=False, separable=False)]
+    return blocks
 
 
 def _quartznet(repeat, with_dilated_tail):
@@ -54,6 +68,8 @@ def builtin(name):
         body, labels = _quartznet(1, False), LABELS_VI_DIGITS
     elif name in ("quartznet15x5", "quartznet15x5.yaml"):
         body, labels = _quartznet(5, True), LABELS_EN
+    elif name in ("jasper10x5dr", "jasper10x5dr.yaml"):
+        body, labels = _jasper10x5dr(), LABELS_EN
     else:
         raise ValueError(f"unknown builtin model {name!r}")
     return {
@@ -61,6 +77,16 @@ def builtin(name):
         "AudioToMelSpectrogramPreprocessor": dict(_PRE),
         "JasperEncoder": {"activation": "relu", "conv_mask": True, "jasper": body},
         "labels": list(labels),
+    }
+
+
+def jasper_definition(jasper, labels=None):
+    """Model definition around a block list (JasperEncoder.jasper): the builtin front end, English labels by default."""
+    return {
+        "model": "custom",
+        "AudioToMelSpectrogramPreprocessor": dict(_PRE),
+        "JasperEncoder": {"activation": "relu", "conv_mask": True, "jasper": copy.deepcopy(list(jasper))},
+        "labels": list(labels or LABELS_EN),
     }
 
 

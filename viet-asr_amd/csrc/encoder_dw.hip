@@ -601,23 +601,24 @@ static int launch_depthwise_impl(const float* x, int64_t ldx, int frames_in, con
 // publish its maxima (port tensors, the fp32 GEMM kernel)
 __global__ __launch_bounds__(256) void amax_kernel(const float* __restrict__ x, int64_t ld, int rows, int frames,
                                                    const int32_t* __restrict__ lens, unsigned* __restrict__ amax,
-                                                   int amax_stride) {
+                                                   int amax_stride, int64_t bs) {
   const int b = blockIdx.y;
   int n = lens ? lens[b] : frames;
   n = n < frames ? n : frames;
   unsigned m = 0;
   for (int r = blockIdx.x; r < rows; r += gridDim.x) {
-    const float* xr = x + ((int64_t)b * rows + r) * ld;
+    const float* xr = x + (int64_t)b * bs + (int64_t)r * ld;
     for (int t = threadIdx.x; t < n; t += blockDim.x) m = max(m, abs_bits(xr[t]));
   }
   amax_publish(amax, amax_stride, b, blockIdx.x * 4 + (threadIdx.x >> 6), m, threadIdx.x & 63);
 }
 
 void launch_amax(const float* x, int64_t ld, int rows, int frames, const int32_t* lens, int batch, AmaxTab* amax,
-                 hipStream_t st) {
+                 hipStream_t st, int64_t batch_stride) {
   const int gx = rows < 64 ? rows : 64;
   amax->n = gx * 4;
-  hipLaunchKernelGGL(amax_kernel, dim3(gx, batch), dim3(256), 0, st, x, ld, rows, frames, lens, amax->p, amax->stride);
+  hipLaunchKernelGGL(amax_kernel, dim3(gx, batch), dim3(256), 0, st, x, ld, rows, frames, lens, amax->p, amax->stride,
+                     batch_stride ? batch_stride : (int64_t)rows * ld);
 }
 
 void launch_len_chain(const int64_t* seq, int batch, const LenStep* d_steps, int n_steps, int32_t* lens_tab,

@@ -24,6 +24,9 @@
 //     k-steps with one coalesced 16-byte load straight from L2, one k-group ahead of use.
 //   * Work-group ids are remapped so that neighbours in (m-block, time-tile) order share an XCD
 //     (private L2 per XCD; block b lands on XCD b % 8).
+//   * CONV (PwArgs::conv_cin > 0): a non-separable K-tap MaskedConv1d as an implicit GEMM over the reduction index
+//     k = tap * C_in + c (encoder_pw_split.hip has the same form): row k of a chunk is x[c] read at column
+//     t * stride + tap * dil - pad, zero outside [0, lens[b]).
 #include <cstdlib>
 
 #include "vasr_internal.h"
@@ -52,7 +55,7 @@ struct PwGeom {
 // DUAL: the reduction runs over two activation tensors back to back -- rows [0, K1) from a.x, rows [K1, K)
 // from a.x2 (masked with a.lens2).  Used to fold a JasperBlock's residual 1x1 conv into its last sub-block's GEMM
 // (weights [s1*W1 | s2*W2] concatenated along K, shift h1 + h2), which removes the residual tensor round trip.
-template <int WM, int TM, bool MASK, bool RES, bool DUAL>
+template <int WM, int TM, bool MASK, bool RES, bool DUAL, bool CONV = false>
 __global__ __launch_bounds__(512, 4) void pw_gemm_kernel(PwArgs a, int blocks_m, int tiles_t, int n_blocks) {
   using G = PwGeom<WM, TM>;
   __shared__ v4f Bs4[2][kChunkFloats / 4];
@@ -80,7 +83,8 @@ __global__ __launch_bounds__(512, 4) void pw_gemm_kernel(PwArgs a, int blocks_m,
   constexpr int C4 = G::BN / 4;
   const int ld_row = tid / C4, ld_c4 = tid % C4;
   const int K1 = DUAL ? a.K1 : a.K;
-  const float* __restrict__ xb = a.x + (int64_t)b * K1 * a.ldx + t0 + ld_c4 * 4;
+  const float* __restrict__ xb = CONV ? a.x + (int64_t)b * a.conv_cin * a.ldx
+                                     : a.x + (a.bsx ? (int64_t)b * a.bsx : (int64_t)b * K1 * a.ldx) + t0 + ld_c4 * 4;
   const float* __restrict__ xb2 = DUAL ? a.x2 + (int64_t)b * (a.K - K1) * a.ldx2 + t0 + ld_c4 * 4 : nullptr;
   // A fragments: packed [M/32][K/8][64 lanes] float4, this wave's TM m-tiles
   const int kgroups = a.K / 8;
@@ -97,6 +101,23 @@ __global__ __launch_bounds__(512, 4) void pw_gemm_kernel(PwArgs a, int blocks_m,
 
   v4f rb[G::PASSES];
   auto gload = [&](int k0) {
+    if constexpr (CONV) {
+#pragma unroll
+      for (int p = 0; p < G::PASSES; ++p) {
+        const int k = k0 + ld_row + G::ROWS_PER_PASS * p, tap = k / a.conv_cin, c = k - tap * a.conv_cin;
+        const float* __restrict__ row = xb + (int64_t)c * a.ldx;
+        v4f v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int col = (t0 + ld_c4 * 4 + e) * a.conv_stride + tap * a.conv_dil - a.conv_pad;
+          const bool ok = col >= 0 && col < len;
+          const float x = row[ok ? col : 0];
+          v[e] = ok ? x : 0.f;
+        }
+        rb[p] = v;
+      }
+      return;
+    }
     const bool second = DUAL && k0 >= K1;      // chunk-uniform: K1 is a multiple of the chunk depth
     const float* __restrict__ src = second ? xb2 + (int64_t)(k0 - K1) * a.ldx2 : xb + (int64_t)k0 * a.ldx;
     const int64_t ld = second ? a.ldx2 : a.ldx;
@@ -188,11 +209,13 @@ template <int WM, int TM>
 void launch_t(const PwArgs& a, hipStream_t st) {
   using G = PwGeom<WM, TM>;
   const int blocks_m = a.M / G::BM;
-  const int tiles_t = (int)((a.ldx + G::BN - 1) / G::BN);
+  const int tiles_t = (int)(((a.conv_cin ? a.conv_cols : a.ldx) + G::BN - 1) / G::BN);
   const int n_blocks = blocks_m * tiles_t * a.batch;
   dim3 grid(n_blocks), block(512);
   const bool mask = a.lens != nullptr, res = a.res != nullptr, dual = a.x2 != nullptr;
-  if (dual) VASR_LAUNCH((pw_gemm_kernel<WM, TM, false, false, true>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
+  if (a.conv_cin && res) VASR_LAUNCH((pw_gemm_kernel<WM, TM, true, true, false, true>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
+  else if (a.conv_cin) VASR_LAUNCH((pw_gemm_kernel<WM, TM, true, false, false, true>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
+  else if (dual) VASR_LAUNCH((pw_gemm_kernel<WM, TM, false, false, true>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
   else if (mask && res) VASR_LAUNCH((pw_gemm_kernel<WM, TM, true, true, false>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
   else if (mask) VASR_LAUNCH((pw_gemm_kernel<WM, TM, true, false, false>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
   else if (res) VASR_LAUNCH((pw_gemm_kernel<WM, TM, false, true, false>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
@@ -227,6 +250,13 @@ void pack_pointwise_weights(const float* w, int cout, int cin, int m_pad, float*
           const int m = mt * 32 + (lane & 31), k = g * 8 + 2 * s + (lane >> 5);
           out[(((size_t)mt * kgroups + g) * 64 + lane) * 4 + s] = m < cout ? w[(size_t)m * cin + k] : 0.f;
         }
+}
+
+// [cout][cin][kernel] (Conv1d weight) -> [cout][kernel * cin], reduction index k = tap * cin + c (c_in inner)
+void pack_conv_gemm_weights(const float* w, int cout, int cin, int kernel, float* out) {
+  for (int m = 0; m < cout; ++m)
+    for (int t = 0; t < kernel; ++t)
+      for (int c = 0; c < cin; ++c) out[((size_t)m * kernel + t) * cin + c] = w[((size_t)m * cin + c) * kernel + t];
 }
 
 }  // namespace vasr

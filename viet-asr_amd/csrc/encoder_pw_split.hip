@@ -29,6 +29,13 @@
 //     accumulator registers, one workgroup per CU): a weight fragment is reused for 12-24 MFMAs;
 //   * latency tile 64 x 32 (2 wavefronts) for small batches, where the throughput tile would leave most of the
 //     256 CUs idle (B = 1: 4 workgroups per layer instead of 128).
+//
+// CONV (PwArgs::conv_cin > 0): the same GEMM as an implicit-GEMM K-tap convolution (a non-separable MaskedConv1d,
+// parts/jasper.py:113-132, of kernel K, stride, dilation, "same" padding :60-65).  The reduction index is (tap, c_in) with
+// c_in inner -- k = tap * C_in + c, weights packed in that order (pack_conv_gemm_weights) -- so that with C_in % 64 == 0 a
+// 64-row chunk lies inside one tap: its rows are x[c0 .. c0 + 63] read at the tap's column offset
+// t * stride + tap * dil - pad, zero outside [0, lens[b]) (the input mask).  Staging, splits, MFMAs and epilogue are the
+// 1x1 kernel's; only the addresses differ.
 #include <cstdlib>
 #include <cstring>
 
@@ -125,7 +132,7 @@ struct Geom {
   static_assert(PATCHES % NT == 0 && PPT >= 1, "staging patches must divide evenly over the threads");
 };
 
-template <int NW, int TM, int TN, bool MASK, bool RES, bool DUAL, int ARITH>
+template <int NW, int TM, int TN, bool MASK, bool RES, bool DUAL, int ARITH, bool CONV = false>
 __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int blocks_m, int tiles_t, int n_blocks) {
   using G = Geom<NW, TM, TN, ARITH>;
   constexpr int BM = G::BM, BN = G::BN, NT = G::NT, PPT = G::PPT, PL = G::PL, PLW = G::PLW;
@@ -158,7 +165,8 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
   float xs = 1.f, out_scale = 1.f;
 
   const int K1 = DUAL ? a.K1 : a.K;
-  const float* __restrict__ xb = a.x + (int64_t)b * K1 * a.ldx + t0;
+  const float* __restrict__ xb = CONV ? a.x + (int64_t)b * a.conv_cin * a.ldx
+                                     : a.x + (a.bsx ? (int64_t)b * a.bsx : (int64_t)b * K1 * a.ldx) + t0;
   const float* __restrict__ xb2 = DUAL ? a.x2 + (int64_t)b * (a.K - K1) * a.ldx2 + t0 : nullptr;
   // A fragments [M/32][K/16][PLW][64] uint4
   const int ksteps = a.K / 16;
@@ -201,6 +209,26 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
   auto gload = [&](int k0, auto set_tag) {
     auto& r = rr[decltype(set_tag)::value % SSETS];
     k0 = k0 < a.K - BKC ? k0 : a.K - BKC;
+    if constexpr (CONV) {
+      // the chunk's tap and first input channel (C_in % BKC == 0: one tap per chunk); one column per patch, its 8 rows
+      // read at the tap's offset -- a clamped address and a select, no branch (column 0 of the row is always readable)
+      const int tap = k0 / a.conv_cin, c0 = k0 - tap * a.conv_cin;
+      const float* __restrict__ base = xb + (int64_t)c0 * a.ldx;
+#pragma unroll
+      for (int p = 0; p < PPT; ++p) {
+        int n, g;
+        patch_of(p, n, g);
+        const int col = (t0 + n) * a.conv_stride + tap * a.conv_dil - a.conv_pad;
+        const bool ok = col >= 0 && col < len;
+        const float* __restrict__ src = base + (int64_t)(8 * g) * a.ldx + (ok ? col : 0);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float v = src[(int64_t)e * a.ldx];
+          r[p][e] = ok ? v : 0.f;
+        }
+      }
+      return;
+    }
     const bool second = DUAL && k0 >= K1;
     const float* __restrict__ base = second ? xb2 + (int64_t)(k0 - K1) * a.ldx2 : xb + (int64_t)k0 * a.ldx;
     const int64_t ld = second ? a.ldx2 : a.ldx;
@@ -236,7 +264,7 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
     const bool masked = second || MASK;
     int n, g;
     patch_of(p, n, g);
-    const bool keep = !masked || (t0 + n < ml);   // MaskedConv1d: x.masked_fill(t >= lens, 0) (jasper.py:113-118)
+    const bool keep = CONV || !masked || (t0 + n < ml);   // (CONV: masked as it is read) MaskedConv1d: x.masked_fill(t >= lens, 0) (jasper.py:113-118)
     float x[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) x[e] = keep ? r[p][4 * h + e] : 0.f;
@@ -284,7 +312,9 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
 
   // A time tile on which every input is zero (past the utterance's length in a ragged batch) has nothing to reduce:
   // its outputs are shift (+ residual) through the ReLU, which is what the epilogue makes of zero accumulators.
-  const int zf = a.zero_from ? max(a.zero_from[b], DUAL ? len2 : 0) : 0x7fffffff;
+  int zf = a.zero_from ? max(a.zero_from[b], DUAL ? len2 : 0) : 0x7fffffff;
+  // CONV: zero_from is the input's; output column t reads input columns from t * stride - pad on
+  if (CONV && a.zero_from) zf = (zf + a.conv_pad + a.conv_stride - 1) / a.conv_stride;
   const int nchunks = t0 >= zf ? 0 : a.K / BKC;
   using S0 = std::integral_constant<int, 0>;
   using S1 = std::integral_constant<int, 1>;
@@ -508,18 +538,18 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
   if (a.amax_y.p) amax_publish(a.amax_y.p, a.amax_y.stride, b, (mb * tiles_t + nt % tiles_t) * NW + wave, ymax, lane);
 }
 
-template <int NW, int TM, int TN, bool MASK, bool RES, bool DUAL, int ARITH>
+template <int NW, int TM, int TN, bool MASK, bool RES, bool DUAL, int ARITH, bool CONV = false>
 int launch_k(const PwArgs& a, hipStream_t st, int* amax_n) {
   using G = Geom<NW, TM, TN, ARITH>;
   const int blocks_m = a.M / G::BM;
-  const int tiles_t = (int)((a.ldx + G::BN - 1) / G::BN);
+  const int tiles_t = (int)(((CONV ? a.conv_cols : a.ldx) + G::BN - 1) / G::BN);
   const int n_blocks = blocks_m * tiles_t * a.batch;
   if (a.amax_y.p) {
     const int n = blocks_m * tiles_t * NW;
     if (n > a.amax_y.stride) return (int)hipErrorInvalidValue;
     if (amax_n) *amax_n = n;
   }
-  auto kern = pw_gemm_split_kernel<NW, TM, TN, MASK, RES, DUAL, ARITH>;
+  auto kern = pw_gemm_split_kernel<NW, TM, TN, MASK, RES, DUAL, ARITH, CONV>;
   static std::atomic<uint64_t> lds_opted{0};   // per device (dyn_lds_opt_in)
   const hipError_t attr = dyn_lds_opt_in(reinterpret_cast<const void*>(kern), (int)G::LDS, lds_opted);
   if (attr != hipSuccess) return (int)attr;
@@ -530,6 +560,10 @@ int launch_k(const PwArgs& a, hipStream_t st, int* amax_n) {
 template <int NW, int TM, int TN, int ARITH>
 int launch_l(const PwArgs& a, hipStream_t st, int* amax_n) {
   const bool mask = a.lens != nullptr, res = a.res != nullptr, dual = a.x2 != nullptr;
+  if (a.conv_cin) {   // K-tap convolution: always masked (lens = the input's), never dual
+    if (res) return launch_k<NW, TM, TN, true, true, false, ARITH, true>(a, st, amax_n);
+    return launch_k<NW, TM, TN, true, false, false, ARITH, true>(a, st, amax_n);
+  }
   if (dual) return launch_k<NW, TM, TN, false, false, true, ARITH>(a, st, amax_n);
   if (mask && res) return launch_k<NW, TM, TN, true, true, false, ARITH>(a, st, amax_n);
   if (mask) return launch_k<NW, TM, TN, true, false, false, ARITH>(a, st, amax_n);
@@ -559,6 +593,9 @@ bool pointwise_split_supported(int M, int K, int K1) {
   return M % 64 == 0 && K % BKC == 0 && (K1 == 0 || K1 % BKC == 0);
 }
 
+// a chunk of the implicit-GEMM convolution must lie inside one tap
+bool conv_split_supported(int M, int cin) { return M % 64 == 0 && cin % BKC == 0; }
+
 // arith: 0 = 3 x bf16 (six products), 1 = 2 x bf16 (three products, reduced), 2 = 2 x fp16 scaled (three products; needs
 // a.amax_x (and a.amax_x2 for a dual source), a.w_inv_scale and the fp16 weight pack).  Returns 0 or a hipError_t.
 // the smallest tile (64 x 32 on two wavefronts) uses the most slots: (M / 64) * (ld / 32) * 2
@@ -569,7 +606,8 @@ int launch_pointwise_split(const PwArgs& args, int arith, hipStream_t st, int* a
   const PwArgs& a = args;
   // the largest tile that divides M and still gives (almost) every one of the 256 CUs a workgroup:
   // 512x128, 256x128, 128x64, 64x32 (the CTC head, 29 or 91 rows padded to 128, runs 128x64 tiles)
-  auto blocks = [&](int bm, int bn) { return (int64_t)(a.M / bm) * ((a.ldx + bn - 1) / bn) * a.batch; };
+  const int64_t cols = a.conv_cin ? a.conv_cols : a.ldx;   // output columns tiled
+  auto blocks = [&](int bm, int bn) { return (int64_t)(a.M / bm) * ((cols + bn - 1) / bn) * a.batch; };
   const int rows[6] = {0, 512, 256, 128, 64, 256};
   int tile = 4;
   if (a.M % 512 == 0 && blocks(512, 128) >= 192) tile = 1;
@@ -598,7 +636,7 @@ int launch_pointwise_split(const PwArgs& args, int arith, hipStream_t st, int* a
   // Small batches (the 64 x 32 tile's territory: <= 5 utterances of 10 s at 512 channels): the whole K range in ONE trip to
   // memory instead of K / 64 dependent chunk steps -- encoder_pw_lat.hip, same bits.  (Devtools: VASR_PW_LAT=0 keeps the chunked
   // kernel.)
-  if (arith == kF16x2 && !force && dev_switches().pw_lat > 0 && tile == 4 && pointwise_latency_supported(a.M, a.K, a.x2 ? a.K1 : 0)) {
+  if (arith == kF16x2 && !force && dev_switches().pw_lat > 0 && tile == 4 && !a.conv_cin && !a.bsx && pointwise_latency_supported(a.M, a.K, a.x2 ? a.K1 : 0)) {
     const int e = launch_pointwise_latency(a, st, amax_n);
     if (e >= 0) return e;
   }

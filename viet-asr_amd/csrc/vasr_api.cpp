@@ -60,6 +60,7 @@ struct ConvLayer {
   float* d_scale = nullptr;  // [m_pad]
   float* d_shift = nullptr;  // [m_pad]
   int step = -1;             // index in the MaskedConv1d length chain
+  int conv_cin = 0;          // non-separable K-tap conv (implicit GEMM over k = tap * conv_cin + c; cin = kernel * conv_cin)
 };
 
 struct SubBlock {
@@ -76,6 +77,14 @@ struct Block {
   ConvLayer fused;          // weights [s1*W1 | s2*W2], scale 1, shift h1 + h2; cin = K1 + K2
   int fused_k1 = 0;
   int first_step = 0;
+  // dense residual (residual_dense): the block's input is pane `pane` of its run's pane buffer [B][pane_c][ld] (-1: not
+  // kept); with dense_panes >= 2 the residual is ONE 1x1 GEMM over channels [0, res.cin) of that buffer (`res` holds
+  // [a_0 W_0 | a_1 W_1 | ...], scale 1, shift sum b_p)
+  int pane = -1, pane_off = 0, pane_c = 0, dense_panes = 0;
+  bool keep_input = false;   // a later block of the run (or this one) reads this block's input as a pane
+  // a residual block that is NOT dense right after a dense run receives the run's pane list and takes its (single) residual
+  // from pane 0, the run's input, not from its own input (parts/jasper.py:428-436: res_out = xs[0])
+  bool res_pane0 = false;
 };
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -102,6 +111,7 @@ struct vasr_handle {
   std::vector<float> fe_window, fe_fb;
   int feat_in = 0, dec_feat_in = 0, num_classes = 0;
   std::vector<Block> blocks;
+  int pane_c_max = 0;   // channels of the dense-residual pane buffer (0: no dense residual GEMM)
   std::vector<LenStep> steps;
   std::map<std::string, HostTensor> weights;
   std::vector<void*> dev_allocs;
@@ -242,29 +252,33 @@ int bn_affine(vasr_handle* h, const std::string& prefix, int c, std::vector<floa
   return 0;
 }
 
-// Last sub-block GEMM and residual GEMM of one JasperBlock as ONE reduction over K1 + K2:
-//   BN1(W1 d) + BN2(W2 x) = [a1*W1 | a2*W2] [d ; x] + (b1 + b2)        (parts/jasper.py:428-439)
-int pack_fused_residual(vasr_handle* h, const std::string& w1_key, const std::string& bn1, const std::string& w2_key,
-                        const std::string& bn2, int cout, int k1, int k2, ConvLayer* L) {
-  const HostTensor *w1, *w2;
-  std::vector<float> a1, b1, a2, b2;
-  int rc;
-  if ((rc = need(h, w1_key, (size_t)cout * k1, &w1)) || (rc = need(h, w2_key, (size_t)cout * k2, &w2)) ||
-      (rc = bn_affine(h, bn1, cout, &a1, &b1)) || (rc = bn_affine(h, bn2, cout, &a2, &b2)))
-    return rc;
-  const int K = k1 + k2;
-  std::vector<float> w((size_t)cout * K);
-  for (int m = 0; m < cout; ++m) {
-    for (int k = 0; k < k1; ++k) w[(size_t)m * K + k] = a1[m] * w1->data[(size_t)m * k1 + k];
-    for (int k = 0; k < k2; ++k) w[(size_t)m * K + k1 + k] = a2[m] * w2->data[(size_t)m * k2 + k];
+// 1x1 convs + BNs over sources concatenated along K as ONE reduction:
+//   sum_p BN_p(W_p x_p) = [a_0*W_0 | a_1*W_1 | ...] [x_0 ; x_1 ; ...] + sum_p b_p        (parts/jasper.py:428-439)
+// Two sources: a JasperBlock's last sub-block GEMM and its residual GEMM (k1_split = K1 of the dual-source kernel); more:
+// the panes of a dense residual (one source, the pane buffer; k1_split = 0).
+struct SumSrc { std::string w_key, bn; int k; };
+int pack_sum_1x1(vasr_handle* h, const std::vector<SumSrc>& src, int cout, int k1_split, ConvLayer* L) {
+  int K = 0, rc;
+  for (const SumSrc& s : src) K += s.k;
+  std::vector<float> w((size_t)cout * K), sh_sum(cout, 0.f);
+  int off = 0;
+  for (const SumSrc& s : src) {
+    const HostTensor* ws;
+    std::vector<float> a, b;
+    if ((rc = need(h, s.w_key, (size_t)cout * s.k, &ws)) || (rc = bn_affine(h, s.bn, cout, &a, &b))) return rc;
+    for (int m = 0; m < cout; ++m) {
+      for (int k = 0; k < s.k; ++k) w[(size_t)m * K + off + k] = a[m] * ws->data[(size_t)m * s.k + k];
+      sh_sum[m] += b[m];
+    }
+    off += s.k;
   }
   L->cin = K;
   L->cout = cout;
   L->m_pad = (int)align_up(cout, 128);
   std::vector<float> wt((size_t)K * L->m_pad, 0.f), sc(L->m_pad, 1.f), sh(L->m_pad, 0.f);
   pack_pointwise_weights(w.data(), cout, K, L->m_pad, wt.data());
-  for (int m = 0; m < cout; ++m) sh[m] = b1[m] + b2[m];
-  if (pointwise_split_supported(L->m_pad, K, k1)) {
+  for (int m = 0; m < cout; ++m) sh[m] = sh_sum[m];
+  if (pointwise_split_supported(L->m_pad, K, k1_split)) {
     std::vector<unsigned short> w3((size_t)K * L->m_pad * 3);
     pack_pointwise_weights_bf16x3(w.data(), cout, K, L->m_pad, w3.data());
     if ((rc = upload(h, w3, &L->d_w3))) return rc;
@@ -274,6 +288,31 @@ int pack_fused_residual(vasr_handle* h, const std::string& w1_key, const std::st
   }
   if ((rc = upload(h, wt, &L->d_w)) || (rc = upload(h, sc, &L->d_scale))) return rc;
   return upload(h, sh, &L->d_shift);
+}
+
+// [cout][cin][kernel] -> the implicit GEMM's [cout][kernel * cin] (k = tap * cin + c) -> the three fragment packs
+int pack_conv(vasr_handle* h, const std::string& key, int cout, int cin, int kernel, ConvLayer* L) {
+  const HostTensor* w;
+  int rc;
+  if ((rc = need(h, key, (size_t)cout * cin * kernel, &w))) return rc;
+  L->m_pad = (int)align_up(cout, 128);
+  if (!conv_split_supported(L->m_pad, cin))
+    return fail(VASR_ERR_UNSUPPORTED, "%s: in_channels %d of a %d-tap conv is not a multiple of 64", key.c_str(), cin, kernel);
+  const int K = kernel * cin;
+  L->cin = K;
+  L->cout = cout;
+  L->conv_cin = cin;
+  std::vector<float> g((size_t)cout * K);
+  pack_conv_gemm_weights(w->data.data(), cout, cin, kernel, g.data());
+  std::vector<float> wt((size_t)K * L->m_pad, 0.f);
+  pack_pointwise_weights(g.data(), cout, K, L->m_pad, wt.data());
+  std::vector<unsigned short> w3((size_t)K * L->m_pad * 3);
+  pack_pointwise_weights_bf16x3(g.data(), cout, K, L->m_pad, w3.data());
+  if ((rc = upload(h, w3, &L->d_w3))) return rc;
+  std::vector<unsigned short> w16((size_t)K * L->m_pad * 2);
+  L->w16_inv = pack_pointwise_weights_f16x2(g.data(), cout, K, L->m_pad, w16.data());
+  if ((rc = upload(h, w16, &L->d_w16))) return rc;
+  return upload(h, wt, &L->d_w);
 }
 
 // [cout][cin][1] -> MFMA A-fragment order
@@ -385,12 +424,16 @@ int build_encoder(vasr_handle* h) {
         if ((rc = fold_bn(h, key, d.filters, S.pw.m_pad, &S.pw))) return rc;
         j += 3;
       } else {
-        if (k != 1 || d.stride != 1)
-          return fail(VASR_ERR_UNSUPPORTED, "block %zu: non-separable conv with kernel %d is not implemented", i, k);
         snprintf(key, sizeof key, "encoder.%zu.mconv.%d.conv.weight", i, j);
-        if ((rc = pack_pointwise(h, key, d.filters, c, &S.pw))) return rc;
+        if (k == 1 && d.stride == 1) {
+          if ((rc = pack_pointwise(h, key, d.filters, c, &S.pw))) return rc;
+          h->steps.push_back(LenStep{1, 1, 1, 0});
+        } else {   // K-tap / strided: implicit GEMM (encoder_pw_split.hip, encoder_pw.hip CONV)
+          if ((rc = pack_conv(h, key, d.filters, c, k, &S.pw))) return rc;
+          S.pw.kernel = k; S.pw.stride = d.stride; S.pw.dilation = d.dilation; S.pw.pad = pad;
+          h->steps.push_back(LenStep{k, d.stride, d.dilation, pad});
+        }
         S.pw.step = step++;
-        h->steps.push_back(LenStep{1, 1, 1, 0});
         snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, j + 1);
         if ((rc = fold_bn(h, key, d.filters, S.pw.m_pad, &S.pw))) return rc;
         j += 2;
@@ -399,7 +442,19 @@ int build_encoder(vasr_handle* h) {
       c = d.filters;
     }
     B.has_res = d.residual != 0;
-    if (B.has_res) {
+    if (B.has_res && B.dense_panes >= 2) {
+      // dense residual: one GEMM over the run's first dense_panes panes (parts/jasper.py:428-439 for each pane)
+      std::vector<SumSrc> src;
+      for (int q = 0; q < B.dense_panes; ++q) {
+        char wk[160], bk[160];
+        snprintf(wk, sizeof wk, "encoder.%zu.res.%d.0.conv.weight", i, q);
+        snprintf(bk, sizeof bk, "encoder.%zu.res.%d.1", i, q);
+        src.push_back(SumSrc{wk, bk, h->blocks[i - B.dense_panes + 1 + q].pane_c});
+      }
+      for (const SumSrc& s : src)
+        if (s.k % 64) return fail(VASR_ERR_UNSUPPORTED, "%s: in_channels %d is not a multiple of 64", s.w_key.c_str(), s.k);
+      if ((rc = pack_sum_1x1(h, src, d.filters, 0, &B.res))) return rc;
+    } else if (B.has_res) {
       snprintf(key, sizeof key, "encoder.%zu.res.0.0.conv.weight", i);
       if ((rc = pack_pointwise(h, key, d.filters, cin, &B.res))) return rc;
       snprintf(key, sizeof key, "encoder.%zu.res.0.1", i);
@@ -408,14 +463,14 @@ int build_encoder(vasr_handle* h) {
       const SubBlock& last = B.subs.back();
       const int k1 = last.pw.cin, k2 = cin;
       const int chunk = d.filters % 512 == 0 ? 128 : (d.filters % 256 == 0 ? 64 : 32);
-      if (d.stride == 1 && k1 % chunk == 0 && k2 % chunk == 0 && h->sw.fused_residual) {
+      if (d.stride == 1 && k1 % chunk == 0 && k2 % chunk == 0 && h->sw.fused_residual && !last.pw.conv_cin && !B.res_pane0) {
         char w1[160], bn1[160], w2[160], bn2[160];
         const int jl = j - (last.separable ? 3 : 2);
         snprintf(w1, sizeof w1, "encoder.%zu.mconv.%d.conv.weight", i, jl + (last.separable ? 1 : 0));
         snprintf(bn1, sizeof bn1, "encoder.%zu.mconv.%d", i, jl + (last.separable ? 2 : 1));
         snprintf(w2, sizeof w2, "encoder.%zu.res.0.0.conv.weight", i);
         snprintf(bn2, sizeof bn2, "encoder.%zu.res.0.1", i);
-        if ((rc = pack_fused_residual(h, w1, bn1, w2, bn2, d.filters, k1, k2, &B.fused))) return rc;
+        if ((rc = pack_sum_1x1(h, {SumSrc{w1, bn1, k1}, SumSrc{w2, bn2, k2}}, d.filters, k1, &B.fused))) return rc;
         B.fused_res = true;
         B.fused_k1 = k1;
       }
@@ -443,15 +498,14 @@ int build_decoder(vasr_handle* h) {
 
 // ---------------- workspace plan ----------------
 struct WsPlan {
-  size_t lens_tab, amax, seq, melp, bufP, bufQ, bufD, bufR, bufS, encp, logits, pred, total;
+  size_t lens_tab, amax, seq, melp, bufP, bufQ, bufD, bufR, bufS, pane, encp, logits, pred, total;
   int64_t T, Tp0, T1, Tp1;
   int amax_stride;   // slots per utterance of one maxima table (kAmaxTabs tables: [tab][B][amax_stride] u32)
 };
 
 int64_t enc_frames(const vasr_handle* h, int64_t t) {
   for (const Block& B : h->blocks)
-    for (const SubBlock& S : B.subs)
-      if (S.separable) t = conv_out_frames(t, S.dw);
+    for (const SubBlock& S : B.subs) t = conv_out_frames(t, S.separable ? S.dw : S.pw);
   return t;
 }
 
@@ -479,9 +533,13 @@ WsPlan plan_ws(const vasr_handle* h, int batch, int64_t T) {
         if (S.separable) {
           t = conv_out_frames(t, S.dw);
           p.amax_stride = std::max(p.amax_stride, depthwise_amax_slots(S.dw.cin, pad_frames(t)));
+        } else if (S.pw.conv_cin) {
+          t = conv_out_frames(t, S.pw);
+          p.amax_stride = std::max(p.amax_stride, 256);   // launch_amax: the maxima of an encoder input no kernel published
         }
         p.amax_stride = std::max(p.amax_stride, pointwise_amax_slots(S.pw.m_pad, pad_frames(t)));
       }
+    if (h->pane_c_max) p.amax_stride = std::max(p.amax_stride, 256);   // launch_amax over the pane buffer
   }
   p.amax = take((size_t)kAmaxTabs * batch * p.amax_stride * 4);
   p.seq = take((size_t)batch * 8);
@@ -492,6 +550,9 @@ WsPlan plan_ws(const vasr_handle* h, int batch, int64_t T) {
   p.bufD = take(h->has_encoder ? mid : 0);
   p.bufR = take(h->has_encoder ? mid : 0);
   p.bufS = take(h->has_encoder ? mid : 0);
+  // dense-residual panes [B][pane_c_max][ld]: ld = the pitch of the run's first block input, which every block of the run
+  // keeps (no stride inside a run; run_encoder checks it)
+  p.pane = take(h->pane_c_max ? (size_t)batch * h->pane_c_max * std::max({p.Tp0, tp_mid, p.Tp1}) * 4 : 0);
   const int c_enc = h->has_encoder ? h->c_last : h->dec_feat_in;
   p.encp = take((size_t)batch * c_enc * p.Tp1 * 4);
   p.logits = take(h->has_decoder ? (size_t)batch * h->num_classes * p.Tp1 * 4 : 0);
@@ -600,6 +661,7 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
     }
     return AmaxTab{};
   };
+  int64_t pane_ld = 0;   // pitch of the current dense run's panes: its first block's input pitch
   for (size_t i = 0; i < h->blocks.size(); ++i) {
     Block& B = h->blocks[i];
     const bool last_block = i + 1 == h->blocks.size();
@@ -612,15 +674,51 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
     int nf = 0;
     for (float* q : bufs) if (q != blk_in && nf < 3) free3[nf++] = q;
     float* R = free3[2];
-    if (B.has_res && !B.fused_res) {
-      // res branch: MaskedConv1d(1x1)(block input, lens_orig) -> BN   (parts/jasper.py:428-436)
+    float* panes = reinterpret_cast<float*>(ws + p.pane);
+    const int64_t pane_bs = (int64_t)h->pane_c_max * cur_ld;   // batch stride of the pane buffer, elements
+    if (B.keep_input && B.pane == 0) pane_ld = cur_ld;
+    // every pane of a run has one pitch (no stride inside a run: vasr_create), which the buffer's layout relies on
+    if ((B.keep_input || B.dense_panes >= 2 || B.res_pane0) && cur_ld != pane_ld)
+      return fail(VASR_ERR_UNSUPPORTED, "block %zu: dense-residual panes of different pitches (%lld, %lld)", i, (long long)pane_ld,
+                  (long long)cur_ld);
+    if (B.keep_input) {
+      // this block's input is pane B.pane of its dense run (parts/jasper.py:446-447: xs + [out])
+      HIP_TRY(hipMemcpy2DAsync(panes + (int64_t)B.pane_off * cur_ld, (size_t)pane_bs * 4, cur, (size_t)B.pane_c * cur_ld * 4,
+                               (size_t)B.pane_c * cur_ld * 4, batch, hipMemcpyDeviceToDevice, st));
+    }
+    if (B.has_res && B.dense_panes >= 2) {
+      // dense residual: sum_p BN_p(W_p mask(x_p)) as one GEMM over the first res.cin channels of the pane buffer, every pane
+      // masked with the block-input lengths (parts/jasper.py:428-436); fp16 split: one scale from the maxima of all panes
       PwArgs a{};
       a.busy_cus = h->busy_cus;
-      a.wt = B.res.d_w; a.x = cur; a.lens = lens(B.first_step); a.scale = B.res.d_scale; a.shift = B.res.d_shift;
+      a.wt = B.res.d_w; a.x = panes; a.bsx = pane_bs; a.lens = lens(B.first_step); a.scale = B.res.d_scale;
+      a.shift = B.res.d_shift; a.res = nullptr; a.y = R; a.M = B.res.m_pad; a.K = B.res.cin; a.batch = batch;
+      a.ldx = cur_ld; a.ldy = cur_ld; a.ldr = 0; a.frames = (int)cur_T; a.store_cols = (int)cur_ld;
+      a.m_store = B.res.m_pad; a.relu = 0;
+      if (want_amax) {
+        a.amax_x = free_tab(AmaxTab{});
+        launch_amax(panes, cur_ld, B.res.cin, (int)cur_T, lens(B.first_step), batch, &a.amax_x, st, pane_bs);
+      }
+      ProfScope ps(h, kProfPointwise, st, 2.0 * B.res.cin * B.res.cout * (double)cur_T * batch, 4.0 * B.res.m_pad * (double)cur_ld * batch);
+      if (run_pointwise(h, a, B.res, st) < 0) return VASR_ERR_HIP;
+    } else if (B.has_res && !B.fused_res) {
+      // res branch: MaskedConv1d(1x1)(block input -- or, right after a dense run, the run's input: pane 0 --, lens_orig) -> BN
+      // (parts/jasper.py:428-436)
+      PwArgs a{};
+      a.busy_cus = h->busy_cus;
+      a.wt = B.res.d_w; a.x = B.res_pane0 ? panes : cur; a.lens = lens(B.first_step); a.scale = B.res.d_scale; a.shift = B.res.d_shift;
       a.res = nullptr; a.y = R; a.M = B.res.m_pad; a.K = B.res.cin; a.batch = batch;
       a.ldx = cur_ld; a.ldy = cur_ld; a.ldr = 0; a.frames = (int)cur_T; a.store_cols = (int)cur_ld;
       a.m_store = B.res.m_pad; a.relu = 0;
       a.amax_x = blk_amax;
+      if (B.res_pane0) {
+        a.bsx = pane_bs;
+        a.amax_x = AmaxTab{};
+        if (want_amax) {
+          a.amax_x = free_tab(AmaxTab{});
+          launch_amax(panes, cur_ld, B.res.cin, (int)cur_T, lens(B.first_step), batch, &a.amax_x, st, pane_bs);
+        }
+      }
       ProfScope ps(h, kProfPointwise, st, 2.0 * B.res.cin * B.res.cout * (double)cur_T * batch,
                    4.0 * B.res.m_pad * (double)cur_ld * batch);   // bytes of class 2 = what the GEMM STORES (its epilogue's share of the time)
       if (run_pointwise(h, a, B.res, st) < 0) return VASR_ERR_HIP;
@@ -722,10 +820,19 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
         gx = D; gx_ld = ld_out; g_T = t_out; gx_amax = am;
       } else {
         g_lens = lens(S.pw.step);  // block input is unmasked: predicate inside the GEMM
+        if (S.pw.conv_cin) {
+          g_T = conv_out_frames(cur_T, S.pw);
+          // fp16 split: an encoder input no kernel published maxima of (the mel features) gets them here
+          if (want_amax && !gx_amax.p) {
+            gx_amax = free_tab(AmaxTab{});
+            launch_amax(cur, cur_ld, S.pw.conv_cin, (int)cur_T, g_lens, batch, &gx_amax, st);
+          }
+        }
       }
       float* dst = free3[flip];
       flip ^= 1;
-      int64_t dst_ld = gx_ld;
+      // (a K-tap conv's output has its own pitch: stride 2 halves the frames)
+      int64_t dst_ld = S.pw.conv_cin ? pad_frames(g_T) : gx_ld;
       if (last_block && last_sub) { dst = out; dst_ld = out_ld; }
       const bool fuse = last_sub && B.fused_res;
       const ConvLayer& W = fuse ? B.fused : S.pw;
@@ -736,10 +843,14 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
       a.y = dst; a.M = W.m_pad; a.K = W.cin; a.batch = batch;
       a.ldx = gx_ld; a.ldy = dst_ld; a.ldr = blk_ld; a.frames = (int)g_T; a.m_store = W.m_pad; a.relu = 1;
       a.store_cols = (dst_ld % kTimeTile == 0) ? (int)dst_ld : (int)g_T;  // port tensors are not padded
+      if (W.conv_cin) {
+        a.conv_cin = W.conv_cin; a.conv_stride = W.stride; a.conv_dil = W.dilation; a.conv_pad = W.pad;
+        a.conv_cols = pad_frames(g_T);
+      }
       // the depthwise output is zero past its lens_out, a masked input past its mask: tiles out there skip their K loop
       a.zero_from = S.separable ? lens(S.dw.step + 1) : g_lens;
       if (fuse) { a.x2 = blk_in; a.lens2 = lens(B.first_step); a.K1 = B.fused_k1; a.ldx2 = blk_ld; }
-      if ((a.res || fuse) && blk_ld != gx_ld)
+      if ((a.res || fuse) && (blk_ld != gx_ld || (W.conv_cin && g_T != cur_T)))
         return fail(VASR_ERR_UNSUPPORTED, "block %zu: residual across a strided block", i);
       a.amax_x = gx_amax;
       a.amax_x2 = fuse ? blk_amax : AmaxTab{};
@@ -831,6 +942,56 @@ int vasr_create(const vasr_model_desc* d, vasr_handle** out) {
       Block B;
       B.d = b;
       h->blocks.push_back(B);
+    }
+    // Dense residual panes, as the reference builds and runs them: every residual_dense block appends its input width to ONE
+    // list shared by all blocks (jasper.py:152-161) and keeps a copy (parts/jasper.py:264); a dense block with residual sums a
+    // 1x1 conv of each entry's pane, xs[p], and hands xs + [out] on, any other block [out] alone (:428-448).  A layout in
+    // which a block's copy is longer than the pane list reaching it raises IndexError in the reference: refused here.
+    std::vector<int> xs_c{d->feat_in};   // channels of the panes reaching the next block
+    int dense_seen = 0, cin = d->feat_in, origin = 0;   // origin: the block whose input is pane 0 of that list
+    for (int i = 0; i < d->n_blocks; ++i) {
+      Block& B = h->blocks[i];
+      const vasr_block_desc& b = B.d;
+      if (!b.residual_dense && b.residual && xs_c.size() > 1) {
+        if (xs_c[0] != cin || b.stride > 1) {
+          delete h;
+          return fail(VASR_ERR_INVALID, "block %d: a residual block after a dense run takes its residual from the run's input "
+                      "(%d channels, block input %d%s) -- the reference fails here", i, xs_c[0], cin, b.stride > 1 ? ", strided" : "");
+        }
+        B.res_pane0 = true;
+        h->blocks[origin].keep_input = true;
+        h->pane_c_max = std::max(h->pane_c_max, xs_c[0]);
+      }
+      if (b.residual_dense) {
+        ++dense_seen;
+        if (b.residual && dense_seen > (int)xs_c.size()) {
+          delete h;
+          return fail(VASR_ERR_INVALID, "block %d: residual_dense block number %d sees %zu residual pane(s): dense blocks must form one "
+                      "contiguous run of residual blocks (the reference fails in JasperBlock.forward)", i, dense_seen, xs_c.size());
+        }
+        if (b.residual && b.stride > 1) {
+          delete h;
+          return fail(VASR_ERR_INVALID, "block %d: a strided block cannot take a dense residual (its panes have other lengths)", i);
+        }
+        B.pane = (int)xs_c.size() - 1;
+        B.pane_c = cin;
+        for (int q = 0; q < B.pane; ++q) B.pane_off += xs_c[q];
+        if (b.residual) B.dense_panes = dense_seen;
+      }
+      if (b.residual_dense && b.residual) {
+        xs_c.push_back(b.filters);
+      } else {
+        xs_c.assign(1, b.filters);
+        origin = i + 1;
+      }
+      cin = b.filters;
+    }
+    // a pane buffer only where some block sums two or more panes; that block's panes are the inputs of the blocks before it
+    for (int i = 0; i < d->n_blocks; ++i) {
+      Block& B = h->blocks[i];
+      if (B.dense_panes < 2) continue;
+      h->pane_c_max = std::max(h->pane_c_max, B.pane_off + B.pane_c);
+      for (int q = 0; q < B.dense_panes; ++q) h->blocks[i - B.dense_panes + 1 + q].keep_input = true;
     }
   }
   if (d->num_classes > 0) {
@@ -1301,6 +1462,8 @@ int vasr_algorithmic_work(const vasr_handle* h, int batch, int64_t samples, doub
         out[1] += 2.0 * S.dw.kernel * S.dw.cin * (double)to * batch;
         out[2] += 4.0 * ((double)S.dw.cin * t + (double)S.dw.cin * to) * batch + 4.0 * S.dw.cin * S.dw.kernel;
         t = to;
+      } else {
+        t = conv_out_frames(t, S.pw);
       }
       out[0] += 2.0 * S.pw.cin * S.pw.cout * (double)t * batch;
     }
@@ -1354,6 +1517,12 @@ int vasr_bench_depthwise_mfma(const float* d_x, const uint32_t* d_taps, const fl
 int vasr_pack_pointwise(const float* h_w, int cout, int cin, int m_pad, float* h_out) {
   if (!h_w || !h_out || cout <= 0 || cin % 8 || m_pad % 32 || m_pad < cout) return fail(VASR_ERR_INVALID, "bad argument");
   pack_pointwise_weights(h_w, cout, cin, m_pad, h_out);
+  return 0;
+}
+
+int vasr_conv_gemm_weights(const float* h_w, int cout, int cin, int kernel, float* h_out) {
+  if (!h_w || !h_out || cout <= 0 || cin <= 0 || kernel <= 0) return fail(VASR_ERR_INVALID, "bad argument");
+  pack_conv_gemm_weights(h_w, cout, cin, kernel, h_out);
   return 0;
 }
 

@@ -186,6 +186,13 @@ struct PwArgs {
   // launch_pointwise_split reports the slots it used through its amax_n argument
   AmaxTab amax_y;
   const int32_t* lens_y;
+  // implicit-GEMM K-tap convolution (conv_cin > 0; both the fp32 and the split kernels): K = taps * conv_cin, reduction
+  // index k = tap * conv_cin + c, x = [B][conv_cin][ldx] read at column t * conv_stride + tap * conv_dil - conv_pad and
+  // zero outside [0, lens[b]) (lens required); conv_cols = output columns to tile (the output's padded frame count);
+  // zero_from = the INPUT's.  Never dual, never the latency kernel.
+  int32_t conv_cin, conv_stride, conv_dil, conv_pad;
+  int64_t conv_cols;
+  int64_t bsx;            // batch stride of x in elements (0: K * ldx) -- the dense-residual pane buffer holds more channels
 };
 void launch_pointwise(const PwArgs& a, hipStream_t st);
 // host: [cout][cin] row-major -> fragment order [m_pad/32][cin/8][64][4] (zero rows past cout)
@@ -195,6 +202,9 @@ void pack_pointwise_weights(const float* w, int cout, int cin, int m_pad, float*
 // arith: 0 = 3 x bf16 (six MFMA products per multiply), 1 = 2 x bf16 (three, reduced precision), 2 = 2 x fp16 scaled
 // (three; needs amax_x / w_inv_scale and the fp16 pack).  Returns 0 or a hipError_t.
 bool pointwise_split_supported(int M, int K, int K1);
+bool conv_split_supported(int M, int cin);
+// host: [cout][cin][kernel] -> the implicit GEMM's [cout][kernel * cin] (k = tap * cin + c), input of the pointwise packers
+void pack_conv_gemm_weights(const float* w, int cout, int cin, int kernel, float* out);
 double launch_mfma_sustained(int gemm_mode, int n_cu, int steps, float* sink, hipStream_t st);
 int launch_pointwise_split(const PwArgs& a, int arith, hipStream_t st, int* amax_n = nullptr);
 // the 2 x fp16 arithmetic on the small-batch latency kernel (encoder_pw_lat.hip), bit-identical results; -1: shape not covered
@@ -204,8 +214,9 @@ int pointwise_amax_slots(int M, int64_t ld);   // slots per utterance the split 
 void pack_pointwise_weights_bf16x3(const float* w, int cout, int cin, int m_pad, unsigned short* out);
 float pack_pointwise_weights_f16x2(const float* w, int cout, int cin, int m_pad, unsigned short* out);   // returns 1 / scale
 // maxima of a contiguous-per-utterance tensor x[b][rows][ld] over columns < lens[b] (or < frames); sets amax->n (<= 256)
+// batch_stride: elements between utterances (0: rows * ld)
 void launch_amax(const float* x, int64_t ld, int rows, int frames, const int32_t* lens, int batch, AmaxTab* amax,
-                 hipStream_t st);
+                 hipStream_t st, int64_t batch_stride = 0);
 
 // ---- fused depthwise + pointwise sub-block, 256 channels (encoder_fused.hip) ----
 struct FusedLaunch {

@@ -29,15 +29,42 @@ def blocks_from_config(jasper_cfg):
         return int(v[0] if isinstance(v, (list, tuple)) else v)
     out = []
     for l in jasper_cfg:
-        for unsupported in ("residual_dense", "se"):
-            if l.get(unsupported, False):
-                raise NotImplementedError(f"JasperBlock option {unsupported!r} is not implemented")
+        if l.get("se", False):
+            raise NotImplementedError("JasperBlock option 'se' is not implemented")
         if l.get("groups", 1) != 1 or l.get("heads", -1) != -1 or float(l.get("kernel_size_factor", 1.0)) != 1.0:
             raise NotImplementedError("groups/heads/kernel_size_factor other than the defaults are not implemented")
         out.append(dict(filters=int(l["filters"]), repeat=int(l["repeat"]), kernel=one(l["kernel"]),
                         stride=one(l["stride"]), dilation=one(l["dilation"]),
-                        residual=int(bool(l["residual"])), separable=int(bool(l.get("separable", False)))))
+                        residual=int(bool(l["residual"])), separable=int(bool(l.get("separable", False))),
+                        residual_dense=int(bool(l.get("residual_dense", False)))))
+    check_dense_layout(out)
     return out
+
+
+def check_dense_layout(blocks, feat_in=None):
+    """Raise ValueError for the dense-residual layouts the reference builds but cannot run (JasperBlock.forward indexes
+    xs[p] for every copied pane, parts/jasper.py:428-436, and only a dense block WITH residual hands xs + [out] on,
+    :446-447): a dense block after a break in the run, after a dense block without residual, or a strided one.  A residual
+    block that is not dense right after a dense run takes its residual from the run's input, xs[0] (:428-436): it must have
+    that many input channels and no stride (``feat_in``: the encoder input width, for a run that starts at block 0)."""
+    xs, seen, origin_c = 1, 0, feat_in
+    for i, b in enumerate(blocks):
+        cin = blocks[i - 1]["filters"] if i else feat_in
+        width_differs = origin_c is not None and cin is not None and origin_c != cin     # (None: encoder input width unknown)
+        if not b.get("residual_dense") and b["residual"] and xs > 1 and (b["stride"] > 1 or width_differs):
+            raise ValueError(f"block {i}: a residual block after a dense run takes its residual from the run's input "
+                             f"({origin_c} channels, block input {cin}, stride {b['stride']}) -- the reference fails here")
+        if b.get("residual_dense"):
+            seen += 1
+            if b["residual"] and seen > xs:
+                raise ValueError(f"block {i}: residual_dense block number {seen} would sum {seen} panes but only {xs} reach it -- "
+                                 "dense blocks must form one contiguous run of residual blocks (the reference fails here)")
+            if b["residual"] and b["stride"] > 1:
+                raise ValueError(f"block {i}: a strided block cannot take a dense residual (its panes have other lengths)")
+        if b.get("residual_dense") and b["residual"]:
+            xs += 1
+        else:
+            xs, origin_c = 1, b["filters"]
 
 
 def _pcm_to_float(s):

@@ -22,6 +22,10 @@ import numpy as np
 # random BN statistics below (measured: 0.85 -> 2.4 for 12x1, 0.85 -> 6 for 15x5).
 G_MAIN = 1.19
 G_RES = 0.7
+# Jasper (non-separable K-tap convs, dense residuals): one conv per sub-block instead of two, so a larger gain; a dense
+# residual's panes share G_RES / sqrt(panes) (keeps the 54-layer jasper10x5dr's activations O(1)).  Only keys the
+# QuartzNet layouts never have use these: their streams are unchanged.
+G_CONV = 1.3
 
 
 def _rs(key, seed):
@@ -63,6 +67,7 @@ def encoder_state_dict(jasper_cfg, feat_in, seed=0):
     """numpy state_dict for JasperEncoder(jasper=jasper_cfg, feat_in=feat_in)."""
     sd = {}
     cin = feat_in
+    residual_panes = []    # JasperEncoder's shared list (jasper.py:152-161)
     for i, l in enumerate(jasper_cfg):
         cout, rep, k = l["filters"], l["repeat"], kernel_of(l)
         sep = l.get("separable", False)
@@ -76,16 +81,22 @@ def encoder_state_dict(jasper_cfg, feat_in, seed=0):
                 _bn(f"{p}.{j + 2}", seed, cout, sd)
                 j += 3
             else:
-                sd[f"{p}.{j}.conv.weight"] = _conv_weight(f"{p}.{j}.conv.weight", seed, cout, c, k, gain=G_MAIN)
+                sd[f"{p}.{j}.conv.weight"] = _conv_weight(f"{p}.{j}.conv.weight", seed, cout, c, k,
+                                                          gain=G_MAIN if k == 1 else G_CONV)
                 _bn(f"{p}.{j + 1}", seed, cout, sd)
                 j += 2
             if r != rep - 1:
                 j += 2  # activation + dropout slots
             c = cout
+        panes = [cin]
+        if l.get("residual_dense", False):
+            residual_panes.append(cin)
+            panes = list(residual_panes)
         if l["residual"]:
-            p = f"encoder.{i}.res.0"
-            sd[f"{p}.0.conv.weight"] = _conv_weight(f"{p}.0.conv.weight", seed, cout, cin, 1, gain=G_RES)
-            _bn(f"{p}.1", seed, cout, sd)
+            for q, ip in enumerate(panes):
+                p = f"encoder.{i}.res.{q}"
+                sd[f"{p}.0.conv.weight"] = _conv_weight(f"{p}.0.conv.weight", seed, cout, ip, 1, gain=G_RES / np.sqrt(len(panes)))
+                _bn(f"{p}.1", seed, cout, sd)
         cin = cout
     return sd
 
