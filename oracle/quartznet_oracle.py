@@ -220,17 +220,24 @@ def _first(v):
     return v[0] if isinstance(v, (list, tuple)) else v
 
 
-def jasper_block_forward(x, lens, sd, i, lcfg):
-    """JasperBlock.forward (parts/jasper.py:408-448) for the layouts the shipped configs use:
-    residual_mode='add', no dense residual, no SE, groups=1, heads=-1, activation ReLU,
-    dropout = identity (eval)."""
+def jasper_block_forward(x, lens, sd, i, lcfg, panes=None):
+    """JasperBlock.forward (parts/jasper.py:408-448) for the layouts the shipped configs and the Jasper-DR layouts use:
+    residual_mode='add', no SE, groups=1, heads=-1, activation ReLU, dropout = identity (eval).
+
+    panes: the block's input list (the reference's ``xs``, parts/jasper.py:411-414) -- None means ``[x]``.  The convs
+    read its last entry (``x``, :417).  Residual p (``encoder.{i}.res.{p}``) is BN(1x1 conv(mask(panes[p]))) with
+    every pane masked at the block's input lengths (:428-436), so a dense block sums one term per pane it receives, and a
+    block with a single residual conv that sits right after a dense run takes panes[0], the run's input.  Returns
+    (output, lengths); encoder_forward builds the next block's list."""
+    xs = [x] if panes is None else list(panes)
+    x = xs[-1]
     k = _first(lcfg["kernel"])
     if k % 2 == 0:
         k += 1
     stride, dil = _first(lcfg["stride"]), _first(lcfg["dilation"])
     pad = get_same_padding(k, stride, dil)
     rep, sep = lcfg["repeat"], lcfg.get("separable", False)
-    lens_orig, x_in = lens, x
+    lens_orig = lens
     out, j = x, 0
     for r in range(rep):
         p = f"encoder.{i}.mconv"
@@ -248,25 +255,32 @@ def jasper_block_forward(x, lens, sd, i, lcfg):
             out = F.relu(out)
             j += 2
     if lcfg["residual"]:
-        p = f"encoder.{i}.res.0"
-        res, _ = masked_conv1d(x_in, lens_orig, _t(sd[f"{p}.0.conv.weight"], x.dtype))
-        res = _bn_eval(res, sd, f"{p}.1")
-        out = out + res                                                        # :438-439
+        n_res = len(xs) if lcfg.get("residual_dense", False) else 1      # one residual conv per pane (jasper.py:152-161)
+        for q in range(n_res):
+            p = f"encoder.{i}.res.{q}"
+            res, _ = masked_conv1d(xs[q], lens_orig, _t(sd[f"{p}.0.conv.weight"], x.dtype))
+            res = _bn_eval(res, sd, f"{p}.1")
+            out = out + res                                                    # :438-439
     return F.relu(out), lens                                                   # :444 mout
 
 
 def encoder_forward(mel, length, sd, jasper_cfg, dtype=torch.float32):
-    """JasperEncoder.forward (jasper.py:198-204): Sequential of JasperBlocks.
+    """JasperEncoder.forward (jasper.py:198-204): Sequential of JasperBlocks passing a LIST of tensors.
+    A block with residual_dense and a residual appends its output to the list it received (parts/jasper.py:446-447: the
+    list grows by one pane per dense block); every other block passes on a list of its output alone.  The encoder returns
+    the last entry.
     Returns (outputs [B,C,T'] f32, encoded_lengths [B] float32 -- quirk Q3).
     dtype=torch.float64 runs the SAME graph in double precision: not the reference's arithmetic (that is float32, the
     default) but the reference's function without its rounding -- the tests use it to tell a frame on which two float32
     computations may legitimately disagree (a top-2 tie inside float32 rounding) from a wrong answer."""
     x = torch.as_tensor(mel).to(dtype)
     lens = torch.as_tensor(length)
+    xs = [x]
     with torch.no_grad():
         for i, l in enumerate(jasper_cfg):
-            x, lens = jasper_block_forward(x, lens, sd, i, l)
-    return x, lens
+            out, lens = jasper_block_forward(xs[-1], lens, sd, i, l, panes=xs)
+            xs = xs + [out] if (l["residual"] and l.get("residual_dense", False)) else [out]
+    return xs[-1], lens
 
 
 # --------------------------------------------------------------------------- A9-A11

@@ -5,7 +5,7 @@ container only; shims and module construction from make_golden.py).
     python tests/golden/make_golden_jasper.py [case ...]     # needs /root/reference
 
 Jasper layouts: non-separable K-tap convolutions (stride 2, dilation 2) and dense residuals (JasperEncoder's
-residual_dense, jasper.py:152-161, parts/jasper.py:264-288, :408-448), which the oracle does not restate.  Inputs and
+residual_dense, jasper.py:152-161, parts/jasper.py:264-288, :408-448).  Inputs and
 weights are NOT stored -- they are regenerated from viet-asr_amd/synth.py seeds; stored are the outputs of the float32
 reference (mel, enc_len, log-probs, predictions, transcripts) and, from the same modules after ``.double()``, the float64
 top-2 margin of every frame (a frame whose margin lies inside float32 round-off may legitimately decode either way).

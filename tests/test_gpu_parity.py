@@ -635,7 +635,8 @@ def test_strongly_ragged_batch_skipped_tiles_match_oracle(gpu):
     assert clear.float().mean() > 0.95
 
 
-@pytest.mark.parametrize("model,B,L", [("quartznet12x1_vi", 3, 20321), ("quartznet15x5", 2, 48000), ("quartznet12x1_vi", 1, 257)])
+@pytest.mark.parametrize("model,B,L", [("quartznet12x1_vi", 3, 20321), ("quartznet15x5", 2, 48000), ("quartznet12x1_vi", 1, 257),
+                                     ("jasper10x5dr", 3, 20321), ("jasper10x5dr", 1, 257)])
 def test_no_writes_outside_the_workspace_and_the_outputs(gpu, model, B, L):
     """Every buffer the fused call writes sits between two guard regions holding a sentinel; nothing outside the
     declared sizes (vasr_workspace_bytes, [B][T'] outputs) may change.  The scratch itself starts filled with NaNs and
@@ -645,7 +646,7 @@ def test_no_writes_outside_the_workspace_and_the_outputs(gpu, model, B, L):
     cfg = configs.builtin(model)
     jas = cfg["JasperEncoder"]["jasper"]
     V1 = len(cfg["labels"]) + 1
-    eng = _engine(cfg, synth.encoder_state_dict(jas, 64, 7), synth.decoder_state_dict(1024, V1, 7))
+    eng = _engine(cfg, synth.encoder_state_dict(jas, 64, 7), synth.decoder_state_dict(jas[-1]["filters"], V1, 7))
     sig, lens = synth.audio_batch(B, L, 7, ragged=B > 1)
     wav, ln = torch.from_numpy(sig).to(gpu), torch.from_numpy(lens).to(gpu)
     _, t1 = eng.frames(L)

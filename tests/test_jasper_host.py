@@ -147,3 +147,70 @@ def test_abi_8_is_consistent():
     fields = re.findall(r"int32_t (\w+);", body)
     assert fields == [f for f, _ in _lib.BlockDesc._fields_]
     assert fields[-1] == "residual_dense"
+
+
+JASPER_FIXTURES = ("jasper_10x5dr_b2_ragged", "jasper_dr3_from_mel_b3", "jasper_k11_s2_b3", "jasper_k29_d2_b3",
+                   "jasper_dense_then_plain_b3")
+
+
+@pytest.mark.parametrize("name", JASPER_FIXTURES)
+def test_oracle_runs_dense_residuals_like_the_reference(name):
+    """oracle.encoder_forward + decoder_forward on the reference's own mel features reproduce what the imported reference
+    computed (tests/golden/make_golden_jasper.py): float32 log-probs to float32 round-off, its greedy predictions and
+    encoded lengths, and in float64 its argmax and top-2 margins.  Three fixtures carry dense residuals (a run after a
+    strided prologue, a run that starts at the mel input, a plain residual block after a run): this pins the oracle's pane
+    list, which the GPU tests of the Jasper layouts then use as their reference at shapes no fixture has."""
+    import torch
+    from oracle import quartznet_oracle as O
+    g = dict(np.load(os.path.join(HERE, "golden", name + ".npz")))
+    src = json.loads(str(g["definition"]))
+    cfg = configs.builtin(src) if isinstance(src, str) else configs.jasper_definition(src)
+    jas = cfg["JasperEncoder"]["jasper"]
+    seed = int(g["seed"])
+    enc_sd = synth.encoder_state_dict(jas, 64, seed)
+    dec_sd = synth.decoder_state_dict(jas[-1]["filters"], len(cfg["labels"]) + 1, seed)
+    seq = torch.from_numpy(np.ceil(g["lens"] / 160).astype(np.int64))     # get_seq_len (features.py:238-239)
+    enc, enc_len = O.encoder_forward(g["mel"], seq, enc_sd, jas)
+    logp = O.decoder_forward(enc, dec_sd).numpy()
+    assert logp.shape == g["logp"].shape
+    # (the same ATen CPU calls in the same order: measured bit-identical; the bound leaves room for another BLAS)
+    assert np.abs(logp - g["logp"]).max() <= 2e-6 * np.abs(g["logp"]).max()
+    assert np.array_equal(logp.argmax(-1), g["pred"])
+    assert np.array_equal(enc_len.numpy().astype(np.float32), g["enc_len"].astype(np.float32))
+    enc64, _ = O.encoder_forward(g["mel"], seq, enc_sd, jas, dtype=torch.float64)
+    logp64 = O.decoder_forward(enc64, dec_sd)
+    assert np.array_equal(logp64.argmax(-1).numpy(), g["pred64"])
+    top2 = torch.topk(logp64, 2, dim=-1).values
+    assert np.abs((top2[..., 0] - top2[..., 1]).numpy() - g["margin64"]).max() <= 1e-9
+
+
+def test_oracle_dense_pane_list():
+    """The pane list on a small layout, checked term by term: a dense block's residual sums one BN(1x1 conv) per pane it
+    receives, and the plain residual block after the run takes pane 0 (the run's input)."""
+    import torch
+    import torch.nn.functional as F
+    from oracle import quartznet_oracle as O
+    jas = [_blk(64, kernel=3, residual=False), _blk(64, kernel=3, dense=True), _blk(64, kernel=5, dense=True),
+           _blk(64, kernel=3)]
+    sd = synth.encoder_state_dict(jas, 64, 5)
+    x = torch.from_numpy(np.random.default_rng(5).standard_normal((2, 64, 40)).astype(np.float64))
+    lens = torch.tensor([40, 23])
+    want, _ = O.encoder_forward(x, lens, sd, jas, dtype=torch.float64)
+
+    def conv_bn(i, j, inp, k):        # block i's mconv.j conv (K taps, same padding) + BN, masked input
+        mask = (torch.arange(inp.shape[2]) < lens[:, None])[:, None, :]
+        w = torch.from_numpy(np.asarray(sd[f"encoder.{i}.mconv.{j}.conv.weight"])).double()
+        y = F.conv1d(inp * mask, w, padding=k // 2)
+        return O._bn_eval(y, sd, f"encoder.{i}.mconv.{j + 1}")
+
+    def res(i, q, inp):
+        mask = (torch.arange(inp.shape[2]) < lens[:, None])[:, None, :]
+        w = torch.from_numpy(np.asarray(sd[f"encoder.{i}.res.{q}.0.conv.weight"])).double()
+        return O._bn_eval(F.conv1d(inp * mask, w), sd, f"encoder.{i}.res.{q}.1")
+
+    p0 = F.relu(conv_bn(0, 0, x, 3))
+    p1 = F.relu(conv_bn(1, 0, p0, 3) + res(1, 0, p0))
+    p2 = F.relu(conv_bn(2, 0, p1, 5) + res(2, 0, p0) + res(2, 1, p1))
+    y = F.relu(conv_bn(3, 0, p2, 3) + res(3, 0, p0))
+    assert "encoder.3.res.1.0.conv.weight" not in sd
+    assert torch.allclose(want, y, rtol=0, atol=1e-12)
