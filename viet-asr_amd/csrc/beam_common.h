@@ -1,7 +1,8 @@
 // Device-side pieces shared by the beam-search kernels (beam_wave.hip: one wavefront per utterance, batches;
 // beam_group.hip: an utterance on four wavefronts of a compute unit, the serving latency): hashing,
 // order-preserving score bits, the hashed back-off n-gram model (KenLM BaseScore semantics, pyctcdecode's LanguageModel.score
-// on top), log(r >= 1) in fp64 without the library call, and wavefront-wide scans / reductions on the DPP data path.
+// on top), log(r >= 1) in fp64 without the library call, wavefront-wide scans / reductions on the DPP data path -- and the
+// steps of the search both kernels run (beam layout, children, LM scoring, radix-select digits, final pass and trace-back).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -262,6 +263,357 @@ __device__ inline long long wave_max_i64(long long v) {
   return (long long)((((unsigned long long)hmax << 32) | lmax) ^ 0x8000000000000000ull);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The steps both kernels run, written once: the two kernels give the same bits because they run this code.  Templated on
+// the kernel's LDS struct (beam_wave.hip WaveLds, beam_group.hip GroupLds<W>), whose beam fields have the same names and
+// layout: key / whash / logit / lm_text / meta / ctx / commit_lmd / commit_wid [2][kMaxBeams] (buffer cur holds the beams of
+// the current frame), the merge table tkey, sel_lgt / sel_tot / fin [kMaxBeams] and cmix [kMaxClasses].
+// ---------------------------------------------------------------------------------------------------------------------------
+
+constexpr int kTbRows = 12;               // back-pointer rows per trace-back batch (6 KB, two batches in LDS)
+constexpr int kLpFrames = 8;              // frames of log-probs per staging batch
+constexpr int kLpRegs = kLpFrames * kMaxClasses / 64;   // floats a lane holds of the batch in flight
+constexpr int kChars = 3072;              // characters of a transcript assembled in LDS (longer ones go through HBM)
+
+// a beam's meta word: (last + 1) [7:0] (0 = none, blank = V + 1) | wlen [23:8] | cached [24] | commit_valid [25] | pending
+// word is "OOV" [26] (is_oov of pyctcdecode's score_partial_token: always with no unigram list, else "not a node of the
+// character trie")
+constexpr unsigned kMetaCached = 1u << 24, kMetaCommit = 1u << 25, kMetaOov = 1u << 26;
+constexpr int kSrcOov = 1 << 16;          // a pair record (beam << 8 | class) carries its child's "OOV" bit here
+__device__ inline int meta_last(unsigned m) { return (int)(m & 0xffu) - 1; }
+__device__ inline int meta_wlen(unsigned m) { return (int)((m >> 8) & 0xffffu); }
+__device__ inline unsigned make_meta(int last, int wlen, unsigned flags) {
+  return (unsigned)(last + 1) | ((unsigned)min(wlen, 0xffff) << 8) | flags;
+}
+
+// Orders the LDS traffic of a wavefront's phases for the COMPILER (the hardware executes one wavefront's LDS operations in
+// order): lanes read what other lanes of the same wavefront wrote, which per-thread alias analysis cannot see.
+__device__ inline void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ inline int lane_id() { return (int)(threadIdx.x & 63); }
+__device__ inline int rank_in(unsigned long long mask) {   // set bits of `mask` below this lane
+  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+}
+
+// Table key of pair src = (beam bi << 8 | character c) -- (prefix text, last character): the prefix grows unless c is blank,
+// a repeat, or a space with no word pending; the "last character" part is a per-class constant (cmix).  The expand steps
+// form the same key inline, next to the home slot of the pair.
+template <class L>
+__device__ __forceinline__ unsigned long long pair_key(const L& S, int cur, int V, int space_id, int src) {
+  const int bi = (src >> 8) & 255, c = src & 255;
+  const unsigned m = S.meta[cur][bi];
+  const bool grows = !(c == V || c == meta_last(m)) && !(c == space_id && meta_wlen(m) == 0);
+  const unsigned long long key = S.key[cur][bi];
+  return ((grows ? hmix(key, (unsigned long long)c) : key) ^ S.cmix[c]) | 1ull;
+}
+
+// One new beam at rank r from pair src = (parent bi << 8 | character c) with merged logit bits lgt: the parent's fields are
+// gathered from buffer cur, the child goes to the other one, one back-pointer word per rank and frame (row t of bp).
+// Returns whether c is a character (not blank).
+template <class L>
+__device__ __forceinline__ bool build_child(L& S, int cur, int V, int space_id, bool use_lm, unsigned int* bp, int t, int r,
+                                            int src, long long lgt, bool has_space) {
+  const int nxt = cur ^ 1;
+  const int bi = (src >> 8) & 255, c = src & 255;
+  const unsigned m = S.meta[cur][bi];
+  const int last = meta_last(m), wlen = meta_wlen(m);
+  const bool stay = (c == V || c == last);
+  unsigned long long key = S.key[cur][bi], whash = S.whash[cur][bi];
+  float lm_text = S.lm_text[cur][bi];
+  const int4 ctx_p = *reinterpret_cast<const int4*>(&S.ctx[cur][bi][0]);
+  int4 ctx_n = ctx_p;
+  const float p_lmd = S.commit_lmd[cur][bi];
+  const int p_wid = S.commit_wid[cur][bi];
+  int wlen_new = wlen;
+  unsigned int appended = 0;
+  unsigned flags = (src & kSrcOov) ? kMetaOov : 0u;       // (the score step decided it: same pending word, same bit)
+  if (stay) {
+    // same text and pending word as the parent: in the LM cache if the parent was, or if this frame put it there; the
+    // commit score of the pending word is inherited with them
+    if ((m & kMetaCached) || (has_space && wlen > 0)) flags |= kMetaCached;
+    flags |= m & kMetaCommit;
+  } else if (c == space_id) {
+    if (wlen > 0) {
+      key = hmix(key, (unsigned long long)c);
+      appended = c + 1;
+      if (use_lm) {
+        lm_text += p_lmd;
+        ctx_n = make_int4(ctx_p.y, ctx_p.z, ctx_p.w, p_wid);
+      }
+      wlen_new = 0; whash = kFnvOffset;
+    }
+  } else {
+    key = hmix(key, (unsigned long long)c);
+    whash = hmix(whash, (unsigned long long)c);
+    wlen_new = wlen + 1;
+    appended = c + 1;
+  }
+  S.key[nxt][r] = key; S.whash[nxt][r] = whash;
+  S.logit[nxt][r] = __longlong_as_double(lgt);
+  S.lm_text[nxt][r] = lm_text;
+  S.meta[nxt][r] = make_meta(c, wlen_new, flags);
+  *reinterpret_cast<int4*>(&S.ctx[nxt][r][0]) = ctx_n;
+  S.commit_lmd[nxt][r] = p_lmd;
+  S.commit_wid[nxt][r] = p_wid;
+  bp[(int64_t)t * kMaxBeams + r] = ((unsigned)bi << 8) | appended;
+  return c != V;
+}
+
+// Step 2 for live beam i of a frame with ' ' among its candidates: returns whether "text + pending word" enters
+// pyctcdecode's LM score cache (the log, key in *h: once per lineage), and gives the pending word the LM score a commit
+// would add (commit_lmd / commit_wid, meta bit kMetaCommit: once per (text, word), children that keep both inherit it).
+template <class L>
+__device__ __forceinline__ bool lm_commit_step(L& S, int cur, int i, int space_id, const LmView& lm, unsigned long long* h) {
+  const unsigned m = S.meta[cur][i];
+  if (meta_wlen(m) == 0) return false;
+  *h = hmix(S.key[cur][i], (unsigned long long)space_id) | 1ull;
+  if (!(m & kMetaCommit)) {
+    int ctx[kMaxCtx];
+#pragma unroll
+    for (int q = 0; q < kMaxCtx; ++q) ctx[q] = S.ctx[cur][i][q];
+    int w;
+    S.commit_lmd[cur][i] = lm_word_score(lm, ctx, S.whash[cur][i], false, &w);
+    S.commit_wid[cur][i] = w;
+    S.meta[cur][i] = m | kMetaCommit;
+  }
+  return !(m & kMetaCached);
+}
+
+// The LM part of pair (parent bi, character c)'s combined score: the LM score of the parent's committed text, pyctcdecode's
+// partial-word penalty of the child's pending word and, when ' ' commits a word, its commit score (filled by step 2).  The
+// child's is_oov goes into *src (kSrcOov).  wnew / tfirst: the child's pending-word hash and its trie home bucket, requested
+// by the expand step (read only with a trie).  Every lane of the wavefront calls it (a ballot inside).
+template <class L>
+__device__ __forceinline__ float pair_lm_part(const L& S, int cur, int bi, int c, int V, int space_id, const LmView& lm,
+                                              bool trie, unsigned long long wnew, ulonglong2 tfirst, int* src) {
+  const unsigned m = S.meta[cur][bi];
+  const int last = meta_last(m), wlen = meta_wlen(m);
+  const bool stay = (c == V || c == last);
+  const int wlen_new = stay ? wlen : (c == space_id ? 0 : wlen + 1);
+  const float commit = S.commit_lmd[cur][bi];
+  // is_oov of the child's pending word: the parent's when the word stays; once outside the trie, outside for good
+  bool oov = true;
+  if (trie) {
+    if (stay) oov = (m & kMetaOov) != 0u;
+    else if (c != space_id && !(wlen > 0 && (m & kMetaOov))) oov = !trie_has_node(lm, wnew, tfirst);
+  }
+  if (oov) *src |= kSrcOov;
+  // partial_penalty(unk_offset, wlen_new, oov), its division only when some lane's pending word is longer than six
+  // characters (as a select the compiler runs the ~12-instruction division in every frame)
+  float pen = (wlen_new > 0 && oov) ? lm.unk_offset : 0.f;
+  if (__ballot(wlen_new > 6) != 0ull) pen = wlen_new > 6 ? pen * (float)wlen_new / 6.0f : pen;
+  return S.lm_text[cur][bi] + pen + ((!stay && c == space_id && wlen > 0) ? commit : 0.f);
+}
+
+// One digit of a radix select: the bucket that holds the want-th largest key.  Lane l owns buckets 255 - 4 l ... 252 - 4 l,
+// counts cnt[0..3] (the largest digit first), and `above` keys lie in the buckets of the lanes before it; exactly one lane
+// finds the bucket (more keys than wanted, want >= 1).  `want` becomes the rank inside the bucket; *whole: the whole
+// bucket is taken.
+__device__ __forceinline__ int radix_bucket(const int (&cnt)[4], int above, int* want, int* whole) {
+  int f_bucket = -1, f_want = 0, f_whole = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (above < *want && *want <= above + cnt[j]) { f_bucket = 255 - (4 * lane_id() + j); f_want = *want - above; f_whole = cnt[j] == *want - above; }
+    above += cnt[j];
+  }
+  const unsigned long long fm = __ballot(f_bucket >= 0);
+  const int fl = __ffsll((long long)fm) - 1;
+  const int bucket = __builtin_amdgcn_readlane(f_bucket, fl);
+  *want = __builtin_amdgcn_readlane(f_want, fl);
+  *whole = __builtin_amdgcn_readlane(f_whole, fl);
+  return bucket;
+}
+
+// The final pass of utterance b, ONE wavefront (the caller has made every back-pointer row and log entry of the search
+// visible to it): commit pending words (LM score with </s>), merge identical texts, pick the best, trace it back and write
+// out_ids / out_len / out_score.  The beams are buffer cur (nb of them), eoslog holds n_log keys; mark: an int[kTab] of the
+// kernel's LDS that is free now, kTab = the size of the (empty) merge table S.tkey, whose words the pending-word lookup
+// and then the trace-back batches use; overflow: the search lost a merge contributor, reported as out_len = -1.
+template <class L, int kTab>
+__device__ __forceinline__ void final_pass(L& S, int (&mark)[kTab], int cur, int nb, int n_log, bool overflow, int space_id,
+                                           bool use_lm, const LmView& lm, unsigned long long* eoslog, const unsigned int* bp,
+                                           int frames, int frames_ld, int b, int32_t* out_ids, int32_t* out_len,
+                                           float* out_score) {
+  static_assert(sizeof(S.tkey) == sizeof(unsigned long long) * kTab, "mark[] has a cell per merge-table slot");
+  const int lane = lane_id();
+  // Is "text + pending word" in pyctcdecode's LM cache (then its cached score, WITHOUT </s>, is what the final pass
+  // uses)?  Known for beams whose own lineage put it there (`cached`); the others look their hash up in eoslog: their
+  // hashes go into the (idle, empty) merge table, the wavefront walks the log and marks the hashes it meets.
+  int in_cache[2] = {0, 0};
+  if (use_lm) {
+    int myslot[2] = {-1, -1};
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int i = lane + 64 * j;
+      if (i < nb) {
+        const unsigned m = S.meta[cur][i];
+        if (meta_wlen(m) > 0) {
+          in_cache[j] = (m & kMetaCached) ? 1 : 0;
+          if (!in_cache[j] && n_log > 0) {
+            const unsigned long long k = hmix(S.key[cur][i], (unsigned long long)space_id) | 1ull;
+            int q = (int)((k >> 17) & (kTab - 1));
+            while (true) {
+              const unsigned long long old = atomicCAS(&S.tkey[q], 0ull, k);
+              if (old == 0ull || old == k) break;
+              q = (q + 1) & (kTab - 1);
+            }
+            myslot[j] = q;
+          }
+        }
+      }
+    }
+    for (int i = lane; i < kTab; i += 64) mark[i] = 0;
+    wave_sync();
+    for (int q = lane; q < n_log; q += 64) {
+      const unsigned long long k = __hip_atomic_load(&eoslog[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      for (int i = (int)((k >> 17) & (kTab - 1));; i = (i + 1) & (kTab - 1)) {
+        const unsigned long long e = S.tkey[i];
+        if (e == k) { mark[i] = 1; break; }
+        if (e == 0) break;
+      }
+    }
+    wave_sync();
+#pragma unroll
+    for (int j = 0; j < 2; ++j) if (myslot[j] >= 0) in_cache[j] = mark[myslot[j]];
+    wave_sync();
+  }
+  // per beam: combined final score, final text key, last-frame combined score (pyctcdecode keeps its beams sorted by it)
+  double* fin = S.fin;                                                     // [kMaxBeams]
+  unsigned long long* fkey = reinterpret_cast<unsigned long long*>(S.sel_lgt);   // [kMaxBeams]
+  double* frank = reinterpret_cast<double*>(S.sel_tot);                    // [kMaxBeams]
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int i = lane + 64 * j;
+    if (i < nb) {
+      const unsigned m = S.meta[cur][i];
+      const int wlen = meta_wlen(m);
+      double total = S.logit[cur][i];
+      if (use_lm) {
+        float lmv = S.lm_text[cur][i];
+        if (wlen > 0) {
+          int ctx[kMaxCtx], wid;
+#pragma unroll
+          for (int q = 0; q < kMaxCtx; ++q) ctx[q] = S.ctx[cur][i][q];
+          lmv += lm_word_score(lm, ctx, S.whash[cur][i], !in_cache[j], &wid);
+        }
+        total += (double)lmv;
+      }
+      fin[i] = total;
+      fkey[i] = wlen > 0 ? hmix(S.key[cur][i], (unsigned long long)space_id) : S.key[cur][i];
+      frank[i] = S.logit[cur][i] + (use_lm ? (double)(S.lm_text[cur][i] + partial_penalty(lm.unk_offset, wlen, (m & kMetaOov) != 0u)) : 0.0);
+    }
+  }
+  wave_sync();
+  // Merge by text: log-sum-exp of the LOGIT scores, as pyctcdecode does.  "abc" with the word still pending and "abc "
+  // with it committed are the same final text but not the same LM part (only the pending word is scored with </s>):
+  // pyctcdecode's _merge_beams overwrites the group's entry with every further member it meets while walking its
+  // score-sorted beam list, so the member with the LOWEST last-frame score provides the LM part.  Every lane takes the
+  // groups whose first member it owns; the best group is the first maximum in beam order.
+  // (Exact ties -- of the last-frame scores inside a group, of the groups' merged scores -- go to the larger key, not to the
+  // earlier beam: the beams' order is not the same in the two kernels, see their selects.)
+  double my_score = -1e300;
+  unsigned long long my_key = 0;
+  int my_first = 0x7fffffff;
+#pragma unroll 1
+  for (int i = lane; i < nb; i += 64) {
+    const unsigned long long k = fkey[i];
+    bool first = true;
+    for (int j = 0; j < i; ++j) if (fkey[j] == k) { first = false; break; }
+    if (!first) continue;
+    double m = S.logit[cur][i];
+    int rep = i;
+    for (int j = i + 1; j < nb; ++j)
+      if (fkey[j] == k) {
+        m = fmax(m, S.logit[cur][j]);
+        if (frank[j] < frank[rep] || (frank[j] == frank[rep] && S.key[cur][j] > S.key[cur][rep])) rep = j;
+      }
+    double ssum = 0;
+    for (int j = i; j < nb; ++j) if (fkey[j] == k) ssum += exp(S.logit[cur][j] - m);
+    const double merged = (fin[rep] - S.logit[cur][rep]) + m + log(ssum);
+    if (merged > my_score || (merged == my_score && k > my_key)) { my_score = merged; my_key = k; my_first = i; }
+  }
+  const long long sbest = wave_max_i64(ord64(my_score));
+  const long long kbest = wave_max_i64(ord64(my_score) == sbest ? (long long)(my_key ^ 0x8000000000000000ull) : (long long)0x8000000000000000ull);
+  const unsigned long long wm = __ballot(ord64(my_score) == sbest && (long long)(my_key ^ 0x8000000000000000ull) == kbest);
+  // lowest beam index among the lanes that hold the maximum (a lane's own groups are already in beam order)
+  int bi_best = 0x7fffffff;
+  for (unsigned long long q = wm; q; q &= q - 1) bi_best = min(bi_best, __builtin_amdgcn_readlane(my_first, __ffsll((long long)q) - 1));
+  const double bs = unord64(sbest);
+
+  // ---- trace back: the back-pointer rows come through LDS kTbRows at a time (one batch = one contiguous 6 KB read), the
+  //      batch after the current one already requested while the current one is walked; the characters are collected in
+  //      LDS and leave as one coalesced write (the workgroup kernel walked 501 dependent HBM round trips and reversed the
+  //      text in HBM with one thread: 0.2 ms of a 3 ms search) ----
+  unsigned int* rows = reinterpret_cast<unsigned int*>(S.tkey);            // [2][kTbRows][kMaxBeams], from the merge table on
+  unsigned short* chars = reinterpret_cast<unsigned short*>(&S.key[0][0]);  // [kChars], aliases the beam keys / hashes / logits
+  int32_t* out = out_ids + (int64_t)b * frames_ld;
+  const bool in_lds = frames <= kChars;
+  int n = 0, cur_b = bi_best;
+  bool lead = true;                                          // still inside the trailing whitespace of the text
+  constexpr int kRowRegs = kTbRows * kMaxBeams / 4 / 64;     // uint4 per lane and batch
+  uint4 rr[kRowRegs];
+  const int nbatch = (frames + kTbRows - 1) / kTbRows;       // batch j: frames (frames - (j + 1) kTbRows, frames - j kTbRows]
+  auto tb_request = [&](int j) __attribute__((always_inline)) {
+    const int t_hi = frames - 1 - j * kTbRows, t_lo = max(0, t_hi - kTbRows + 1), nq = (t_hi - t_lo + 1) * (kMaxBeams / 4);
+    const uint4* g = reinterpret_cast<const uint4*>(bp + (int64_t)t_lo * kMaxBeams);
+#pragma unroll
+    for (int k = 0; k < kRowRegs; ++k) rr[k] = 64 * k + lane < nq ? g[64 * k + lane] : make_uint4(0, 0, 0, 0);
+  };
+  auto tb_land = [&](int j) __attribute__((always_inline)) {
+    uint4* dst = reinterpret_cast<uint4*>(rows + (j & 1) * kTbRows * kMaxBeams);
+#pragma unroll
+    for (int k = 0; k < kRowRegs; ++k) dst[64 * k + lane] = rr[k];
+  };
+  if (nbatch > 0) { tb_request(0); tb_land(0); }
+  for (int j = 0; j < nbatch; ++j) {
+    if (j + 1 < nbatch) tb_request(j + 1);
+    wave_sync();
+    const int t_hi = frames - 1 - j * kTbRows, t_lo = max(0, t_hi - kTbRows + 1);
+    const unsigned int* rb = rows + (j & 1) * kTbRows * kMaxBeams;
+    for (int tt = t_hi - t_lo; tt >= 0; --tt) {
+      const unsigned int e = rb[tt * kMaxBeams + cur_b];
+      const unsigned int ch = e & 255;
+      if (ch) {
+        const int id = (int)ch - 1;
+        if (!(lead && id == space_id)) {                      // normalise trailing whitespace
+          lead = false;
+          if (in_lds) chars[n] = (unsigned short)id;
+          else if (lane == 0) out[frames_ld - 1 - n] = id;    // long transcripts: filled from the back, moved below
+          ++n;
+        }
+      }
+      cur_b = (int)(e >> 8);
+    }
+    if (j + 1 < nbatch) tb_land(j + 1);
+    wave_sync();
+  }
+  if (in_lds) {
+    for (int j = lane; j < n; j += 64) out[j] = (int)chars[n - 1 - j];
+  } else {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    // out[j] = out[frames_ld - n + j]: destination indices lie below the source indices and a chunk's loads complete
+    // before its stores, so overlapping ranges are safe
+    const int off = frames_ld - n;
+    if (off > 0) {
+      for (int j0 = 0; j0 < n; j0 += 64) {
+        const int j = j0 + lane;
+        int v = 0;
+        if (j < n) v = __hip_atomic_load(&out[off + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        if (j < n) out[j] = v;
+      }
+    }
+  }
+  if (lane == 0) {
+    out_len[b] = overflow ? -1 : n;
+    out_score[b] = (float)bs;
+  }
+}
 
 }  // namespace beam_detail
 }  // namespace vasr

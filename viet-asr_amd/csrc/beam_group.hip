@@ -47,7 +47,8 @@
 //   * candidate characters depend on the frame alone: the four wavefronts list them for 32 frames at a time in parallel
 //     (eight frames each, records in LDS, two barriers per 32 frames) instead of repeating every frame's list in the serial
 //     loop;
-//   * the final pass (commit pending words, merge identical texts, trace-back) is wavefront 0 alone, as in beam_wave.hip.
+//   * the final pass (commit pending words, merge identical texts, trace-back) is wavefront 0 alone: beam_common.h final_pass,
+//     the same code as beam_wave.hip's.
 //
 // Results equal beam_wave.hip's bit for bit (tests/test_beam.py::test_wave_kernel_and_group_kernel_agree,
 // ::test_exact_score_ties_do_not_depend_on_the_kernel_form, every case of the randomised comparison runs both forms; soak:
@@ -65,10 +66,6 @@ using namespace beam_detail;
 
 constexpr int kTab = 2048;                // merge-table slots
 constexpr int kFill = 716;                // pairs per pass (file header; beam_wave.hip: 358)
-constexpr int kTbRows = 12;
-constexpr int kLpFrames = 8;
-constexpr int kLpRegs = kLpFrames * kMaxClasses / 64;
-constexpr int kChars = 3072;
 constexpr int kMaxBlocks = 16;            // block indices W j + w of a pass (W PPL <= 12) + 2 blocks of carried survivors
 static_assert(4 * 3 + 2 <= kMaxBlocks, "block mailboxes");
 
@@ -110,21 +107,9 @@ struct GroupLds {
 static_assert(2 * kTbRows * kMaxBeams * 4 <= (int)(sizeof(unsigned long long) * kTab), "trace-back batches alias tkey");
 static_assert(kChars * 2 <= (int)(sizeof(unsigned long long) * 2 * kMaxBeams * 3), "transcript characters alias the beam keys / hashes / logits");
 static_assert(sizeof(GroupLds<4>) <= 160 * 1024, "one workgroup per compute unit");
+static_assert(sizeof(GroupLds<4>) == 133296, "a new field changes the LDS per utterance: check that it still fits a compute unit, then update this number");
 static_assert(kFill <= 3 * 256 && kFill <= kTab * 7 / 20, "pairs per pass: three per lane at most, table at most 35 % full");
 
-constexpr unsigned kMetaCached = 1u << 24, kMetaCommit = 1u << 25, kMetaOov = 1u << 26;   // (beam_wave.hip WaveLds::meta)
-constexpr int kSrcOov = 1 << 16;          // a pair record (beam << 8 | class) carries its child's "OOV" bit here
-__device__ inline int meta_last(unsigned m) { return (int)(m & 0xffu) - 1; }
-__device__ inline int meta_wlen(unsigned m) { return (int)((m >> 8) & 0xffffu); }
-__device__ inline unsigned make_meta(int last, int wlen, unsigned flags) {
-  return (unsigned)(last + 1) | ((unsigned)min(wlen, 0xffff) << 8) | flags;
-}
-
-__device__ inline void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 // LDS-only workgroup barrier: __syncthreads() would also drain the vector-memory counter, i.e. wait for the back-pointer
 // stores and the prefetched log-probs at every phase boundary
 __device__ inline void group_sync() {
@@ -143,11 +128,6 @@ __device__ inline unsigned long long fix44(float e) {
   const unsigned long long m = (unsigned long long)((b & 0x7fffffu) | 0x800000u);
   const int sh = E - 106;
   return E == 0 ? 0ull : (sh >= 0 ? m << sh : (sh > -64 ? m >> -sh : 0ull));
-}
-
-__device__ inline int lane_id() { return (int)(threadIdx.x & 63); }
-__device__ inline int rank_in(unsigned long long mask) {
-  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
 
 // grid (B), block 64 W: workgroup g searches utterance g
@@ -206,52 +186,6 @@ __global__ __launch_bounds__(64 * W) void beam_group_kernel(const float* __restr
   };
   lp_request(kLpFrames * wv);
   float* lpq = S.lpq[wv];
-
-  // One new beam at rank r from pair (parent bi, character c) with merged logit bits lgt
-  auto build_child = [&](int t, int r, int src, long long lgt, bool has_space) __attribute__((always_inline)) {
-    const int nxt = cur ^ 1;
-    const int bi = (src >> 8) & 255, c = src & 255;
-    const unsigned m = S.meta[cur][bi];
-    const int last = meta_last(m), wlen = meta_wlen(m);
-    const bool stay = (c == V || c == last);
-    unsigned long long key = S.key[cur][bi], whash = S.whash[cur][bi];
-    float lm_text = S.lm_text[cur][bi];
-    const int4 ctx_p = *reinterpret_cast<const int4*>(&S.ctx[cur][bi][0]);
-    int4 ctx_n = ctx_p;
-    const float p_lmd = S.commit_lmd[cur][bi];
-    const int p_wid = S.commit_wid[cur][bi];
-    int wlen_new = wlen;
-    unsigned int appended = 0;
-    unsigned flags = (src & kSrcOov) ? kMetaOov : 0u;       // (the score step decided it: same pending word, same bit)
-    if (stay) {
-      if ((m & kMetaCached) || (has_space && wlen > 0)) flags |= kMetaCached;
-      flags |= m & kMetaCommit;
-    } else if (c == space_id) {
-      if (wlen > 0) {
-        key = hmix(key, (unsigned long long)c);
-        appended = c + 1;
-        if (use_lm) {
-          lm_text += p_lmd;
-          ctx_n = make_int4(ctx_p.y, ctx_p.z, ctx_p.w, p_wid);
-        }
-        wlen_new = 0; whash = kFnvOffset;
-      }
-    } else {
-      key = hmix(key, (unsigned long long)c);
-      whash = hmix(whash, (unsigned long long)c);
-      wlen_new = wlen + 1;
-      appended = c + 1;
-    }
-    if (c != V) S.anychar_epoch = t;                 // (every writer stores the same value)
-    S.key[nxt][r] = key; S.whash[nxt][r] = whash;
-    S.logit[nxt][r] = __longlong_as_double(lgt);
-    S.lm_text[nxt][r] = lm_text;
-    S.meta[nxt][r] = make_meta(c, wlen_new, flags);
-    *reinterpret_cast<int4*>(&S.ctx[nxt][r][0]) = ctx_n;
-    S.commit_lmd[nxt][r] = p_lmd;
-    S.commit_wid[nxt][r] = p_wid;
-    bp[(int64_t)t * kMaxBeams + r] = ((unsigned)bi << 8) | appended;
-  };
 
   for (int t = 0; t < frames; ++t) {
     // ---- 1. candidate characters: from the chunk's records (pre-pass at every chunk boundary) ----
@@ -319,24 +253,8 @@ __global__ __launch_bounds__(64 * W) void beam_group_kernel(const float* __restr
     if (use_lm && has_space) {
       for (int i0 = 0; i0 < nb; i0 += 64 * W) {
         const int i = i0 + tid;
-        bool put = false;
         unsigned long long h = 0;
-        if (i < nb) {
-          const unsigned m = S.meta[cur][i];
-          if (meta_wlen(m) > 0) {
-            put = !(m & kMetaCached);
-            h = hmix(S.key[cur][i], (unsigned long long)space_id) | 1ull;
-            if (!(m & kMetaCommit)) {
-              int ctx[kMaxCtx];
-#pragma unroll
-              for (int qq = 0; qq < kMaxCtx; ++qq) ctx[qq] = S.ctx[cur][i][qq];
-              int w;
-              S.commit_lmd[cur][i] = lm_word_score(lm, ctx, S.whash[cur][i], false, &w);
-              S.commit_wid[cur][i] = w;
-              S.meta[cur][i] = m | kMetaCommit;
-            }
-          }
-        }
+        const bool put = i < nb && lm_commit_step(S, cur, i, space_id, lm, &h);
         const unsigned long long pm = __ballot(put);
         if (pm) {                                    // the log is a SET of keys: its order does not matter
           int base = 0;
@@ -353,15 +271,6 @@ __global__ __launch_bounds__(64 * W) void beam_group_kernel(const float* __restr
     long long c_tot[2] = {ord64(-1e300), ord64(-1e300)}, c_lgt[2] = {0, 0};
     int c_src[2] = {0, 0};
     int n_sel = 0;
-
-    // table key of pair (beam bi, character c) = src -- (prefix text, last character), as the expand step forms it
-    auto pair_key = [&](int sr) __attribute__((always_inline)) -> unsigned long long {
-      const int bi = (sr >> 8) & 255, c = sr & 255;
-      const unsigned m = S.meta[cur][bi];
-      const bool grows = !(c == V || c == meta_last(m)) && !(c == space_id && meta_wlen(m) == 0);
-      const unsigned long long key = S.key[cur][bi];
-      return ((grows ? hmix(key, (unsigned long long)c) : key) ^ S.cmix[c]) | 1ull;
-    };
 
     // carry_tag: the frame's earlier passes left survivors (wavefront 0 carries them as two more blocks of entries); a
     // single-pass frame -- the usual case -- compiles them out
@@ -393,6 +302,7 @@ __global__ __launch_bounds__(64 * W) void beam_group_kernel(const float* __restr
         unsigned long long key = S.key[cur][bi];
         score[j] = S.logit[cur][bi] + (double)cval[ci];
         src[j] = (bi << 8) | c;
+        // pair_key (beam_common.h) inline
         const bool grows = !(c == V || c == last) && !(c == space_id && meta_wlen(m) == 0);
         const unsigned long long kx = hmix(key, (unsigned long long)c);
         key = grows ? kx : key;
@@ -452,26 +362,7 @@ __global__ __launch_bounds__(64 * W) void beam_group_kernel(const float* __restr
       for (int j = 0; j < PPL; ++j) {
         const bool mine = claimed >> j & 1;
         const int i = slot[j], bi = src[j] >> 8, c = src[j] & 255;
-        float lmt = 0.f;
-        if (use_lm) {
-          const unsigned m = S.meta[cur][bi];
-          const int last = meta_last(m), wlen = meta_wlen(m);
-          const bool stay = (c == V || c == last);
-          const int wlen_new = stay ? wlen : (c == space_id ? 0 : wlen + 1);
-          const float commit = S.commit_lmd[cur][bi];
-          // partial_penalty(unk_offset, wlen_new), its division only when some lane's pending word is longer than six
-          // characters (as a select the compiler runs the ~12-instruction division in every frame)
-          // is_oov of the child's pending word: the parent's when the word stays; once outside the trie, outside for good
-          bool oov = true;
-          if (trie) {
-            if (stay) oov = (m & kMetaOov) != 0u;
-            else if (c != space_id && !(wlen > 0 && (m & kMetaOov))) oov = !trie_has_node(lm, wnew[j], tfirst[j]);
-          }
-          if (oov) src[j] |= kSrcOov;
-          float pen = (wlen_new > 0 && oov) ? lm.unk_offset : 0.f;
-          if (__ballot(wlen_new > 6) != 0ull) pen = wlen_new > 6 ? pen * (float)wlen_new / 6.0f : pen;
-          lmt = S.lm_text[cur][bi] + pen + ((!stay && c == space_id && wlen > 0) ? commit : 0.f);
-        }
+        const float lmt = use_lm ? pair_lm_part(S, cur, bi, c, V, space_id, lm, trie, wnew[j], tfirst[j], &src[j]) : 0.f;
         double logit = score[j];
         if (mine) {
           S.tkey[i] = 0;
@@ -561,18 +452,8 @@ __global__ __launch_bounds__(64 * W) void beam_group_kernel(const float* __restr
             first = false;
             if (__builtin_amdgcn_readlane(incl, 63) <= want) { mask = 0; prefix = 0; break; }   // no more live entries than beams
           }
-          int above = incl - mine;
-          int f_bucket = -1, f_want = 0, f_whole = 0;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            if (above < want && want <= above + cnt[j]) { f_bucket = 255 - (4 * lane + j); f_want = want - above; f_whole = cnt[j] == want - above; }
-            above += cnt[j];
-          }
-          const unsigned long long fm = __ballot(f_bucket >= 0);
-          const int fl = __ffsll((long long)fm) - 1;
-          const int bucket = __builtin_amdgcn_readlane(f_bucket, fl);
-          want = __builtin_amdgcn_readlane(f_want, fl);
-          const int whole = __builtin_amdgcn_readlane(f_whole, fl);
+          int whole;
+          const int bucket = radix_bucket(cnt, incl - mine, &want, &whole);
           prefix |= (unsigned long long)bucket << shift;
           mask |= 0xFFull << shift;
           if (whole || shift == 0) { tie = !whole; break; }
@@ -590,7 +471,7 @@ __global__ __launch_bounds__(64 * W) void beam_group_kernel(const float* __restr
           unsigned tied = 0;
 #pragma unroll
           for (int j = 0; j < PPL + NC; ++j) {
-            tk[j] = pair_key(j < PPL ? src[j] : c_src[j - PPL]);
+            tk[j] = pair_key(S, cur, V, space_id, j < PPL ? src[j] : c_src[j - PPL]);
             const unsigned long long u = (unsigned long long)(j < PPL ? tot[j] : c_tot[j - PPL]) ^ 0x8000000000000000ull;
             if ((live >> j & 1) && u == prefix) tied |= 1u << j;
           }
@@ -610,18 +491,8 @@ __global__ __launch_bounds__(64 * W) void beam_group_kernel(const float* __restr
             const int mine = (c4.x + c4.y) + (c4.z + c4.w);
             const int incl = wave_scan_incl(mine);
             if (shift == 56 && __builtin_amdgcn_readlane(incl, 63) <= want) { fits = true; break; }   // (lead == 64 only) all tied entries fit
-            int above = incl - mine;
-            int f_bucket = -1, f_want = 0, f_whole = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              if (above < want && want <= above + cnt[j]) { f_bucket = 255 - (4 * lane + j); f_want = want - above; f_whole = cnt[j] == want - above; }
-              above += cnt[j];
-            }
-            const unsigned long long fm = __ballot(f_bucket >= 0);
-            const int fl = __ffsll((long long)fm) - 1;
-            const int bucket = __builtin_amdgcn_readlane(f_bucket, fl);
-            want = __builtin_amdgcn_readlane(f_want, fl);
-            const int whole = __builtin_amdgcn_readlane(f_whole, fl);
+            int whole;
+            const int bucket = radix_bucket(cnt, incl - mine, &want, &whole);
             kprefix |= (unsigned long long)bucket << shift;
             kmask |= 0xFFull << shift;
             if (whole || shift == 0) break;
@@ -676,7 +547,9 @@ __global__ __launch_bounds__(64 * W) void beam_group_kernel(const float* __restr
         if (take && dst < kMaxBeams) {
           const int sr = j < PPL ? src[j] : c_src[j - PPL];
           const long long lg = j < PPL ? lgt[j] : c_lgt[j - PPL];
-          if (last_pass) build_child(t, dst, sr, lg, has_space);
+          if (last_pass) {
+            if (build_child(S, cur, V, space_id, use_lm, bp, t, dst, sr, lg, has_space)) S.anychar_epoch = t;   // (every writer stores the same value)
+          }
           else { S.sel_src[dst] = sr; S.sel_lgt[dst] = lg; S.sel_tot[dst] = j < PPL ? tot[j] : c_tot[j - PPL]; }
         }
       }
@@ -717,167 +590,8 @@ __global__ __launch_bounds__(64 * W) void beam_group_kernel(const float* __restr
   // every wavefront's back-pointer and log stores have reached L2 before wavefront 0 reads them back
   __syncthreads();
   if (wv != 0) return;
-  const int n_log = S.n_log;
-
-  // ---- final: commit pending words (LM score with </s>), merge identical texts, pick the best (as beam_wave.hip) ----
-  int in_cache[2] = {0, 0};
-  if (use_lm) {
-    int myslot[2] = {-1, -1};
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int i = lane + 64 * j;
-      if (i < nb) {
-        const unsigned m = S.meta[cur][i];
-        if (meta_wlen(m) > 0) {
-          in_cache[j] = (m & kMetaCached) ? 1 : 0;
-          if (!in_cache[j] && n_log > 0) {
-            const unsigned long long k = hmix(S.key[cur][i], (unsigned long long)space_id) | 1ull;
-            int q2 = (int)((k >> 17) & (kTab - 1));
-            while (true) {
-              const unsigned long long old = atomicCAS(&S.tkey[q2], 0ull, k);
-              if (old == 0ull || old == k) break;
-              q2 = (q2 + 1) & (kTab - 1);
-            }
-            myslot[j] = q2;
-          }
-        }
-      }
-    }
-    for (int i = lane; i < kTab; i += 64) S.tcnt[i] = 0;
-    wave_sync();
-    for (int q2 = lane; q2 < n_log; q2 += 64) {
-      const unsigned long long k = __hip_atomic_load(&eoslog[q2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      for (int i = (int)((k >> 17) & (kTab - 1));; i = (i + 1) & (kTab - 1)) {
-        const unsigned long long e = S.tkey[i];
-        if (e == k) { S.tcnt[i] = 1; break; }
-        if (e == 0) break;
-      }
-    }
-    wave_sync();
-#pragma unroll
-    for (int j = 0; j < 2; ++j) if (myslot[j] >= 0) in_cache[j] = S.tcnt[myslot[j]];
-    wave_sync();
-  }
-  double* fin = S.fin;
-  unsigned long long* fkey = reinterpret_cast<unsigned long long*>(S.sel_lgt);
-  double* frank = reinterpret_cast<double*>(S.sel_tot);
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int i = lane + 64 * j;
-    if (i < nb) {
-      const unsigned m = S.meta[cur][i];
-      const int wlen = meta_wlen(m);
-      double total = S.logit[cur][i];
-      if (use_lm) {
-        float lmv = S.lm_text[cur][i];
-        if (wlen > 0) {
-          int ctx[kMaxCtx], wid;
-#pragma unroll
-          for (int q2 = 0; q2 < kMaxCtx; ++q2) ctx[q2] = S.ctx[cur][i][q2];
-          lmv += lm_word_score(lm, ctx, S.whash[cur][i], !in_cache[j], &wid);
-        }
-        total += (double)lmv;
-      }
-      fin[i] = total;
-      fkey[i] = wlen > 0 ? hmix(S.key[cur][i], (unsigned long long)space_id) : S.key[cur][i];
-      frank[i] = S.logit[cur][i] + (use_lm ? (double)(S.lm_text[cur][i] + partial_penalty(lm.unk_offset, wlen, (m & kMetaOov) != 0u)) : 0.0);
-    }
-  }
-  wave_sync();
-  // (exact ties -- of the last-frame scores inside a group, of the groups' merged scores -- go to the larger key, not to the
-  // earlier beam: the beams' order is not the same in the two kernels, see the select)
-  double my_score = -1e300;
-  unsigned long long my_key = 0;
-  int my_first = 0x7fffffff;
-#pragma unroll 1
-  for (int i = lane; i < nb; i += 64) {
-    const unsigned long long k = fkey[i];
-    bool first = true;
-    for (int j = 0; j < i; ++j) if (fkey[j] == k) { first = false; break; }
-    if (!first) continue;
-    double m = S.logit[cur][i];
-    int rep = i;
-    for (int j = i + 1; j < nb; ++j)
-      if (fkey[j] == k) {
-        m = fmax(m, S.logit[cur][j]);
-        if (frank[j] < frank[rep] || (frank[j] == frank[rep] && S.key[cur][j] > S.key[cur][rep])) rep = j;
-      }
-    double ssum = 0;
-    for (int j = i; j < nb; ++j) if (fkey[j] == k) ssum += exp(S.logit[cur][j] - m);
-    const double merged = (fin[rep] - S.logit[cur][rep]) + m + log(ssum);
-    if (merged > my_score || (merged == my_score && k > my_key)) { my_score = merged; my_key = k; my_first = i; }
-  }
-  const long long sbest = wave_max_i64(ord64(my_score));
-  const long long kbest = wave_max_i64(ord64(my_score) == sbest ? (long long)(my_key ^ 0x8000000000000000ull) : (long long)0x8000000000000000ull);
-  const unsigned long long wm = __ballot(ord64(my_score) == sbest && (long long)(my_key ^ 0x8000000000000000ull) == kbest);
-  int bi_best = 0x7fffffff;
-  for (unsigned long long q2 = wm; q2; q2 &= q2 - 1) bi_best = min(bi_best, __builtin_amdgcn_readlane(my_first, __ffsll((long long)q2) - 1));
-  const double bs = unord64(sbest);
-
-  // ---- trace back (as beam_wave.hip: rows through LDS kTbRows at a time, characters collected in LDS) ----
-  unsigned int* rows = reinterpret_cast<unsigned int*>(S.tkey);
-  unsigned short* chars = reinterpret_cast<unsigned short*>(&S.key[0][0]);
-  int32_t* out = out_ids + (int64_t)b * frames_ld;
-  const bool in_lds = frames <= kChars;
-  int n = 0, cur_b = bi_best;
-  bool lead = true;
-  constexpr int kRowRegs = kTbRows * kMaxBeams / 4 / 64;
-  uint4 rr[kRowRegs];
-  const int nbatch = (frames + kTbRows - 1) / kTbRows;
-  auto tb_request = [&](int j) __attribute__((always_inline)) {
-    const int t_hi = frames - 1 - j * kTbRows, t_lo = max(0, t_hi - kTbRows + 1), nq = (t_hi - t_lo + 1) * (kMaxBeams / 4);
-    const uint4* g = reinterpret_cast<const uint4*>(bp + (int64_t)t_lo * kMaxBeams);
-#pragma unroll
-    for (int k = 0; k < kRowRegs; ++k) rr[k] = 64 * k + lane < nq ? g[64 * k + lane] : make_uint4(0, 0, 0, 0);
-  };
-  auto tb_land = [&](int j) __attribute__((always_inline)) {
-    uint4* dst = reinterpret_cast<uint4*>(rows + (j & 1) * kTbRows * kMaxBeams);
-#pragma unroll
-    for (int k = 0; k < kRowRegs; ++k) dst[64 * k + lane] = rr[k];
-  };
-  if (nbatch > 0) { tb_request(0); tb_land(0); }
-  for (int j = 0; j < nbatch; ++j) {
-    if (j + 1 < nbatch) tb_request(j + 1);
-    wave_sync();
-    const int t_hi = frames - 1 - j * kTbRows, t_lo = max(0, t_hi - kTbRows + 1);
-    const unsigned int* rb = rows + (j & 1) * kTbRows * kMaxBeams;
-    for (int tt = t_hi - t_lo; tt >= 0; --tt) {
-      const unsigned int e = rb[tt * kMaxBeams + cur_b];
-      const unsigned int ch = e & 255;
-      if (ch) {
-        const int id = (int)ch - 1;
-        if (!(lead && id == space_id)) {
-          lead = false;
-          if (in_lds) chars[n] = (unsigned short)id;
-          else if (lane == 0) out[frames_ld - 1 - n] = id;
-          ++n;
-        }
-      }
-      cur_b = (int)(e >> 8);
-    }
-    if (j + 1 < nbatch) tb_land(j + 1);
-    wave_sync();
-  }
-  if (in_lds) {
-    for (int j = lane; j < n; j += 64) out[j] = (int)chars[n - 1 - j];
-  } else {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    const int off = frames_ld - n;
-    if (off > 0) {
-      for (int j0 = 0; j0 < n; j0 += 64) {
-        const int j = j0 + lane;
-        int v = 0;
-        if (j < n) v = __hip_atomic_load(&out[off + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (j < n) out[j] = v;
-      }
-    }
-  }
-  if (lane == 0) {
-    out_len[b] = S.overflow ? -1 : n;
-    out_score[b] = (float)bs;
-  }
+  final_pass(S, S.tcnt, cur, nb, S.n_log, S.overflow != 0, space_id, use_lm, lm, eoslog, bp, frames, frames_ld, b, out_ids, out_len,
+             out_score);
 }
 
 template <int W>

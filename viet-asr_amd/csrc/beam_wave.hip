@@ -45,10 +45,6 @@ using namespace beam_detail;
 
 constexpr int kTab = 512;                 // merge-table slots per utterance
 constexpr int kFill = kTab * 7 / 10;      // pairs per pass (<= 70 % load)
-constexpr int kTbRows = 12;               // back-pointer rows per trace-back batch (6 KB, two batches in LDS)
-constexpr int kLpFrames = 8;              // frames of log-probs per staging batch
-constexpr int kLpRegs = kLpFrames * kMaxClasses / 64;   // floats a lane holds of the batch in flight
-constexpr int kChars = 3072;              // characters of a transcript assembled in LDS (longer ones go through HBM)
 
 // One utterance's working set in LDS.
 struct WaveLds {
@@ -57,9 +53,7 @@ struct WaveLds {
   unsigned long long whash[2][kMaxBeams];  // rolling hash of the pending word (label ids)
   double logit[2][kMaxBeams];
   float lm_text[2][kMaxBeams];             // LM score of the committed words
-  // (last + 1) [7:0] (0 = none, blank = V + 1) | wlen [23:8] | cached [24] | commit_valid [25] | pending word is "OOV" [26]
-  // (is_oov of pyctcdecode's score_partial_token: always with no unigram list, else "not a node of the character trie")
-  unsigned int meta[2][kMaxBeams];
+  unsigned int meta[2][kMaxBeams];         // beam_common.h: last character, pending word length, flags
   int ctx[2][kMaxBeams][kMaxCtx];          // LM history, most recent last, -1 = empty
   float commit_lmd[2][kMaxBeams];          // LM score the pending word gets when ' ' commits it (valid: meta bit 25)
   int commit_wid[2][kMaxBeams];            // its word id
@@ -83,29 +77,6 @@ static_assert(sizeof(WaveLds) * 4 <= 160 * 1024, "four utterances per compute un
 static_assert(sizeof(WaveLds) == 38528, "a new field changes the LDS per utterance: check that four still fit a compute unit, then update this number");
 static_assert(2 * kTbRows * kMaxBeams * 4 <= (int)(sizeof(unsigned long long) * kTab * 3), "trace-back batches alias tkey + tmx + tsum");
 static_assert(kChars * 2 <= (int)(sizeof(unsigned long long) * 2 * kMaxBeams * 3), "transcript characters alias the beam keys / hashes / logits");
-
-constexpr unsigned kMetaCached = 1u << 24, kMetaCommit = 1u << 25, kMetaOov = 1u << 26;
-constexpr int kSrcOov = 1 << 16;          // a pair record (beam << 8 | class) carries its child's "OOV" bit here
-__device__ inline int meta_last(unsigned m) { return (int)(m & 0xffu) - 1; }
-__device__ inline int meta_wlen(unsigned m) { return (int)((m >> 8) & 0xffffu); }
-__device__ inline unsigned make_meta(int last, int wlen, unsigned flags) {
-  return (unsigned)(last + 1) | ((unsigned)min(wlen, 0xffff) << 8) | flags;
-}
-
-// Orders the LDS traffic of the wavefront's phases for the COMPILER (the hardware executes one wavefront's LDS
-// operations in order): lanes read what other lanes of the same wavefront wrote, which per-thread alias analysis
-// cannot see.
-__device__ inline void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ inline int lane_id() { return (int)(threadIdx.x & 63); }
-__device__ inline int rank_in(unsigned long long mask) {   // set bits of `mask` below this lane
-  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-__device__ inline int wave_sum(int v) { return __builtin_amdgcn_readlane(wave_scan_incl(v), 63); }
 
 // grid (ceil(B / upw)), block 64 * upw: wavefront w of workgroup g searches utterance g * upw + w, alone
 __global__ __launch_bounds__(256) void beam_wave_kernel(const float* __restrict__ logp, int batch, int frames_ld,
@@ -162,55 +133,6 @@ __global__ __launch_bounds__(256) void beam_wave_kernel(const float* __restrict_
   };
   lp_request(0);
 
-  // One new beam at rank r from pair (parent bi, character c) with merged logit bits lgt: the parent's fields are gathered
-  // from the current buffer, the child goes to the other one, one back-pointer word per rank and frame.
-  auto build_child = [&](int t, int r, int src, long long lgt, bool has_space, bool& any_char) __attribute__((always_inline)) {
-    const int nxt = cur ^ 1;
-    const int bi = (src >> 8) & 255, c = src & 255;
-    const unsigned m = S.meta[cur][bi];
-    const int last = meta_last(m), wlen = meta_wlen(m);
-    const bool stay = (c == V || c == last);
-    unsigned long long key = S.key[cur][bi], whash = S.whash[cur][bi];
-    float lm_text = S.lm_text[cur][bi];
-    const int4 ctx_p = *reinterpret_cast<const int4*>(&S.ctx[cur][bi][0]);
-    int4 ctx_n = ctx_p;
-    const float p_lmd = S.commit_lmd[cur][bi];
-    const int p_wid = S.commit_wid[cur][bi];
-    int wlen_new = wlen;
-    unsigned int appended = 0;
-    unsigned flags = (src & kSrcOov) ? kMetaOov : 0u;       // (the score step decided it: same pending word, same bit)
-    if (stay) {
-      // same text and pending word as the parent: in the LM cache if the parent was, or if this frame put it there; the
-      // commit score of the pending word is inherited with them
-      if ((m & kMetaCached) || (has_space && wlen > 0)) flags |= kMetaCached;
-      flags |= m & kMetaCommit;
-    } else if (c == space_id) {
-      if (wlen > 0) {
-        key = hmix(key, (unsigned long long)c);
-        appended = c + 1;
-        if (use_lm) {
-          lm_text += p_lmd;
-          ctx_n = make_int4(ctx_p.y, ctx_p.z, ctx_p.w, p_wid);
-        }
-        wlen_new = 0; whash = kFnvOffset;
-      }
-    } else {
-      key = hmix(key, (unsigned long long)c);
-      whash = hmix(whash, (unsigned long long)c);
-      wlen_new = wlen + 1;
-      appended = c + 1;
-    }
-    if (c != V) any_char = true;
-    S.key[nxt][r] = key; S.whash[nxt][r] = whash;
-    S.logit[nxt][r] = __longlong_as_double(lgt);
-    S.lm_text[nxt][r] = lm_text;
-    S.meta[nxt][r] = make_meta(c, wlen_new, flags);
-    *reinterpret_cast<int4*>(&S.ctx[nxt][r][0]) = ctx_n;
-    S.commit_lmd[nxt][r] = p_lmd;
-    S.commit_wid[nxt][r] = p_wid;
-    bp[(int64_t)t * kMaxBeams + r] = ((unsigned)bi << 8) | appended;
-  };
-
   for (int t = 0; t < frames; ++t) {
     // ---- 1. candidate characters.  pyctcdecode works on log(clip(p, 1e-15, 1)) = clip(x, log 1e-15, 0); for every class
     //         that can be a candidate (x >= token_min_logp, or the arg-max) that is min(x, 0), a float: no fp64 here ----
@@ -264,24 +186,8 @@ __global__ __launch_bounds__(256) void beam_wave_kernel(const float* __restrict_
     if (use_lm && has_space) {
       for (int i0 = 0; i0 < nb; i0 += 64) {
         const int i = i0 + lane;
-        bool put = false;
         unsigned long long h = 0;
-        if (i < nb) {
-          const unsigned m = S.meta[cur][i];
-          if (meta_wlen(m) > 0) {
-            put = !(m & kMetaCached);
-            h = hmix(S.key[cur][i], (unsigned long long)space_id) | 1ull;
-            if (!(m & kMetaCommit)) {
-              int ctx[kMaxCtx];
-#pragma unroll
-              for (int qq = 0; qq < kMaxCtx; ++qq) ctx[qq] = S.ctx[cur][i][qq];
-              int w;
-              S.commit_lmd[cur][i] = lm_word_score(lm, ctx, S.whash[cur][i], false, &w);
-              S.commit_wid[cur][i] = w;
-              S.meta[cur][i] = m | kMetaCommit;
-            }
-          }
-        }
+        const bool put = i < nb && lm_commit_step(S, cur, i, space_id, lm, &h);
         const unsigned long long pm = __ballot(put);
         if (put) eoslog[n_log + rank_in(pm)] = h;
         n_log += __popcll(pm);
@@ -297,15 +203,6 @@ __global__ __launch_bounds__(256) void beam_wave_kernel(const float* __restrict_
     int c_src[2] = {0, 0};
     int n_sel = 0;
     bool any_char = false;
-
-    // table key of pair (beam bi, character c) = src -- (prefix text, last character), as the expand step forms it
-    auto pair_key = [&](int sr) __attribute__((always_inline)) -> unsigned long long {
-      const int bi = (sr >> 8) & 255, c = sr & 255;
-      const unsigned m = S.meta[cur][bi];
-      const bool grows = !(c == V || c == meta_last(m)) && !(c == space_id && meta_wlen(m) == 0);
-      const unsigned long long key = S.key[cur][bi];
-      return ((grows ? hmix(key, (unsigned long long)c) : key) ^ S.cmix[c]) | 1ull;
-    };
 
     // One pass = nc candidates x nb beams, PPL pairs per lane (pair p = 64 j + lane), everything between the table and the
     // new beams in REGISTERS: a pair's slot and score, a merged prefix's combined score and logit in the lane that claimed
@@ -343,8 +240,8 @@ __global__ __launch_bounds__(256) void beam_wave_kernel(const float* __restrict_
         unsigned long long key = S.key[cur][bi];
         score[j] = S.logit[cur][bi] + (double)fminf(lq[c], 0.f);
         src[j] = (bi << 8) | c;
-        // the prefix grows unless the character is blank, a repeat, or a space with no word pending -- one multiply,
-        // no branches; the "last character" part of the key is a per-class constant (S.cmix)
+        // pair_key (beam_common.h) inline: the prefix grows unless the character is blank, a repeat, or a space with no word
+        // pending -- one multiply, no branches; the "last character" part of the key is a per-class constant (S.cmix)
         const bool grows = !(c == V || c == last) && !(c == space_id && meta_wlen(m) == 0);
         const unsigned long long kx = hmix(key, (unsigned long long)c);
         key = grows ? kx : key;
@@ -425,22 +322,7 @@ __global__ __launch_bounds__(256) void beam_wave_kernel(const float* __restrict_
         // only the writes are predicated)
         const bool mine = claimed >> j & 1;
         const int i = slot[j], bi = src[j] >> 8, c = src[j] & 255;
-        float lmt = 0.f;
-        if (use_lm) {
-          const unsigned m = S.meta[cur][bi];
-          const int last = meta_last(m), wlen = meta_wlen(m);
-          const bool stay = (c == V || c == last);
-          const int wlen_new = stay ? wlen : (c == space_id ? 0 : wlen + 1);
-          const float commit = S.commit_lmd[cur][bi];                                   // filled by step 2 when it is needed
-          // is_oov of the child's pending word: the parent's when the word stays; once outside the trie, outside for good
-          bool oov = true;
-          if (trie) {
-            if (stay) oov = (m & kMetaOov) != 0u;
-            else if (c != space_id && !(wlen > 0 && (m & kMetaOov))) oov = !trie_has_node(lm, wnew[j], tfirst[j]);
-          }
-          if (oov) src[j] |= kSrcOov;
-          lmt = S.lm_text[cur][bi] + partial_penalty(lm.unk_offset, wlen_new, oov) + ((!stay && c == space_id && wlen > 0) ? commit : 0.f);
-        }
+        const float lmt = use_lm ? pair_lm_part(S, cur, bi, c, V, space_id, lm, trie, wnew[j], tfirst[j], &src[j]) : 0.f;
         if (mine) S.tkey[i] = 0;
         // a prefix with a single contributor keeps that pair's score, exactly (exp(0) = 1: no logarithm)
         double logit = score[j];
@@ -497,18 +379,8 @@ __global__ __launch_bounds__(256) void beam_wave_kernel(const float* __restrict_
           int cnt[4], mine = 0;
 #pragma unroll
           for (int j = 0; j < 4; ++j) { cnt[j] = S.hist[255 - (4 * lane + j)]; mine += cnt[j]; }
-          int above = wave_scan_incl(mine) - mine;
-          int f_bucket = -1, f_want = 0, f_whole = 0;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            if (above < want && want <= above + cnt[j]) { f_bucket = 255 - (4 * lane + j); f_want = want - above; f_whole = cnt[j] == want - above; }
-            above += cnt[j];
-          }
-          const unsigned long long fm = __ballot(f_bucket >= 0);
-          const int fl = __ffsll((long long)fm) - 1;           // exactly one lane finds it (tot_live > want >= 1)
-          const int bucket = __builtin_amdgcn_readlane(f_bucket, fl);
-          want = __builtin_amdgcn_readlane(f_want, fl);
-          const int whole = __builtin_amdgcn_readlane(f_whole, fl);
+          int whole;
+          const int bucket = radix_bucket(cnt, wave_scan_incl(mine) - mine, &want, &whole);   // (tot_live > want >= 1)
           prefix |= (unsigned long long)bucket << shift;
           mask |= 0xFFull << shift;
           if (whole || shift == 0) { tie = !whole; break; }   // the whole bucket is taken: no need to refine further
@@ -526,7 +398,7 @@ __global__ __launch_bounds__(256) void beam_wave_kernel(const float* __restrict_
           unsigned tied = 0;
 #pragma unroll
           for (int j = 0; j < PPL + 2; ++j) {
-            tk[j] = pair_key(j < PPL ? src[j] : c_src[j - PPL]);
+            tk[j] = pair_key(S, cur, V, space_id, j < PPL ? src[j] : c_src[j - PPL]);
             const unsigned long long u = (unsigned long long)(j < PPL ? tot[j] : c_tot[j - PPL]) ^ 0x8000000000000000ull;
             if ((live >> j & 1) && u == prefix) tied |= 1u << j;
           }
@@ -541,18 +413,8 @@ __global__ __launch_bounds__(256) void beam_wave_kernel(const float* __restrict_
             int cnt[4], mine = 0;
 #pragma unroll
             for (int j = 0; j < 4; ++j) { cnt[j] = S.hist[255 - (4 * lane + j)]; mine += cnt[j]; }
-            int above = wave_scan_incl(mine) - mine;
-            int f_bucket = -1, f_want = 0, f_whole = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              if (above < want && want <= above + cnt[j]) { f_bucket = 255 - (4 * lane + j); f_want = want - above; f_whole = cnt[j] == want - above; }
-              above += cnt[j];
-            }
-            const unsigned long long fm = __ballot(f_bucket >= 0);
-            const int fl = __ffsll((long long)fm) - 1;         // exactly one lane finds it (more tied entries than wanted, want >= 1)
-            const int bucket = __builtin_amdgcn_readlane(f_bucket, fl);
-            want = __builtin_amdgcn_readlane(f_want, fl);
-            const int whole = __builtin_amdgcn_readlane(f_whole, fl);
+            int whole;
+            const int bucket = radix_bucket(cnt, wave_scan_incl(mine) - mine, &want, &whole);   // (more tied entries than wanted)
             kprefix |= (unsigned long long)bucket << shift;
             kmask |= 0xFFull << shift;
             if (whole || shift == 0) break;
@@ -620,189 +482,17 @@ __global__ __launch_bounds__(256) void beam_wave_kernel(const float* __restrict_
     }
     // ---- 5. the new beams, one per rank ----
 #pragma unroll 1
-    for (int r = lane; r < n_sel; r += 64) build_child(t, r, S.sel_src[r], S.sel_lgt[r], has_space, any_char);
+    for (int r = lane; r < n_sel; r += 64)
+      if (build_child(S, cur, V, space_id, use_lm, bp, t, r, S.sel_src[r], S.sel_lgt[r], has_space)) any_char = true;
     all_blank = __ballot(any_char) == 0ull;
     nb = n_sel;
     cur ^= 1;
     wave_sync();
   }
 
-  // ---- final: commit pending words (LM score with </s>), merge identical texts, pick the best ----
-  // Is "text + pending word" in pyctcdecode's LM cache (then its cached score, WITHOUT </s>, is what the final pass
-  // uses)?  Known for beams whose own lineage put it there (`cached`); the others look their hash up in eoslog: their
-  // hashes go into the (idle, empty) merge table, the wavefront walks the log and marks the hashes it meets.
-  int in_cache[2] = {0, 0};
-  if (use_lm) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the log's stores have reached L2 (read back past the L1 below)
-    int myslot[2] = {-1, -1};
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int i = lane + 64 * j;
-      if (i < nb) {
-        const unsigned m = S.meta[cur][i];
-        if (meta_wlen(m) > 0) {
-          in_cache[j] = (m & kMetaCached) ? 1 : 0;
-          if (!in_cache[j] && n_log > 0) {
-            const unsigned long long k = hmix(S.key[cur][i], (unsigned long long)space_id) | 1ull;
-            int q = (int)((k >> 17) & (kTab - 1));
-            while (true) {
-              const unsigned long long old = atomicCAS(&S.tkey[q], 0ull, k);
-              if (old == 0ull || old == k) break;
-              q = (q + 1) & (kTab - 1);
-            }
-            myslot[j] = q;
-          }
-        }
-      }
-    }
-    for (int i = lane; i < kTab; i += 64) S.tsrc[i] = 0;
-    wave_sync();
-    for (int q = lane; q < n_log; q += 64) {
-      const unsigned long long k = __hip_atomic_load(&eoslog[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      for (int i = (int)((k >> 17) & (kTab - 1));; i = (i + 1) & (kTab - 1)) {
-        const unsigned long long e = S.tkey[i];
-        if (e == k) { S.tsrc[i] = 1; break; }
-        if (e == 0) break;
-      }
-    }
-    wave_sync();
-#pragma unroll
-    for (int j = 0; j < 2; ++j) if (myslot[j] >= 0) in_cache[j] = S.tsrc[myslot[j]];
-    wave_sync();
-  }
-  // per beam: combined final score, final text key, last-frame combined score (pyctcdecode keeps its beams sorted by it)
-  double* fin = S.fin;                                                     // [kMaxBeams]
-  unsigned long long* fkey = reinterpret_cast<unsigned long long*>(S.sel_lgt);   // [kMaxBeams]
-  double* frank = reinterpret_cast<double*>(S.sel_tot);                    // [kMaxBeams]
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int i = lane + 64 * j;
-    if (i < nb) {
-      const unsigned m = S.meta[cur][i];
-      const int wlen = meta_wlen(m);
-      double total = S.logit[cur][i];
-      if (use_lm) {
-        float lmv = S.lm_text[cur][i];
-        if (wlen > 0) {
-          int ctx[kMaxCtx], wid;
-#pragma unroll
-          for (int q = 0; q < kMaxCtx; ++q) ctx[q] = S.ctx[cur][i][q];
-          lmv += lm_word_score(lm, ctx, S.whash[cur][i], !in_cache[j], &wid);
-        }
-        total += (double)lmv;
-      }
-      fin[i] = total;
-      fkey[i] = wlen > 0 ? hmix(S.key[cur][i], (unsigned long long)space_id) : S.key[cur][i];
-      frank[i] = S.logit[cur][i] + (use_lm ? (double)(S.lm_text[cur][i] + partial_penalty(lm.unk_offset, wlen, (m & kMetaOov) != 0u)) : 0.0);
-    }
-  }
-  wave_sync();
-  // Merge by text: log-sum-exp of the LOGIT scores, as pyctcdecode does.  "abc" with the word still pending and "abc "
-  // with it committed are the same final text but not the same LM part (only the pending word is scored with </s>):
-  // pyctcdecode's _merge_beams overwrites the group's entry with every further member it meets while walking its
-  // score-sorted beam list, so the member with the LOWEST last-frame score provides the LM part.  Every lane takes the
-  // groups whose first member it owns; the best group is the first maximum in beam order.
-  // (Exact ties -- of the last-frame scores inside a group, of the groups' merged scores -- go to the larger key, not to the
-  // earlier beam: the beams' order is not the same in the two kernels, see the select.)
-  double my_score = -1e300;
-  unsigned long long my_key = 0;
-  int my_first = 0x7fffffff;
-#pragma unroll 1
-  for (int i = lane; i < nb; i += 64) {
-    const unsigned long long k = fkey[i];
-    bool first = true;
-    for (int j = 0; j < i; ++j) if (fkey[j] == k) { first = false; break; }
-    if (!first) continue;
-    double m = S.logit[cur][i];
-    int rep = i;
-    for (int j = i + 1; j < nb; ++j)
-      if (fkey[j] == k) {
-        m = fmax(m, S.logit[cur][j]);
-        if (frank[j] < frank[rep] || (frank[j] == frank[rep] && S.key[cur][j] > S.key[cur][rep])) rep = j;
-      }
-    double ssum = 0;
-    for (int j = i; j < nb; ++j) if (fkey[j] == k) ssum += exp(S.logit[cur][j] - m);
-    const double merged = (fin[rep] - S.logit[cur][rep]) + m + log(ssum);
-    if (merged > my_score || (merged == my_score && k > my_key)) { my_score = merged; my_key = k; my_first = i; }
-  }
-  const long long sbest = wave_max_i64(ord64(my_score));
-  const long long kbest = wave_max_i64(ord64(my_score) == sbest ? (long long)(my_key ^ 0x8000000000000000ull) : (long long)0x8000000000000000ull);
-  const unsigned long long wm = __ballot(ord64(my_score) == sbest && (long long)(my_key ^ 0x8000000000000000ull) == kbest);
-  // lowest beam index among the lanes that hold the maximum (a lane's own groups are already in beam order)
-  int bi_best = 0x7fffffff;
-  for (unsigned long long q = wm; q; q &= q - 1) bi_best = min(bi_best, __builtin_amdgcn_readlane(my_first, __ffsll((long long)q) - 1));
-  const double bs = unord64(sbest);
-
-  // ---- trace back: the back-pointer rows come through LDS kTbRows at a time (one batch = one contiguous 6 KB read), the
-  //      batch after the current one already requested while the current one is walked; the characters are collected in
-  //      LDS and leave as one coalesced write (the workgroup kernel walked 501 dependent HBM round trips and reversed the
-  //      text in HBM with one thread: 0.2 ms of a 3 ms search) ----
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wavefront's own back-pointer stores have reached L2
-  unsigned int* rows = reinterpret_cast<unsigned int*>(S.tkey);            // [2][kTbRows][kMaxBeams], aliases tkey + tmx + tsum
-  unsigned short* chars = reinterpret_cast<unsigned short*>(&S.key[0][0]);  // [kChars], aliases the beam keys / hashes / logits
-  int32_t* out = out_ids + (int64_t)b * frames_ld;
-  const bool in_lds = frames <= kChars;
-  int n = 0, cur_b = bi_best;
-  bool lead = true;                                          // still inside the trailing whitespace of the text
-  constexpr int kRowRegs = kTbRows * kMaxBeams / 4 / 64;     // uint4 per lane and batch
-  uint4 rr[kRowRegs];
-  const int nbatch = (frames + kTbRows - 1) / kTbRows;       // batch j: frames (frames - (j + 1) kTbRows, frames - j kTbRows]
-  auto tb_request = [&](int j) __attribute__((always_inline)) {
-    const int t_hi = frames - 1 - j * kTbRows, t_lo = max(0, t_hi - kTbRows + 1), nq = (t_hi - t_lo + 1) * (kMaxBeams / 4);
-    const uint4* g = reinterpret_cast<const uint4*>(bp + (int64_t)t_lo * kMaxBeams);
-#pragma unroll
-    for (int k = 0; k < kRowRegs; ++k) rr[k] = 64 * k + lane < nq ? g[64 * k + lane] : make_uint4(0, 0, 0, 0);
-  };
-  auto tb_land = [&](int j) __attribute__((always_inline)) {
-    uint4* dst = reinterpret_cast<uint4*>(rows + (j & 1) * kTbRows * kMaxBeams);
-#pragma unroll
-    for (int k = 0; k < kRowRegs; ++k) dst[64 * k + lane] = rr[k];
-  };
-  if (nbatch > 0) { tb_request(0); tb_land(0); }
-  for (int j = 0; j < nbatch; ++j) {
-    if (j + 1 < nbatch) tb_request(j + 1);
-    wave_sync();
-    const int t_hi = frames - 1 - j * kTbRows, t_lo = max(0, t_hi - kTbRows + 1);
-    const unsigned int* rb = rows + (j & 1) * kTbRows * kMaxBeams;
-    for (int tt = t_hi - t_lo; tt >= 0; --tt) {
-      const unsigned int e = rb[tt * kMaxBeams + cur_b];
-      const unsigned int ch = e & 255;
-      if (ch) {
-        const int id = (int)ch - 1;
-        if (!(lead && id == space_id)) {                      // normalise trailing whitespace
-          lead = false;
-          if (in_lds) chars[n] = (unsigned short)id;
-          else if (lane == 0) out[frames_ld - 1 - n] = id;    // long transcripts: filled from the back, moved below
-          ++n;
-        }
-      }
-      cur_b = (int)(e >> 8);
-    }
-    if (j + 1 < nbatch) tb_land(j + 1);
-    wave_sync();
-  }
-  if (in_lds) {
-    for (int j = lane; j < n; j += 64) out[j] = (int)chars[n - 1 - j];
-  } else {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    // out[j] = out[frames_ld - n + j]: destination indices lie below the source indices and a chunk's loads complete
-    // before its stores, so overlapping ranges are safe
-    const int off = frames_ld - n;
-    if (off > 0) {
-      for (int j0 = 0; j0 < n; j0 += 64) {
-        const int j = j0 + lane;
-        int v = 0;
-        if (j < n) v = __hip_atomic_load(&out[off + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (j < n) out[j] = v;
-      }
-    }
-  }
-  if (lane == 0) {
-    out_len[b] = n;
-    out_score[b] = (float)bs;
-  }
+  // ---- final: commit pending words (LM score with </s>), merge identical texts, pick the best, trace back ----
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wavefront's back-pointer and log stores have reached L2
+  final_pass(S, S.tsrc, cur, nb, n_log, false, space_id, use_lm, lm, eoslog, bp, frames, frames_ld, b, out_ids, out_len, out_score);
 }
 
 }  // namespace
