@@ -286,6 +286,19 @@ VASR_API int vasr_beam_search_rows_f32(const float* d_logp, const int32_t* d_row
                               int num_classes, int space_id, int beam_width, float token_min_logp,
                               float beam_prune_logp, const vasr_lm* lm, int32_t* d_ids, int32_t* d_id_len,
                               float* d_score, void* d_workspace, size_t workspace_bytes, vasr_stream stream);
+/* The n-best list, pyctcdecode's decode_beams (oracle/beam_oracle.py decode_beams): per row b the text groups of the final
+ * beams whose combined score is >= best + beam_prune_logp, best first (exact ties: a fixed order that depends on the texts and
+ * scores only), at most `nbest` of them, 1 <= nbest <= beam_width.  Slot s of row b:
+ *   d_ids [B][nbest][frames] i32: ids row b * nbest + s, d_id_len [B][nbest] i32 (-1 in every slot of a row: the overflow of
+ *   vasr_beam_search_rows_f32), d_logit_score / d_score [B][nbest] f64 the merged logit (acoustic) score and the combined
+ *   (acoustic + LM) score; d_count [B] i32 the number of slots filled (>= 1).  Slots at or beyond the count get length 0 and
+ *   scores -INFINITY; their ids are not written.  Slot 0 is vasr_beam_search_rows_f32's hypothesis: the same ids and length,
+ *   and (float)d_score[b][0] is its score.  Workspace: vasr_beam_workspace_bytes; d_row_frames as above (NULL = all). */
+VASR_API int vasr_beam_search_nbest_f32(const float* d_logp, const int32_t* d_row_frames, int batch, int64_t frames,
+                               int num_classes, int space_id, int beam_width, int nbest, float token_min_logp,
+                               float beam_prune_logp, const vasr_lm* lm, int32_t* d_ids, int32_t* d_id_len,
+                               int32_t* d_count, double* d_logit_score, double* d_score, void* d_workspace,
+                               size_t workspace_bytes, vasr_stream stream);
 /* Back-off n-gram model as two open-addressing hash tables of 16-BYTE entries (one load returns key and value), both with
  * power-of-two capacity 2^lg >= 16, linear probing from the home slot ((uint32)(key ^ key >> 32) * 0x9E3779B1) >> (32 - lg),
  * key 0 = empty slot, stored keys have bit 0 set:

@@ -317,11 +317,8 @@ class BeamSearchDecoder:
             self._lm = DeviceLM(self.lm_path, self.labels, self.alpha, self.beta, unigrams=self.unigrams)
         return self._lm
 
-    def decode_ids(self, log_probs, beam_width, frames=None):
-        """log_probs [B,T,V+1] cuda f32 -> (ids [B,T] i32, id_len [B] i32, score [B] f32).
-
-        frames: optional [B] frame counts (sequence or tensor); row b is then searched over its first frames[b]
-        frames only -- for batches of different lengths (the reference searches every frame of its batch-1 tensor)."""
+    def _search_args(self, log_probs, frames):
+        """-> (x [B,T,V+1] f32, workspace, stream, row frame counts or None) for a vasr_beam_search_* call."""
         if log_probs.device.type != "cuda":
             raise _lib.VasrError("viet-asr_amd kernels need HIP-resident tensors; there is no CPU fallback for this path")
         x = log_probs.to(torch.float32).contiguous()
@@ -335,21 +332,70 @@ class BeamSearchDecoder:
             ws = self._ws.get((x.device, stream))
             if ws is None or ws.numel() < need:
                 ws = self._ws[(x.device, stream)] = torch.empty(need, dtype=torch.uint8, device=x.device)
-        ids = torch.empty((B, T), dtype=torch.int32, device=x.device)
-        n = torch.empty((B,), dtype=torch.int32, device=x.device)
-        score = torch.empty((B,), dtype=torch.float32, device=x.device)
-        lm = self._get_lm()
         rows = None
         if frames is not None:
             rows = torch.as_tensor(frames).to(device=x.device, dtype=torch.int32).contiguous()
             if rows.shape != (B,):
                 raise ValueError(f"frames must have one entry per row ({B}), got shape {tuple(rows.shape)}")
+        return x, ws, stream, rows
+
+    def decode_ids(self, log_probs, beam_width, frames=None):
+        """log_probs [B,T,V+1] cuda f32 -> (ids [B,T] i32, id_len [B] i32, score [B] f32).
+
+        frames: optional [B] frame counts (sequence or tensor); row b is then searched over its first frames[b]
+        frames only -- for batches of different lengths (the reference searches every frame of its batch-1 tensor)."""
+        x, ws, stream, rows = self._search_args(log_probs, frames)
+        B, T, V1 = x.shape
+        L = _lib.lib()
+        ids = torch.empty((B, T), dtype=torch.int32, device=x.device)
+        n = torch.empty((B,), dtype=torch.int32, device=x.device)
+        score = torch.empty((B,), dtype=torch.float32, device=x.device)
+        lm = self._get_lm()
         _lib.check(L.vasr_beam_search_rows_f32(x.data_ptr(), rows.data_ptr() if rows is not None else None, B, T, V1,
                                                self.space_id, int(beam_width), float(self.token_min_logp),
                                                float(self.beam_prune_logp), lm.handle if lm is not None else None,
                                                ids.data_ptr(), n.data_ptr(), score.data_ptr(), ws.data_ptr(),
                                                ws.numel(), stream))
         return ids, n, score
+
+    def decode_beams_ids(self, log_probs, beam_width, nbest, frames=None):
+        """The n-best list on the device (include/vasr.h vasr_beam_search_nbest_f32): log_probs [B,T,V+1] cuda f32 ->
+        (ids [B,nbest,T] i32, id_len [B,nbest] i32, count [B] i32, logit_score [B,nbest] f64, score [B,nbest] f64).
+
+        Per row the text groups of the final beams within beam_prune_logp of the best, best first, at most nbest
+        (1 <= nbest <= beam_width) of them; slots from count[b] on have id_len 0 and scores -inf.  Slot 0 is decode_ids'
+        hypothesis.  frames: as in decode_ids."""
+        beam_width, nbest = int(beam_width), int(nbest)
+        if not 1 <= nbest <= beam_width:
+            raise ValueError(f"nbest must be 1..beam_width ({beam_width}), got {nbest}")
+        x, ws, stream, rows = self._search_args(log_probs, frames)
+        B, T, V1 = x.shape
+        L = _lib.lib()
+        dev = x.device
+        ids = torch.empty((B, nbest, T), dtype=torch.int32, device=dev)
+        n = torch.empty((B, nbest), dtype=torch.int32, device=dev)
+        count = torch.empty((B,), dtype=torch.int32, device=dev)
+        logit = torch.empty((B, nbest), dtype=torch.float64, device=dev)
+        score = torch.empty((B, nbest), dtype=torch.float64, device=dev)
+        lm = self._get_lm()
+        _lib.check(L.vasr_beam_search_nbest_f32(x.data_ptr(), rows.data_ptr() if rows is not None else None, B, T, V1,
+                                                self.space_id, beam_width, nbest, float(self.token_min_logp),
+                                                float(self.beam_prune_logp), lm.handle if lm is not None else None,
+                                                ids.data_ptr(), n.data_ptr(), count.data_ptr(), logit.data_ptr(),
+                                                score.data_ptr(), ws.data_ptr(), ws.numel(), stream))
+        return ids, n, count, logit, score
+
+    def decode_beams(self, log_probs, beam_width, nbest=None, frames=None):
+        """pyctcdecode's decode_beams for every row: a list per row of (text, logit_score, combined_score), best first
+        (the shape oracle.beam_oracle.decode_beams returns).  nbest=None: beam_width, as in pyctcdecode."""
+        ids, n, count, logit, score = self.decode_beams_ids(log_probs, beam_width, beam_width if nbest is None else nbest, frames)
+        ids, n, count = ids.cpu().numpy(), n.cpu().numpy(), count.cpu().numpy()
+        logit, score = logit.cpu().numpy(), score.cpu().numpy()
+        if (n < 0).any():      # vasr.h: id_len = -1 reports a merge-cell overflow of the four-wavefront kernel (provably impossible)
+            raise _lib.VasrError("beam search reported an internal overflow (id_len = -1) for rows %s"
+                                 % np.nonzero((n < 0).any(1))[0].tolist())
+        return [[("".join(self.labels[c] for c in ids[b, k, : n[b, k]]), float(logit[b, k]), float(score[b, k]))
+                 for k in range(count[b])] for b in range(ids.shape[0])]
 
     def decode_batch(self, log_probs, beam_width, frames=None):
         ids, n, _ = self.decode_ids(log_probs, beam_width, frames)

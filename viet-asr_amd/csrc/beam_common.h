@@ -6,6 +6,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "vasr_internal.h"
 
 namespace vasr {
@@ -428,16 +430,14 @@ __device__ __forceinline__ int radix_bucket(const int (&cnt)[4], int above, int*
   return bucket;
 }
 
-// The final pass of utterance b, ONE wavefront (the caller has made every back-pointer row and log entry of the search
-// visible to it): commit pending words (LM score with </s>), merge identical texts, pick the best, trace it back and write
-// out_ids / out_len / out_score.  The beams are buffer cur (nb of them), eoslog holds n_log keys; mark: an int[kTab] of the
-// kernel's LDS that is free now, kTab = the size of the (empty) merge table S.tkey, whose words the pending-word lookup
-// and then the trace-back batches use; overflow: the search lost a merge contributor, reported as out_len = -1.
+// The first steps of the final passes (final_pass, final_pass_nbest), ONE wavefront (the caller has made every
+// back-pointer row and log entry of the search visible to it): commit pending words (LM score with </s>) and leave per
+// beam i < nb of buffer cur its combined final score fin[i] (S.fin), final text key fkey[i] (S.sel_lgt) and last-frame
+// combined score frank[i] (S.sel_tot).  eoslog holds n_log keys; mark: an int[kTab] of the kernel's LDS that is free now,
+// kTab = the size of the (empty) merge table S.tkey, whose words the pending-word lookup uses.
 template <class L, int kTab>
-__device__ __forceinline__ void final_pass(L& S, int (&mark)[kTab], int cur, int nb, int n_log, bool overflow, int space_id,
-                                           bool use_lm, const LmView& lm, unsigned long long* eoslog, const unsigned int* bp,
-                                           int frames, int frames_ld, int b, int32_t* out_ids, int32_t* out_len,
-                                           float* out_score) {
+__device__ __forceinline__ void final_scores(L& S, int (&mark)[kTab], int cur, int nb, int n_log, int space_id, bool use_lm,
+                                             const LmView& lm, unsigned long long* eoslog) {
   static_assert(sizeof(S.tkey) == sizeof(unsigned long long) * kTab, "mark[] has a cell per merge-table slot");
   const int lane = lane_id();
   // Is "text + pending word" in pyctcdecode's LM cache (then its cached score, WITHOUT </s>, is what the final pass
@@ -508,13 +508,46 @@ __device__ __forceinline__ void final_pass(L& S, int (&mark)[kTab], int cur, int
     }
   }
   wave_sync();
-  // Merge by text: log-sum-exp of the LOGIT scores, as pyctcdecode does.  "abc" with the word still pending and "abc "
-  // with it committed are the same final text but not the same LM part (only the pending word is scored with </s>):
-  // pyctcdecode's _merge_beams overwrites the group's entry with every further member it meets while walking its
-  // score-sorted beam list, so the member with the LOWEST last-frame score provides the LM part.  Every lane takes the
-  // groups whose first member it owns; the best group is the first maximum in beam order.
-  // (Exact ties -- of the last-frame scores inside a group, of the groups' merged scores -- go to the larger key, not to the
-  // earlier beam: the beams' order is not the same in the two kernels, see their selects.)
+}
+
+// Merge by text: log-sum-exp of the LOGIT scores, as pyctcdecode does.  "abc" with the word still pending and "abc "
+// with it committed are the same final text but not the same LM part (only the pending word is scored with </s>):
+// pyctcdecode's _merge_beams overwrites the group's entry with every further member it meets while walking its
+// score-sorted beam list, so the member with the LOWEST last-frame score provides the LM part.  merge_group: the group of
+// beam i (its first member, final text key k), after final_scores: returns its combined score, *logit its logit score.
+// (Exact ties -- of the last-frame scores inside a group, of the groups' merged scores -- go to the larger key, not to the
+// earlier beam: the beams' order is not the same in the two kernels, see their selects.)
+template <class L>
+__device__ __forceinline__ double merge_group(const L& S, int cur, int nb, int i, unsigned long long k, double* logit) {
+  const double* fin = S.fin;
+  const unsigned long long* fkey = reinterpret_cast<const unsigned long long*>(S.sel_lgt);
+  const double* frank = reinterpret_cast<const double*>(S.sel_tot);
+  double m = S.logit[cur][i];
+  int rep = i;
+  for (int j = i + 1; j < nb; ++j)
+    if (fkey[j] == k) {
+      m = fmax(m, S.logit[cur][j]);
+      if (frank[j] < frank[rep] || (frank[j] == frank[rep] && S.key[cur][j] > S.key[cur][rep])) rep = j;
+    }
+  double ssum = 0;
+  for (int j = i; j < nb; ++j) if (fkey[j] == k) ssum += exp(S.logit[cur][j] - m);
+  const double merged = (fin[rep] - S.logit[cur][rep]) + m + log(ssum);
+  *logit = m + log(ssum);
+  return merged;
+}
+
+// The final pass of utterance b, ONE wavefront: final_scores, merge identical texts, pick the best, trace it back and write
+// out_ids / out_len / out_score.  The trace-back batches use the words of the (empty) merge table S.tkey; overflow: the
+// search lost a merge contributor, reported as out_len = -1.
+template <class L, int kTab>
+__device__ __forceinline__ void final_pass(L& S, int (&mark)[kTab], int cur, int nb, int n_log, bool overflow, int space_id,
+                                           bool use_lm, const LmView& lm, unsigned long long* eoslog, const unsigned int* bp,
+                                           int frames, int frames_ld, int b, int32_t* out_ids, int32_t* out_len,
+                                           float* out_score) {
+  const int lane = lane_id();
+  final_scores(S, mark, cur, nb, n_log, space_id, use_lm, lm, eoslog);
+  const unsigned long long* fkey = reinterpret_cast<const unsigned long long*>(S.sel_lgt);
+  // every lane takes the groups whose first member it owns; the best group is the first maximum in beam order
   double my_score = -1e300;
   unsigned long long my_key = 0;
   int my_first = 0x7fffffff;
@@ -524,16 +557,8 @@ __device__ __forceinline__ void final_pass(L& S, int (&mark)[kTab], int cur, int
     bool first = true;
     for (int j = 0; j < i; ++j) if (fkey[j] == k) { first = false; break; }
     if (!first) continue;
-    double m = S.logit[cur][i];
-    int rep = i;
-    for (int j = i + 1; j < nb; ++j)
-      if (fkey[j] == k) {
-        m = fmax(m, S.logit[cur][j]);
-        if (frank[j] < frank[rep] || (frank[j] == frank[rep] && S.key[cur][j] > S.key[cur][rep])) rep = j;
-      }
-    double ssum = 0;
-    for (int j = i; j < nb; ++j) if (fkey[j] == k) ssum += exp(S.logit[cur][j] - m);
-    const double merged = (fin[rep] - S.logit[cur][rep]) + m + log(ssum);
+    double lg;
+    const double merged = merge_group(S, cur, nb, i, k, &lg);
     if (merged > my_score || (merged == my_score && k > my_key)) { my_score = merged; my_key = k; my_first = i; }
   }
   const long long sbest = wave_max_i64(ord64(my_score));
@@ -612,6 +637,158 @@ __device__ __forceinline__ void final_pass(L& S, int (&mark)[kTab], int cur, int
   if (lane == 0) {
     out_len[b] = overflow ? -1 : n;
     out_score[b] = (float)bs;
+  }
+}
+
+// The last argument of a beam kernel: out_score (float [B]) of the top-1 search, the BeamNbest outputs of the n-best one
+template <bool kNbest>
+using BeamResult = std::conditional_t<kNbest, BeamNbest, float* __restrict__>;
+
+// The n-best final pass of utterance b (vasr_beam_search_nbest_f32: slot s of utterance b is ids row b nbest + s, frames_ld
+// wide, and element b nbest + s of out_len and o's arrays), ONE wavefront: final_scores and merge_group as final_pass, then every text group
+// whose combined score is >= best + prune, ranked by combined score, exact ties to the larger key (so slot 0 is what
+// final_pass picks), and the first o.nbest of them traced back together: lane l follows slots l and l + 64 through the
+// same LDS batches of back-pointer rows, writes each slot's ids from the back of its own row and then moves them to the
+// front.  Slots from the count on: length 0, scores -inf; overflow: every slot's length is -1.  Per group the LDS keeps,
+// by the index i of its first member: mark[i] = 1, fin[i] its combined score, S.sel_tot[i] its logit score, S.sel_lgt[i]
+// its key; mark[kMaxBeams + s] is the first member of slot s (traced back: all members spell the same text).
+template <class L, int kTab>
+__device__ __forceinline__ void final_pass_nbest(L& S, int (&mark)[kTab], int cur, int nb, int n_log, bool overflow,
+                                                 int space_id, bool use_lm, const LmView& lm, unsigned long long* eoslog,
+                                                 const unsigned int* bp, int frames, int frames_ld, int b, float prune,
+                                                 int32_t* out_ids, int32_t* out_len, const BeamNbest& o) {
+  static_assert(kTab >= 2 * kMaxBeams, "mark[] holds the group flags and the slots' beams");
+  const int lane = lane_id();
+  final_scores(S, mark, cur, nb, n_log, space_id, use_lm, lm, eoslog);
+  unsigned long long* fkey = reinterpret_cast<unsigned long long*>(S.sel_lgt);
+  double* glogit = reinterpret_cast<double*>(S.sel_tot);
+  // a lane's groups: those whose first member is beam lane or lane + 64
+  bool own[2] = {false, false};
+  double gsc[2] = {-1e300, -1e300}, glg[2] = {0.0, 0.0};
+  unsigned long long gk[2] = {0ull, 0ull};
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int i = lane + 64 * j;
+    if (i < nb) {
+      const unsigned long long k = fkey[i];
+      bool first = true;
+      for (int q = 0; q < i; ++q) if (fkey[q] == k) { first = false; break; }
+      if (first) { own[j] = true; gk[j] = k; gsc[j] = merge_group(S, cur, nb, i, k, &glg[j]); }
+    }
+  }
+  wave_sync();                                                             // every lane is done with fkey / frank
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int i = lane + 64 * j;
+    if (i < kMaxBeams) {
+      mark[i] = own[j] ? 1 : 0;
+      if (own[j]) { S.fin[i] = gsc[j]; glogit[i] = glg[j]; fkey[i] = gk[j]; }
+    }
+  }
+  const double best = unord64(wave_max_i64(ord64(fmax(gsc[0], gsc[1]))));
+  const double thr = best + (double)prune;
+  wave_sync();
+  // rank by counting: groups ahead = higher combined score, or the same score and a larger key
+  int rank[2] = {0, 0};
+#pragma unroll 1
+  for (int q = 0; q < nb; ++q) {
+    if (!mark[q]) continue;
+    const double sq = S.fin[q];
+    const unsigned long long kq = fkey[q];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) rank[j] += (sq > gsc[j] || (sq == gsc[j] && kq > gk[j])) ? 1 : 0;
+  }
+  const int nbest = o.nbest;
+  bool kept[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) kept[j] = own[j] && gsc[j] >= thr && rank[j] < nbest;
+  const int count = __popcll(__ballot(kept[0])) + __popcll(__ballot(kept[1]));
+  const int64_t slot0 = (int64_t)b * nbest;
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+    if (kept[j]) {
+      mark[kMaxBeams + rank[j]] = lane + 64 * j;
+      o.logit[slot0 + rank[j]] = glg[j];
+      o.score[slot0 + rank[j]] = gsc[j];
+    }
+  for (int s = count + lane; s < nbest; s += 64) {
+    out_len[slot0 + s] = overflow ? -1 : 0;
+    o.logit[slot0 + s] = -INFINITY;
+    o.score[slot0 + s] = -INFINITY;
+  }
+  if (lane == 0) o.count[b] = count;
+  wave_sync();
+
+  // ---- trace back, as final_pass does, lane l for slots l and l + 64 ----
+  const bool two = count > 64;                               // (uniform)
+  int cur_b[2], n[2] = {0, 0};
+  bool act[2], lead[2] = {true, true};
+  int32_t* out[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int s = lane + 64 * j;
+    act[j] = s < count;
+    cur_b[j] = act[j] ? mark[kMaxBeams + s] : 0;
+    out[j] = out_ids + (slot0 + (act[j] ? s : 0)) * frames_ld;
+  }
+  unsigned int* rows = reinterpret_cast<unsigned int*>(S.tkey);            // [2][kTbRows][kMaxBeams]
+  constexpr int kRowRegs = kTbRows * kMaxBeams / 4 / 64;
+  uint4 rr[kRowRegs];
+  const int nbatch = (frames + kTbRows - 1) / kTbRows;
+  auto tb_request = [&](int j) __attribute__((always_inline)) {
+    const int t_hi = frames - 1 - j * kTbRows, t_lo = max(0, t_hi - kTbRows + 1), nq = (t_hi - t_lo + 1) * (kMaxBeams / 4);
+    const uint4* g = reinterpret_cast<const uint4*>(bp + (int64_t)t_lo * kMaxBeams);
+#pragma unroll
+    for (int k = 0; k < kRowRegs; ++k) rr[k] = 64 * k + lane < nq ? g[64 * k + lane] : make_uint4(0, 0, 0, 0);
+  };
+  auto tb_land = [&](int j) __attribute__((always_inline)) {
+    uint4* dst = reinterpret_cast<uint4*>(rows + (j & 1) * kTbRows * kMaxBeams);
+#pragma unroll
+    for (int k = 0; k < kRowRegs; ++k) dst[64 * k + lane] = rr[k];
+  };
+  auto walk = [&](int j, unsigned int e) __attribute__((always_inline)) {
+    const unsigned int ch = e & 255;
+    if (ch) {
+      const int id = (int)ch - 1;
+      if (!(lead[j] && id == space_id)) {                   // normalise trailing whitespace
+        lead[j] = false;
+        out[j][frames_ld - 1 - n[j]] = id;                  // filled from the back, moved below
+        ++n[j];
+      }
+    }
+    cur_b[j] = (int)(e >> 8);
+  };
+  if (nbatch > 0) { tb_request(0); tb_land(0); }
+  for (int j = 0; j < nbatch; ++j) {
+    if (j + 1 < nbatch) tb_request(j + 1);
+    wave_sync();
+    const int t_hi = frames - 1 - j * kTbRows, t_lo = max(0, t_hi - kTbRows + 1);
+    const unsigned int* rb = rows + (j & 1) * kTbRows * kMaxBeams;
+    for (int tt = t_hi - t_lo; tt >= 0; --tt) {
+      if (act[0]) walk(0, rb[tt * kMaxBeams + cur_b[0]]);
+      if (two && act[1]) walk(1, rb[tt * kMaxBeams + cur_b[1]]);
+    }
+    if (j + 1 < nbatch) tb_land(j + 1);
+    wave_sync();
+  }
+  // out[j][0 .. n) = out[j][frames_ld - n ..): a lane moves its own rows, 16 words at a time, every load of a chunk before
+  // its stores (destination indices lie below the source indices: a chunk never overwrites what a later one reads)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    if (!act[j]) continue;
+    const int off = frames_ld - n[j];
+    if (off > 0) {
+      for (int c0 = 0; c0 < n[j]; c0 += 16) {
+        int v[16];
+#pragma unroll
+        for (int c = 0; c < 16; ++c) v[c] = c0 + c < n[j] ? out[j][off + c0 + c] : 0;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) if (c0 + c < n[j]) out[j][c0 + c] = v[c];
+      }
+    }
+    out_len[slot0 + lane + 64 * j] = overflow ? -1 : n[j];
   }
 }
 

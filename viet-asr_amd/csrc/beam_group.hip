@@ -131,14 +131,15 @@ __device__ inline unsigned long long fix44(float e) {
 }
 
 // grid (B), block 64 W: workgroup g searches utterance g
-template <int W>
+// (the final pass: final_pass into out_res = out_score, or with kNbest final_pass_nbest into the BeamNbest outputs, as beam_wave_kernel)
+template <int W, bool kNbest>
 __global__ __launch_bounds__(64 * W) void beam_group_kernel(const float* __restrict__ logp, int batch, int frames_ld,
                                                              const int32_t* __restrict__ row_frames, int V1, int space_id,
                                                              int beam_width, float token_min_logp, float beam_prune_logp,
                                                              LmView lm, int use_lm, unsigned int* __restrict__ bp_all,
                                                              unsigned long long* __restrict__ eoslog_all,
                                                              int32_t* __restrict__ out_ids, int32_t* __restrict__ out_len,
-                                                             float* __restrict__ out_score) {
+                                                             BeamResult<kNbest> out_res) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   using Lds = GroupLds<W>;
   Lds& S = *reinterpret_cast<Lds*>(smem);
@@ -590,18 +591,33 @@ __global__ __launch_bounds__(64 * W) void beam_group_kernel(const float* __restr
   // every wavefront's back-pointer and log stores have reached L2 before wavefront 0 reads them back
   __syncthreads();
   if (wv != 0) return;
-  final_pass(S, S.tcnt, cur, nb, S.n_log, S.overflow != 0, space_id, use_lm, lm, eoslog, bp, frames, frames_ld, b, out_ids, out_len,
-             out_score);
+  if constexpr (kNbest)
+    final_pass_nbest(S, S.tcnt, cur, nb, S.n_log, S.overflow != 0, space_id, use_lm, lm, eoslog, bp, frames, frames_ld, b,
+                     beam_prune_logp, out_ids, out_len, out_res);
+  else
+    final_pass(S, S.tcnt, cur, nb, S.n_log, S.overflow != 0, space_id, use_lm, lm, eoslog, bp, frames, frames_ld, b, out_ids, out_len,
+               out_res);
 }
 
 template <int W>
 int launch_group(const float* logp, int batch, int frames, int V1, int space_id, int beam_width, float token_min_logp,
                  float beam_prune_logp, const LmView& v, int use_lm, unsigned int* bp, unsigned long long* eoslog,
-                 int32_t* out_ids, int32_t* out_len, float* out_score, hipStream_t st, const int32_t* row_frames) {
+                 int32_t* out_ids, int32_t* out_len, float* out_score, hipStream_t st, const int32_t* row_frames,
+                 const BeamNbest* nbest) {
+  if (nbest) {
+    static std::atomic<uint64_t> lds_opted_nb{0};
+    const hipError_t attr = dyn_lds_opt_in(reinterpret_cast<const void*>(beam_group_kernel<W, true>), (int)sizeof(GroupLds<W>),
+                                           lds_opted_nb);
+    if (attr != hipSuccess) return (int)attr;
+    hipLaunchKernelGGL((beam_group_kernel<W, true>), dim3(batch), dim3(64 * W), sizeof(GroupLds<W>), st, logp, batch, frames,
+                       row_frames, V1, space_id, beam_width, token_min_logp, beam_prune_logp, v, use_lm, bp, eoslog, out_ids,
+                       out_len, *nbest);
+    return 0;
+  }
   static std::atomic<uint64_t> lds_opted{0};   // per device (dyn_lds_opt_in): the table alone is 72 KB
-  const hipError_t attr = dyn_lds_opt_in(reinterpret_cast<const void*>(beam_group_kernel<W>), (int)sizeof(GroupLds<W>), lds_opted);
+  const hipError_t attr = dyn_lds_opt_in(reinterpret_cast<const void*>(beam_group_kernel<W, false>), (int)sizeof(GroupLds<W>), lds_opted);
   if (attr != hipSuccess) return (int)attr;
-  hipLaunchKernelGGL(beam_group_kernel<W>, dim3(batch), dim3(64 * W), sizeof(GroupLds<W>), st, logp, batch, frames, row_frames,
+  hipLaunchKernelGGL((beam_group_kernel<W, false>), dim3(batch), dim3(64 * W), sizeof(GroupLds<W>), st, logp, batch, frames, row_frames,
                      V1, space_id, beam_width, token_min_logp, beam_prune_logp, v, use_lm, bp, eoslog, out_ids, out_len,
                      out_score);
   return 0;
@@ -627,15 +643,15 @@ int beam_group_width(int batch) {
 int launch_beam_search_group(const float* logp, int batch, int frames, int V1, int space_id, int beam_width,
                              float token_min_logp, float beam_prune_logp, const BeamLm* lm, unsigned int* bp,
                              int32_t* out_ids, int32_t* out_len, float* out_score, hipStream_t st,
-                             const int32_t* row_frames) {
+                             const int32_t* row_frames, const BeamNbest* nbest) {
   const int W = beam_group_width(batch);
   if (W == 1) return launch_beam_search_wave(logp, batch, frames, V1, space_id, beam_width, token_min_logp, beam_prune_logp, lm,
-                                             bp, out_ids, out_len, out_score, st, row_frames);
+                                             bp, out_ids, out_len, out_score, st, row_frames, nbest);
   unsigned long long* eoslog = reinterpret_cast<unsigned long long*>(bp + (size_t)batch * frames * kMaxBeams);
   const LmView v = make_lm_view(lm);
   const int use_lm = lm ? 1 : 0;
   return launch_group<4>(logp, batch, frames, V1, space_id, beam_width, token_min_logp, beam_prune_logp, v, use_lm, bp, eoslog,
-                         out_ids, out_len, out_score, st, row_frames);
+                         out_ids, out_len, out_score, st, row_frames, nbest);
 }
 
 }  // namespace vasr

@@ -78,14 +78,17 @@ static_assert(sizeof(WaveLds) == 38528, "a new field changes the LDS per utteran
 static_assert(2 * kTbRows * kMaxBeams * 4 <= (int)(sizeof(unsigned long long) * kTab * 3), "trace-back batches alias tkey + tmx + tsum");
 static_assert(kChars * 2 <= (int)(sizeof(unsigned long long) * 2 * kMaxBeams * 3), "transcript characters alias the beam keys / hashes / logits");
 
-// grid (ceil(B / upw)), block 64 * upw: wavefront w of workgroup g searches utterance g * upw + w, alone
+// grid (ceil(B / upw)), block 64 * upw: wavefront w of workgroup g searches utterance g * upw + w, alone.  The final pass:
+// final_pass into out_res = out_score (float [B]), or with kNbest final_pass_nbest into the BeamNbest outputs (out_ids [B][nbest][T],
+// out_len [B][nbest]).
+template <bool kNbest>
 __global__ __launch_bounds__(256) void beam_wave_kernel(const float* __restrict__ logp, int batch, int frames_ld,
                                                         const int32_t* __restrict__ row_frames, int V1, int space_id,
                                                         int beam_width, float token_min_logp, float beam_prune_logp,
                                                         LmView lm, int use_lm, unsigned int* __restrict__ bp_all,
                                                         unsigned long long* __restrict__ eoslog_all,
                                                         int32_t* __restrict__ out_ids, int32_t* __restrict__ out_len,
-                                                        float* __restrict__ out_score) {
+                                                        BeamResult<kNbest> out_res) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = lane_id(), wv = (int)(threadIdx.x >> 6);
   const int b = (int)blockIdx.x * (int)(blockDim.x >> 6) + wv;
@@ -492,7 +495,11 @@ __global__ __launch_bounds__(256) void beam_wave_kernel(const float* __restrict_
 
   // ---- final: commit pending words (LM score with </s>), merge identical texts, pick the best, trace back ----
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wavefront's back-pointer and log stores have reached L2
-  final_pass(S, S.tsrc, cur, nb, n_log, false, space_id, use_lm, lm, eoslog, bp, frames, frames_ld, b, out_ids, out_len, out_score);
+  if constexpr (kNbest)
+    final_pass_nbest(S, S.tsrc, cur, nb, n_log, false, space_id, use_lm, lm, eoslog, bp, frames, frames_ld, b, beam_prune_logp,
+                     out_ids, out_len, out_res);
+  else
+    final_pass(S, S.tsrc, cur, nb, n_log, false, space_id, use_lm, lm, eoslog, bp, frames, frames_ld, b, out_ids, out_len, out_res);
 }
 
 }  // namespace
@@ -508,16 +515,26 @@ int beam_wave_utts_per_workgroup(int batch) {
 int launch_beam_search_wave(const float* logp, int batch, int frames, int V1, int space_id, int beam_width,
                             float token_min_logp, float beam_prune_logp, const BeamLm* lm, unsigned int* bp,
                             int32_t* out_ids, int32_t* out_len, float* out_score, hipStream_t st,
-                            const int32_t* row_frames) {
+                            const int32_t* row_frames, const BeamNbest* nbest) {
   unsigned long long* eoslog = reinterpret_cast<unsigned long long*>(bp + (size_t)batch * frames * kMaxBeams);
   const LmView v = make_lm_view(lm);
   const int use_lm = lm ? 1 : 0;
   const int upw = beam_wave_utts_per_workgroup(batch);
   const size_t lds = sizeof(WaveLds) * (size_t)upw;
+  if (nbest) {
+    static std::atomic<uint64_t> lds_opted_nb{0};
+    const hipError_t attr = dyn_lds_opt_in(reinterpret_cast<const void*>(beam_wave_kernel<true>), (int)(sizeof(WaveLds) * 4),
+                                           lds_opted_nb);
+    if (attr != hipSuccess) return (int)attr;
+    hipLaunchKernelGGL(beam_wave_kernel<true>, dim3((batch + upw - 1) / upw), dim3(64 * upw), lds, st, logp, batch, frames,
+                       row_frames, V1, space_id, beam_width, token_min_logp, beam_prune_logp, v, use_lm, bp, eoslog, out_ids,
+                       out_len, *nbest);
+    return 0;
+  }
   static std::atomic<uint64_t> lds_opted{0};   // per device (dyn_lds_opt_in)
-  const hipError_t attr = dyn_lds_opt_in(reinterpret_cast<const void*>(beam_wave_kernel), (int)(sizeof(WaveLds) * 4), lds_opted);
+  const hipError_t attr = dyn_lds_opt_in(reinterpret_cast<const void*>(beam_wave_kernel<false>), (int)(sizeof(WaveLds) * 4), lds_opted);
   if (attr != hipSuccess) return (int)attr;
-  hipLaunchKernelGGL(beam_wave_kernel, dim3((batch + upw - 1) / upw), dim3(64 * upw), lds, st, logp, batch, frames,
+  hipLaunchKernelGGL(beam_wave_kernel<false>, dim3((batch + upw - 1) / upw), dim3(64 * upw), lds, st, logp, batch, frames,
                      row_frames, V1, space_id, beam_width, token_min_logp, beam_prune_logp, v, use_lm, bp, eoslog, out_ids,
                      out_len, out_score);
   return 0;

@@ -1359,6 +1359,29 @@ int vasr_beam_search_rows_f32(const float* d_logp, const int32_t* d_row_frames, 
   return check_launch("beam_search");
 }
 
+int vasr_beam_search_nbest_f32(const float* d_logp, const int32_t* d_row_frames, int batch, int64_t frames,
+                               int num_classes, int space_id, int beam_width, int nbest, float token_min_logp,
+                               float beam_prune_logp, const vasr_lm* lm, int32_t* d_ids, int32_t* d_id_len,
+                               int32_t* d_count, double* d_logit_score, double* d_score, void* d_ws, size_t ws_bytes,
+                               vasr_stream stream) {
+  if (!d_logp || !d_ids || !d_id_len || !d_count || !d_logit_score || !d_score || !d_ws || batch <= 0 || frames <= 0)
+    return fail(VASR_ERR_INVALID, "bad argument");
+  if (num_classes < 2 || num_classes > 128 || beam_width < 1 || beam_width > kBeamMax)
+    return fail(VASR_ERR_UNSUPPORTED, "beam search supports 2..128 classes and beam_width 1..%d", kBeamMax);
+  if (nbest < 1 || nbest > beam_width) return fail(VASR_ERR_INVALID, "nbest must be 1..beam_width (%d)", beam_width);
+  if (space_id < -1 || space_id >= num_classes - 1) return fail(VASR_ERR_INVALID, "space_id out of range");
+  const size_t need_bytes = vasr_beam_workspace_bytes(batch, frames);
+  if (ws_bytes < need_bytes) return fail(VASR_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, need_bytes);
+  // the same kernel forms as vasr_beam_search_rows_f32, with the n-best final pass
+  const BeamNbest nb{nbest, d_count, d_logit_score, d_score};
+  const int e = launch_beam_search_group(
+      d_logp, batch, (int)frames, num_classes, space_id < 0 ? 255 : space_id, beam_width, token_min_logp, beam_prune_logp,
+      lm ? &lm->view : nullptr, static_cast<unsigned int*>(d_ws), d_ids, d_id_len, nullptr, static_cast<hipStream_t>(stream),
+      d_row_frames, &nb);
+  if (e) return fail(VASR_ERR_HIP, "beam search: %s", hipGetErrorString((hipError_t)e));
+  return check_launch("beam_search_nbest");
+}
+
 int vasr_lm_create(const void* h_vocab, int vcap, const void* h_ngram, int ncap, const void* h_trie, int trie_buckets,
                    int order, int bos_id, int eos_id, int unk_id, float alpha, float beta, float unk_offset, vasr_lm** out) {
   if (!h_vocab || !h_ngram || !out || vcap <= 0 || ncap <= 0) return fail(VASR_ERR_INVALID, "bad argument");

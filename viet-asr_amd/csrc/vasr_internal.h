@@ -275,19 +275,27 @@ struct BeamLm {  // device-resident hashed back-off n-gram model
   float alpha, beta, unk_offset;
 };
 constexpr int kBeamMax = 128;  // beams kept per utterance at most
+// the n-best form of a search (vasr_beam_search_nbest_f32): out_ids [B][nbest][T], out_len [B][nbest], and these; out_score
+// is not written
+struct BeamNbest {
+  int nbest;               // 1 .. beam_width
+  int32_t* count;          // [B] hypotheses kept
+  double* logit;           // [B][nbest] merged logit score
+  double* score;           // [B][nbest] combined score
+};
 // beam_wave.hip: one wavefront per utterance, `beam_wave_utts_per_workgroup` utterances per workgroup (= compute unit);
 // returns 0 or a hipError_t; row_frames: [batch] frames searched per row, nullptr = all
 int launch_beam_search_wave(const float* logp, int batch, int frames, int V1, int space_id, int beam_width,
                             float token_min_logp, float beam_prune_logp, const BeamLm* lm, unsigned int* bp,
                             int32_t* out_ids, int32_t* out_len, float* out_score, hipStream_t st,
-                            const int32_t* row_frames = nullptr);
+                            const int32_t* row_frames = nullptr, const BeamNbest* nbest = nullptr);
 int beam_wave_utts_per_workgroup(int batch);
 // beam_group.hip: the latency form -- an utterance on `beam_group_width(batch)` wavefronts of one compute unit (4 below 16
 // utterances, else 1 = beam_wave.hip); same results bit for bit.  The entry point of vasr_beam_search_*.
 int launch_beam_search_group(const float* logp, int batch, int frames, int V1, int space_id, int beam_width,
                              float token_min_logp, float beam_prune_logp, const BeamLm* lm, unsigned int* bp,
                              int32_t* out_ids, int32_t* out_len, float* out_score, hipStream_t st,
-                             const int32_t* row_frames = nullptr);
+                             const int32_t* row_frames = nullptr, const BeamNbest* nbest = nullptr);
 int beam_group_width(int batch);
 size_t beam_wave_lds_bytes();
 unsigned long long beam_hash_step(unsigned long long h, unsigned long long v);
