@@ -115,6 +115,19 @@ VASR_API void vasr_destroy(vasr_handle* h);
  * Keys ending in "num_batches_tracked" are accepted and ignored. */
 VASR_API int vasr_load_weight(vasr_handle* h, const char* key, const float* h_data, const int64_t* shape, int ndim);
 
+/* JasperBlock's se / se_reduction_ratio (parts/jasper.py:152-168, :223-253) for block `block`: reduction_ratio 0 = no SE (the
+ * default), else SqueezeExcite(filters, reduction_ratio) -- y = x * sigmoid(W2 relu(W1 mean_t(x))), W1 [filters / r][filters],
+ * W2 [filters][filters / r], no bias -- where the reference puts it: with residual, on every residual pane's branch after its
+ * BN (weights encoder.{i}.res.{p}.2.fc.{0,2}.weight); without, after every sub-layer (after its activation, except the last
+ * one's: after its BN, before the block's output activation), weights encoder.{i}.mconv.{j}.fc.{0,2}.weight with the mconv
+ * indices of the reference's ModuleList (each SE entry shifts the ones behind it).  Between vasr_create and vasr_finalize.
+ * vasr_finalize refuses filters / r == 0 (VASR_ERR_INVALID), filters > 1024 (VASR_ERR_UNSUPPORTED) and missing SE weights
+ * (VASR_ERR_STATE).  The one deliberate difference: the time mean is taken over each row's OWN frames at that layer (sum over
+ * t < len_b, divided by len_b), not over the padded tensor width as nn.AdaptiveAvgPool1d does -- equal whenever the row is as
+ * long as the tensor (every batch-1 call with pad_to = 0, the longest row of a batch), and what keeps a row's result
+ * independent of its batch.  (ABI 8: a function, no layout change.) */
+VASR_API int vasr_set_block_se(vasr_handle* h, int block, int reduction_ratio);
+
 /* Checks that every tensor arrived, folds eval-mode BatchNorm1d(eps=1e-3)
  * (parts/jasper.py:392) into per-channel (scale, shift), packs the 1x1-conv weights
  * K-major for the MFMA kernels and uploads everything.  Needed before any compute call. */

@@ -16,7 +16,7 @@ from . import _lib, stages
 from .core import (AcousticEncodedRepresentation, AudioSignal, DataLayerNM, DeviceType, LengthsType,
                    LogprobsType, MelSpectrogramType, NeuralType, NonTrainableNM, PredictionsType,
                    SpectrogramType, TrainableNM)
-from .engine import blocks_from_config, check_dense_layout
+from .engine import blocks_from_config, check_dense_layout, se_from_config
 from .frontend_tables import frontend_description
 
 __all__ = ["AudioToMelSpectrogramPreprocessor", "JasperEncoder", "JasperDecoderForCTC", "GreedyCTCDecoder",
@@ -108,10 +108,20 @@ class _MaskedConvParams(nn.Module):
         self.conv = nn.Conv1d(cin, cout, k, groups=groups, bias=False)
 
 
-class _JasperBlockParams(nn.Module):
-    """ModuleList skeleton of one JasperBlock (parts/jasper.py:214-288): same indices, parameters only."""
+class _SqueezeExciteParams(nn.Module):
+    """Parameter container with SqueezeExcite's key layout (parts/jasper.py:152-168: ``.fc.0.weight``, ``.fc.2.weight``)."""
 
-    def __init__(self, inplanes, planes, repeat, kernel, separable, residual, residual_panes=()):
+    def __init__(self, channels, reduction_ratio):
+        super().__init__()
+        self.fc = nn.Sequential(nn.Linear(channels, channels // reduction_ratio, bias=False), nn.Identity(),
+                                nn.Linear(channels // reduction_ratio, channels, bias=False))
+
+
+class _JasperBlockParams(nn.Module):
+    """ModuleList skeleton of one JasperBlock (parts/jasper.py:214-288): same indices, parameters only.  se: the
+    SqueezeExcite reduction ratio (0: none)."""
+
+    def __init__(self, inplanes, planes, repeat, kernel, separable, residual, residual_panes=(), se=0):
         super().__init__()
         layers, c = [], inplanes
         for r in range(repeat):
@@ -122,12 +132,15 @@ class _JasperBlockParams(nn.Module):
             layers.append(nn.BatchNorm1d(planes, eps=1e-3, momentum=0.1))
             if r != repeat - 1:
                 layers += [nn.Identity(), nn.Identity()]      # activation, dropout slots
+            if se and not residual:
+                layers.append(_SqueezeExciteParams(planes, se))
             c = planes
         self.mconv = nn.ModuleList(layers)
         self.res = None
-        if residual:   # one 1x1 conv + BN per pane (parts/jasper.py:264-288); no dense panes: the block input alone
+        if residual:   # one 1x1 conv + BN (+ SE) per pane (parts/jasper.py:264-288); no dense panes: the block input alone
             self.res = nn.ModuleList([nn.ModuleList([_MaskedConvParams(ip, planes, 1),
-                                                     nn.BatchNorm1d(planes, eps=1e-3, momentum=0.1)])
+                                                     nn.BatchNorm1d(planes, eps=1e-3, momentum=0.1)]
+                                                    + ([_SqueezeExciteParams(planes, se)] if se else []))
                                       for ip in (list(residual_panes) or [inplanes])])
 
 
@@ -184,6 +197,7 @@ class JasperEncoder(_HipWeights, TrainableNM):
             raise NotImplementedError("implemented: activation='relu', normalization_mode='batch', "
                                       "residual_mode='add', conv_mask=True, frame_splicing=1")
         self._blocks = blocks_from_config(jasper)
+        self._se = se_from_config(jasper)
         self._feat_in = feat_in * frame_splicing
         check_dense_layout(self._blocks, self._feat_in)
         for b in self._blocks:
@@ -191,14 +205,14 @@ class JasperEncoder(_HipWeights, TrainableNM):
                 raise ValueError("Only stride OR dilation may be greater than 1")   # parts/jasper.py:61-62
         layers, c = [], self._feat_in
         residual_panes = []     # ONE list shared by the dense blocks, copied by each (jasper.py:152-161, parts/jasper.py:264)
-        for b in self._blocks:
+        for b, se in zip(self._blocks, self._se):
             k = b["kernel"] + (1 if b["kernel"] % 2 == 0 else 0)
             dense_res = []
             if b["residual_dense"]:
                 residual_panes.append(c)
                 dense_res = residual_panes
             layers.append(_JasperBlockParams(c, b["filters"], b["repeat"], k, bool(b["separable"]), bool(b["residual"]),
-                                             list(dense_res)))
+                                             list(dense_res), se))
             c = b["filters"]
         self.encoder = nn.Sequential(*layers)
         self._c_out = c
@@ -209,7 +223,7 @@ class JasperEncoder(_HipWeights, TrainableNM):
         if self._handle is None:
             if not torch.cuda.is_available():
                 raise _no_gpu()
-            h = _lib.Handle(feat_in=self._feat_in, blocks=self._blocks)
+            h = _lib.Handle(feat_in=self._feat_in, blocks=self._blocks, se=self._se)
             h.load_state_dict(self.state_dict())
             h.finalize()
             self._handle = h

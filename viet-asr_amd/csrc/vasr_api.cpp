@@ -63,9 +63,17 @@ struct ConvLayer {
   int conv_cin = 0;          // non-separable K-tap conv (implicit GEMM over k = tap * conv_cin + c; cin = kernel * conv_cin)
 };
 
+// squeeze-and-excitation (parts/jasper.py:152-168): fc.0 [hidden][c], fc.2 [c][hidden] (encoder_se.hip)
+struct SeLayer {
+  float* d_w1 = nullptr;
+  float* d_w2 = nullptr;
+  int c = 0, hidden = 0;
+};
+
 struct SubBlock {
   bool separable = true;
   ConvLayer dw, pw;
+  SeLayer se;               // se and not residual: after this sub-layer (d_w1 == nullptr: none)
 };
 
 struct Block {
@@ -85,6 +93,13 @@ struct Block {
   // a residual block that is NOT dense right after a dense run receives the run's pane list and takes its (single) residual
   // from pane 0, the run's input, not from its own input (parts/jasper.py:428-436: res_out = xs[0])
   bool res_pane0 = false;
+  // se (vasr_set_block_se): 0 = none, else the reduction ratio.  With residual, one SE per residual pane (res_se[p]); the
+  // residual then always takes the separate-GEMM form, and a dense one runs one GEMM per pane (res_panes[p], channels
+  // res_pane_off[p] .. + res_panes[p].cin of the pane buffer) whose SE-scaled results are summed into R
+  int se_r = 0;
+  std::vector<SeLayer> res_se;
+  std::vector<ConvLayer> res_panes;
+  std::vector<int> res_pane_off;
 };
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -112,6 +127,7 @@ struct vasr_handle {
   int feat_in = 0, dec_feat_in = 0, num_classes = 0;
   std::vector<Block> blocks;
   int pane_c_max = 0;   // channels of the dense-residual pane buffer (0: no dense residual GEMM)
+  int se_c_max = 0;     // widest squeeze-and-excitation (0: the model has none)
   std::vector<LenStep> steps;
   std::map<std::string, HostTensor> weights;
   std::vector<void*> dev_allocs;
@@ -338,6 +354,65 @@ int pack_pointwise(vasr_handle* h, const std::string& key, int cout, int cin, Co
   return upload(h, wt, &L->d_w);
 }
 
+// State-dict prefixes of block i's SqueezeExcite modules in the reference's construction order (parts/jasper.py:214-288):
+// with residual, entry 2 of every residual pane's list (conv, BN, SE); without, the entry after each sub-layer's conv + BN
+// (+ activation and dropout, except after the last one) -- which shifts the mconv indices of everything behind it.
+std::vector<std::string> se_prefixes(const vasr_handle* h, size_t i) {
+  const Block& B = h->blocks[i];
+  std::vector<std::string> out;
+  if (!B.se_r) return out;
+  char key[160];
+  if (B.d.residual) {
+    const int panes = B.dense_panes >= 2 ? B.dense_panes : 1;
+    for (int q = 0; q < panes; ++q) {
+      snprintf(key, sizeof key, "encoder.%zu.res.%d.2", i, q);
+      out.push_back(key);
+    }
+    return out;
+  }
+  int j = 0;
+  for (int r = 0; r < B.d.repeat; ++r) {
+    j += B.d.separable ? 3 : 2;
+    if (r != B.d.repeat - 1) j += 2;
+    snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, j);
+    out.push_back(key);
+    j += 1;
+  }
+  return out;
+}
+
+// vasr_finalize's first check (before anything touches the device): every SE has a non-empty hidden layer, a width the
+// kernels cover, and both of its weights
+int check_se(vasr_handle* h) {
+  for (size_t i = 0; i < h->blocks.size(); ++i) {
+    const Block& B = h->blocks[i];
+    if (!B.se_r) continue;
+    const int c = B.d.filters, hid = c / B.se_r;
+    if (hid == 0)
+      return fail(VASR_ERR_INVALID, "block %zu: se_reduction_ratio %d leaves no hidden unit of %d channels", i, B.se_r, c);
+    if (!se_supported(c, hid))
+      return fail(VASR_ERR_UNSUPPORTED, "block %zu: squeeze-and-excitation over %d channels (at most 1024)", i, c);
+    const HostTensor* t;
+    int rc;
+    for (const std::string& pre : se_prefixes(h, i))
+      if ((rc = need(h, pre + ".fc.0.weight", (size_t)hid * c, &t)) || (rc = need(h, pre + ".fc.2.weight", (size_t)c * hid, &t)))
+        return rc;
+  }
+  return 0;
+}
+
+int load_se(vasr_handle* h, const std::string& pre, int c, int ratio, SeLayer* L) {
+  const HostTensor *w1, *w2;
+  int rc;
+  L->c = c;
+  L->hidden = c / ratio;
+  if ((rc = need(h, pre + ".fc.0.weight", (size_t)L->hidden * c, &w1)) || (rc = need(h, pre + ".fc.2.weight", (size_t)c * L->hidden, &w2)))
+    return rc;
+  if ((rc = upload(h, w1->data, &L->d_w1))) return rc;
+  h->se_c_max = std::max(h->se_c_max, c);
+  return upload(h, w2->data, &L->d_w2);
+}
+
 int build_frontend(vasr_handle* h) {
   const vasr_frontend_desc& fe = h->fe;
   const int nfft = fe.n_fft, nb = nfft / 2 + 1;
@@ -439,10 +514,32 @@ int build_encoder(vasr_handle* h) {
         j += 2;
       }
       if (r != d.repeat - 1) j += 2;  // activation + dropout entries of the ModuleList
+      if (B.se_r && !d.residual) {      // SqueezeExcite entry (parts/jasper.py:233-234, :250-251)
+        snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, j);
+        if ((rc = load_se(h, key, d.filters, B.se_r, &S.se))) return rc;
+        j += 1;
+      }
       c = d.filters;
     }
     B.has_res = d.residual != 0;
-    if (B.has_res && B.dense_panes >= 2) {
+    if (B.has_res && B.se_r) {
+      // one SE per residual pane: the panes' 1x1 convs cannot be summed before their SEs, so each pane is its own GEMM
+      const std::vector<std::string> pre = se_prefixes(h, i);
+      B.res_se.resize(pre.size());
+      for (size_t q = 0; q < pre.size(); ++q)
+        if ((rc = load_se(h, pre[q], d.filters, B.se_r, &B.res_se[q]))) return rc;
+    }
+    if (B.has_res && B.se_r && B.dense_panes >= 2) {
+      B.res_panes.resize(B.dense_panes);
+      for (int q = 0; q < B.dense_panes; ++q) {
+        const Block& P = h->blocks[i - B.dense_panes + 1 + q];
+        snprintf(key, sizeof key, "encoder.%zu.res.%d.0.conv.weight", i, q);
+        if ((rc = pack_pointwise(h, key, d.filters, P.pane_c, &B.res_panes[q]))) return rc;
+        snprintf(key, sizeof key, "encoder.%zu.res.%d.1", i, q);
+        if ((rc = fold_bn(h, key, d.filters, B.res_panes[q].m_pad, &B.res_panes[q]))) return rc;
+        B.res_pane_off.push_back(P.pane_off);
+      }
+    } else if (B.has_res && B.dense_panes >= 2) {
       // dense residual: one GEMM over the run's first dense_panes panes (parts/jasper.py:428-439 for each pane)
       std::vector<SumSrc> src;
       for (int q = 0; q < B.dense_panes; ++q) {
@@ -463,7 +560,8 @@ int build_encoder(vasr_handle* h) {
       const SubBlock& last = B.subs.back();
       const int k1 = last.pw.cin, k2 = cin;
       const int chunk = d.filters % 512 == 0 ? 128 : (d.filters % 256 == 0 ? 64 : 32);
-      if (d.stride == 1 && k1 % chunk == 0 && k2 % chunk == 0 && h->sw.fused_residual && !last.pw.conv_cin && !B.res_pane0) {
+      if (d.stride == 1 && k1 % chunk == 0 && k2 % chunk == 0 && h->sw.fused_residual && !last.pw.conv_cin && !B.res_pane0 &&
+          !B.se_r) {
         char w1[160], bn1[160], w2[160], bn2[160];
         const int jl = j - (last.separable ? 3 : 2);
         snprintf(w1, sizeof w1, "encoder.%zu.mconv.%d.conv.weight", i, jl + (last.separable ? 1 : 0));
@@ -498,7 +596,7 @@ int build_decoder(vasr_handle* h) {
 
 // ---------------- workspace plan ----------------
 struct WsPlan {
-  size_t lens_tab, amax, seq, melp, bufP, bufQ, bufD, bufR, bufS, pane, encp, logits, pred, total;
+  size_t lens_tab, amax, se, seq, melp, bufP, bufQ, bufD, bufR, bufS, pane, encp, logits, pred, total;
   int64_t T, Tp0, T1, Tp1;
   int amax_stride;   // slots per utterance of one maxima table (kAmaxTabs tables: [tab][B][amax_stride] u32)
 };
@@ -540,8 +638,10 @@ WsPlan plan_ws(const vasr_handle* h, int batch, int64_t T) {
         p.amax_stride = std::max(p.amax_stride, pointwise_amax_slots(S.pw.m_pad, pad_frames(t)));
       }
     if (h->pane_c_max) p.amax_stride = std::max(p.amax_stride, 256);   // launch_amax over the pane buffer
+    if (h->se_c_max) p.amax_stride = std::max(p.amax_stride, 256);     // launch_se republishes up to 256 slots
   }
   p.amax = take((size_t)kAmaxTabs * batch * p.amax_stride * 4);
+  p.se = take((size_t)2 * batch * h->se_c_max * 4);   // SE row sums and scales, [B][c] each
   p.seq = take((size_t)batch * 8);
   p.melp = take((size_t)batch * (h->has_encoder ? h->feat_in : 64) * p.Tp0 * 4);
   const size_t mid = (size_t)batch * h->c_mid_max * std::max(tp_mid, p.Tp1) * 4;
@@ -662,6 +762,24 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
     return AmaxTab{};
   };
   int64_t pane_ld = 0;   // pitch of the current dense run's panes: its first block's input pitch
+  // squeeze-and-excitation of a tensor [B][L.c][ld] a GEMM has just stored (encoder_se.hip): pool over t < pool_lens[b],
+  // then y = act(x * s) (acc: y += x * s) over the stored columns, zero from zero_lens[b] on (nullptr: none)
+  float* se_sums = reinterpret_cast<float*>(ws + p.se);
+  float* se_scale = se_sums + (size_t)batch * h->se_c_max;
+  auto run_se = [&](const SeLayer& L, const float* sx, float* sy, int64_t ld, int64_t frames, int store_cols,
+                    const int32_t* pool_lens, const int32_t* zero_lens, int relu, int acc, AmaxTab* am,
+                    const int32_t* lens_y) -> int {
+    SeLaunch a{};
+    a.x = sx; a.y = sy; a.ld = ld; a.bs = 0; a.channels = L.c; a.hidden = L.hidden; a.batch = batch;
+    a.frames = (int)frames; a.store_cols = store_cols; a.lens = pool_lens; a.w1 = L.d_w1; a.w2 = L.d_w2;
+    a.sums = se_sums; a.scale = se_scale; a.zero_lens = zero_lens; a.relu = relu; a.accumulate = acc;
+    a.amax_y = am; a.lens_y = lens_y;
+    ProfScope ps(h, kProfDepthwise, st, 4.0 * L.c * L.hidden * (double)batch,
+                 4.0 * (acc ? 4.0 : 3.0) * L.c * (double)store_cols * batch);
+    const int e = launch_se(a, st);
+    if (e) return fail(VASR_ERR_HIP, "squeeze-and-excitation: %s", hipGetErrorString((hipError_t)e));
+    return 0;
+  };
   for (size_t i = 0; i < h->blocks.size(); ++i) {
     Block& B = h->blocks[i];
     const bool last_block = i + 1 == h->blocks.size();
@@ -686,7 +804,32 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
       HIP_TRY(hipMemcpy2DAsync(panes + (int64_t)B.pane_off * cur_ld, (size_t)pane_bs * 4, cur, (size_t)B.pane_c * cur_ld * 4,
                                (size_t)B.pane_c * cur_ld * 4, batch, hipMemcpyDeviceToDevice, st));
     }
-    if (B.has_res && B.dense_panes >= 2) {
+    if (B.has_res && B.se_r && B.dense_panes >= 2) {
+      // dense residual with SE: sum_p SE_p(BN_p(W_p mask(x_p))) (parts/jasper.py:428-439) -- pane 0's GEMM writes R and is
+      // rescaled in place, every later pane's goes through D and is scaled onto R
+      for (int q = 0; q < B.dense_panes; ++q) {
+        const ConvLayer& W = B.res_panes[q];
+        float* Rq = q == 0 ? R : D;
+        const float* px = panes + (int64_t)B.res_pane_off[q] * cur_ld;
+        PwArgs a{};
+        a.busy_cus = h->busy_cus;
+        a.wt = W.d_w; a.x = px; a.bsx = pane_bs; a.lens = lens(B.first_step); a.scale = W.d_scale; a.shift = W.d_shift;
+        a.res = nullptr; a.y = Rq; a.M = W.m_pad; a.K = W.cin; a.batch = batch;
+        a.ldx = cur_ld; a.ldy = cur_ld; a.ldr = 0; a.frames = (int)cur_T; a.store_cols = (int)cur_ld;
+        a.m_store = W.m_pad; a.relu = 0;
+        if (want_amax) {
+          a.amax_x = free_tab(AmaxTab{});
+          launch_amax(px, cur_ld, W.cin, (int)cur_T, lens(B.first_step), batch, &a.amax_x, st, pane_bs);
+        }
+        {
+          ProfScope ps(h, kProfPointwise, st, 2.0 * W.cin * W.cout * (double)cur_T * batch, 4.0 * W.m_pad * (double)cur_ld * batch);
+          if (run_pointwise(h, a, W, st) < 0) return VASR_ERR_HIP;
+        }
+        if (run_se(B.res_se[q], Rq, R, cur_ld, cur_T, (int)cur_ld, lens(B.first_step), last_block ? nullptr : lens(B.first_step),
+                   0, q > 0, nullptr, nullptr))
+          return VASR_ERR_HIP;
+      }
+    } else if (B.has_res && B.dense_panes >= 2) {
       // dense residual: sum_p BN_p(W_p mask(x_p)) as one GEMM over the first res.cin channels of the pane buffer, every pane
       // masked with the block-input lengths (parts/jasper.py:428-436); fp16 split: one scale from the maxima of all panes
       PwArgs a{};
@@ -719,9 +862,15 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
           launch_amax(panes, cur_ld, B.res.cin, (int)cur_T, lens(B.first_step), batch, &a.amax_x, st, pane_bs);
         }
       }
-      ProfScope ps(h, kProfPointwise, st, 2.0 * B.res.cin * B.res.cout * (double)cur_T * batch,
-                   4.0 * B.res.m_pad * (double)cur_ld * batch);   // bytes of class 2 = what the GEMM STORES (its epilogue's share of the time)
-      if (run_pointwise(h, a, B.res, st) < 0) return VASR_ERR_HIP;
+      {
+        ProfScope ps(h, kProfPointwise, st, 2.0 * B.res.cin * B.res.cout * (double)cur_T * batch,
+                     4.0 * B.res.m_pad * (double)cur_ld * batch);   // bytes of class 2 = what the GEMM STORES (its epilogue's share of the time)
+        if (run_pointwise(h, a, B.res, st) < 0) return VASR_ERR_HIP;
+      }
+      // se and residual: the residual branch's SqueezeExcite, in place on R (parts/jasper.py:279-280)
+      if (B.se_r && run_se(B.res_se[0], R, R, cur_ld, cur_T, (int)cur_ld, lens(B.first_step),
+                           last_block ? nullptr : lens(B.first_step), 0, 0, nullptr, nullptr))
+        return VASR_ERR_HIP;
     }
     int flip = 0;
     for (size_t r = 0; r < B.subs.size(); ++r) {
@@ -767,7 +916,9 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
       const ConvLayer& WF = fuse_res ? B.fused : S.pw;
       // (not in row-independent mode: whether a sub-block is fused depends on the batch's tile count, and the two forms
       // round differently -- that mode promises bit-identical rows whatever the batch)
+      // (a sub-layer whose output feeds an SE: the fused kernel does not produce its row sums)
       if (fused_on && !h->row_independent && S.separable && S.dw.d_ftaps && h->gemm_mode == 3 && want_amax && cur_amax.p && WF.d_w16 &&
+          !S.se.d_w1 &&
           !(last_sub && B.has_res && !B.fused_res) &&
           // a folded residual must come from a 256-channel block input (K = 256 + 256): the kernel's second K range is 4 chunks
           (fuse_res ? (blk_amax.p && blk_ld == cur_ld && WF.cin == 2 * S.dw.cin && B.fused_k1 == S.dw.cin) : WF.cin == S.dw.cin) &&
@@ -841,7 +992,9 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
       a.wt = W.d_w; a.x = gx; a.lens = g_lens; a.scale = W.d_scale; a.shift = W.d_shift;
       a.res = (last_sub && B.has_res && !B.fused_res) ? R : nullptr;
       a.y = dst; a.M = W.m_pad; a.K = W.cin; a.batch = batch;
-      a.ldx = gx_ld; a.ldy = dst_ld; a.ldr = blk_ld; a.frames = (int)g_T; a.m_store = W.m_pad; a.relu = 1;
+      a.ldx = gx_ld; a.ldy = dst_ld; a.ldr = blk_ld; a.frames = (int)g_T; a.m_store = W.m_pad;
+      // se and not residual: the last sub-layer's SE comes before the block's output activation (parts/jasper.py:250-251, mout)
+      a.relu = (last_sub && S.se.d_w1) ? 0 : 1;
       a.store_cols = (dst_ld % kTimeTile == 0) ? (int)dst_ld : (int)g_T;  // port tensors are not padded
       if (W.conv_cin) {
         a.conv_cin = W.conv_cin; a.conv_stride = W.stride; a.conv_dil = W.dilation; a.conv_pad = W.pad;
@@ -866,6 +1019,14 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
         published = run_pointwise(h, a, W, st);
       }
       if (published < 0) return VASR_ERR_HIP;
+      // se and not residual: SE after the sub-layer, pooled over the conv's output lengths; the rescaled tensor's maxima
+      // replace the ones the GEMM published
+      if (S.se.d_w1) {
+        const bool enc_out = last_block && last_sub;
+        if (run_se(S.se, dst, dst, dst_ld, g_T, a.store_cols, lens(S.pw.step + 1), enc_out ? nullptr : lens(S.pw.step + 1),
+                   last_sub ? 1 : 0, 0, published ? &a.amax_y : nullptr, a.lens_y))
+          return VASR_ERR_HIP;
+      }
       cur = dst; cur_ld = dst_ld; cur_T = g_T;
       cur_amax = published ? a.amax_y : AmaxTab{};
     }
@@ -1036,10 +1197,20 @@ int vasr_load_weight(vasr_handle* h, const char* key, const float* data, const i
   return 0;
 }
 
+int vasr_set_block_se(vasr_handle* h, int block, int reduction_ratio) {
+  if (!h) return fail(VASR_ERR_INVALID, "null handle");
+  if (h->finalized) return fail(VASR_ERR_STATE, "handle already finalized");
+  if (block < 0 || block >= (int)h->blocks.size()) return fail(VASR_ERR_INVALID, "block %d of %zu", block, h->blocks.size());
+  if (reduction_ratio < 0) return fail(VASR_ERR_INVALID, "se_reduction_ratio %d is negative", reduction_ratio);
+  h->blocks[block].se_r = reduction_ratio;
+  return 0;
+}
+
 int vasr_finalize(vasr_handle* h) {
   if (!h) return fail(VASR_ERR_INVALID, "null handle");
   if (h->finalized) return 0;
   int rc;
+  if (h->has_encoder && (rc = check_se(h))) return rc;
   if (h->has_frontend && (rc = build_frontend(h))) return rc;
   if (h->has_encoder && (rc = build_encoder(h))) return rc;
   if (h->has_decoder && (rc = build_decoder(h))) return rc;

@@ -250,6 +250,24 @@ int fused_dwpw_taps_per_pair(int kernel);
 float pack_fused_taps(const float* w, int channels, int kernel, float* out);
 int launch_fused_dwpw(const FusedLaunch& f, hipStream_t st, int* amax_n);   // 0, a hipError_t, or -1 (shape not covered)
 
+// ---- squeeze-and-excitation (encoder_se.hip) ----
+// y[b][c][t] = act(x[b][c][t] * s[b][c]) (accumulate: y += x * s), s = sigmoid(W2 relu(W1 mean)), mean = the sum of x over
+// t < min(lens[b], frames) divided by that count; columns t >= zero_lens[b] (nullptr: none) of the stored range
+// [0, store_cols) are stored as 0.  x may equal y.  amax_y (optional): republished over t < lens_y[b] (nullptr: < frames).
+struct SeLaunch {
+  const float* x; float* y;
+  int64_t ld, bs;                 // pitch; batch stride in elements (0: channels * ld)
+  int channels, hidden, batch, frames, store_cols;
+  const int32_t* lens;            // pooling length
+  const float* w1; const float* w2;   // [hidden][channels], [channels][hidden]
+  float* sums; float* scale;      // workspace, [batch][channels] each
+  const int32_t* zero_lens;
+  int relu, accumulate;
+  AmaxTab* amax_y; const int32_t* lens_y;
+};
+bool se_supported(int channels, int hidden);   // channels and hidden in [1, 1024]
+int launch_se(const SeLaunch& a, hipStream_t st);   // 0 or a hipError_t
+
 // ---- CTC head / decode (decode.hip) ----
 // logits [B][ldm rows][ld] (row v, column t) -> logp [B][T][V] (optional), pred [B][T] (optional)
 void launch_logsoftmax_argmax(const float* logits, int64_t row_ld, int64_t batch_stride, int batch, int frames,

@@ -29,8 +29,6 @@ def blocks_from_config(jasper_cfg):
         return int(v[0] if isinstance(v, (list, tuple)) else v)
     out = []
     for l in jasper_cfg:
-        if l.get("se", False):
-            raise NotImplementedError("JasperBlock option 'se' is not implemented")
         if l.get("groups", 1) != 1 or l.get("heads", -1) != -1 or float(l.get("kernel_size_factor", 1.0)) != 1.0:
             raise NotImplementedError("groups/heads/kernel_size_factor other than the defaults are not implemented")
         out.append(dict(filters=int(l["filters"]), repeat=int(l["repeat"]), kernel=one(l["kernel"]),
@@ -38,6 +36,24 @@ def blocks_from_config(jasper_cfg):
                         residual=int(bool(l["residual"])), separable=int(bool(l.get("separable", False))),
                         residual_dense=int(bool(l.get("residual_dense", False)))))
     check_dense_layout(out)
+    return out
+
+
+def se_from_config(jasper_cfg):
+    """Per block of a YAML block list: JasperBlock's SqueezeExcite reduction ratio (``se_reduction_ratio``, default 16,
+    jasper.py:168-169), 0 for a block without ``se`` -- the argument of vasr_set_block_se."""
+    out = []
+    for l in jasper_cfg:
+        if not l.get("se", False):
+            out.append(0)
+            continue
+        r = l.get("se_reduction_ratio", 16)
+        if int(r) != r or r <= 0:
+            raise ValueError(f"se_reduction_ratio must be a positive integer, got {r!r}")
+        if int(l["filters"]) // int(r) == 0:
+            raise ValueError(f"se_reduction_ratio {r} leaves no hidden unit of {l['filters']} channels "
+                             "(the reference builds a zero-width Linear)")
+        out.append(int(r))
     return out
 
 
@@ -91,10 +107,11 @@ class QuartzNetCTC:
         self.frontend = frontend_description(pre)
         self.hop = self.frontend["hop_length"]
         self._blocks = blocks_from_config(jas)
+        self._se = se_from_config(jas)
         with torch.cuda.device(self.device):
             self.handle = _lib.Handle(frontend=self.frontend, feat_in=pre.get("features", 64),
                                       blocks=blocks_from_config(jas), dec_feat_in=jas[-1]["filters"],
-                                      num_classes=len(self.labels) + 1)
+                                      num_classes=len(self.labels) + 1, se=self._se)
             self.handle.load_state_dict(encoder_state)
             self.handle.load_state_dict(decoder_state)
             self.handle.finalize()
@@ -244,6 +261,9 @@ class QuartzNetCTC:
         tolerance and a frame whose two best classes are closer than that may decode differently (round-6 campaign,
         tests/devtools/fuzz_long.py: 14 444 exact cases bit-equal; 2 such frames in 7 048 f16x2 recordings).  Returns dict(ids, id_len, pred, enc_len, logp or None, workspace_bytes)."""
         from . import stages
+        if any(self._se):
+            # the halo windows assume a finite receptive field; an SE's time mean makes it the whole recording
+            raise NotImplementedError("forward_long: a model with squeeze-and-excitation (se) has no finite receptive field")
         if wav.dim() != 1 or wav.device.type != "cuda" or wav.dtype != torch.float32:
             raise ValueError("wav must be a 1-D float32 cuda tensor")
         h = self.handle

@@ -71,6 +71,7 @@ def encoder_state_dict(jasper_cfg, feat_in, seed=0):
     for i, l in enumerate(jasper_cfg):
         cout, rep, k = l["filters"], l["repeat"], kernel_of(l)
         sep = l.get("separable", False)
+        se = l.get("se_reduction_ratio", 16) if l.get("se", False) else 0
         c = cin
         j = 0
         for r in range(rep):
@@ -87,6 +88,9 @@ def encoder_state_dict(jasper_cfg, feat_in, seed=0):
                 j += 2
             if r != rep - 1:
                 j += 2  # activation + dropout slots
+            if se and not l["residual"]:
+                _se(f"{p}.{j}", seed, cout, se, sd)
+                j += 1
             c = cout
         panes = [cin]
         if l.get("residual_dense", False):
@@ -97,8 +101,19 @@ def encoder_state_dict(jasper_cfg, feat_in, seed=0):
                 p = f"encoder.{i}.res.{q}"
                 sd[f"{p}.0.conv.weight"] = _conv_weight(f"{p}.0.conv.weight", seed, cout, ip, 1, gain=G_RES / np.sqrt(len(panes)))
                 _bn(f"{p}.1", seed, cout, sd)
+                if se:
+                    _se(f"{p}.2", seed, cout, se, sd)
         cin = cout
     return sd
+
+
+def _se(prefix, seed, c, ratio, sd):
+    """SqueezeExcite weights (fc.0 [c // r][c], fc.2 [c][c // r]), each from its own key-named stream like every other
+    tensor, so the weights of a model without SE are what they were.  fc.2's entries lean positive (the hidden units are
+    ReLU'd), so most scales sit near 1 with a spread below it, and a stack of SEs does not shrink the activations to nothing."""
+    h = c // ratio
+    sd[f"{prefix}.fc.0.weight"] = _rs(f"{prefix}.fc.0.weight", seed).normal(0, 1.0 / np.sqrt(c), size=(h, c)).astype(np.float32)
+    sd[f"{prefix}.fc.2.weight"] = _rs(f"{prefix}.fc.2.weight", seed).normal(3.0, 2.0, size=(c, h)).astype(np.float32) / np.float32(np.sqrt(h))
 
 
 def decoder_state_dict(feat_in, num_classes_with_blank, seed=0):
