@@ -220,9 +220,34 @@ def _first(v):
     return v[0] if isinstance(v, (list, tuple)) else v
 
 
-def jasper_block_forward(x, lens, sd, i, lcfg, panes=None):
+def squeeze_excite(x, lens, sd, prefix, se_mean="rows"):
+    """SqueezeExcite.forward (parts/jasper.py:152-168): x * sigmoid(W2 relu(W1 mean_t(x))), bias-free, in x's dtype.
+
+    se_mean="rows" (default) averages each row over its own frames t < lens[b] (lens truncated as the next mask truncates
+    them): the device's documented semantics (vasr.h vasr_set_block_se).  se_mean="width" is the
+    reference's nn.AdaptiveAvgPool1d(1) over the whole tensor width, padding included; the two agree wherever a row is as long
+    as the tensor (every batch-1 call)."""
+    if se_mean == "width":
+        m = x.mean(dim=2)
+    elif se_mean == "rows":
+        n = lens.to(dtype=torch.long).clamp(0, x.shape[2])
+        keep = torch.arange(x.shape[2])[None, :] < n[:, None]
+        m = (x * keep[:, None, :].to(x.dtype)).sum(dim=2) / n.clamp(min=1)[:, None].to(x.dtype)   # (an empty row: mean 0)
+    else:
+        raise ValueError("se_mean: 'rows' or 'width'")
+    h = F.relu(F.linear(m, _t(sd[f"{prefix}.fc.0.weight"], x.dtype)))
+    s = torch.sigmoid(F.linear(h, _t(sd[f"{prefix}.fc.2.weight"], x.dtype)))
+    return x * s[:, :, None]
+
+
+def jasper_block_forward(x, lens, sd, i, lcfg, panes=None, se_mean="rows"):
     """JasperBlock.forward (parts/jasper.py:408-448) for the layouts the shipped configs and the Jasper-DR layouts use:
-    residual_mode='add', no SE, groups=1, heads=-1, activation ReLU, dropout = identity (eval).
+    residual_mode='add', groups=1, heads=-1, activation ReLU, dropout = identity (eval).
+
+    SE (lcfg["se"], parts/jasper.py:223-253): without residual, after every sub-layer -- after its activation, except the
+    last one's, which comes after its BN and before the block's output activation; with residual, on every residual pane
+    after its BN (dense panes included) and never in mconv.  Each SE entry shifts the mconv indices behind it.  The time mean
+    follows `se_mean` (squeeze_excite).
 
     panes: the block's input list (the reference's ``xs``, parts/jasper.py:411-414) -- None means ``[x]``.  The convs
     read its last entry (``x``, :417).  Residual p (``encoder.{i}.res.{p}``) is BN(1x1 conv(mask(panes[p]))) with
@@ -237,6 +262,7 @@ def jasper_block_forward(x, lens, sd, i, lcfg, panes=None):
     stride, dil = _first(lcfg["stride"]), _first(lcfg["dilation"])
     pad = get_same_padding(k, stride, dil)
     rep, sep = lcfg["repeat"], lcfg.get("separable", False)
+    se = bool(lcfg.get("se", False))
     lens_orig = lens
     out, j = x, 0
     for r in range(rep):
@@ -254,17 +280,22 @@ def jasper_block_forward(x, lens, sd, i, lcfg, panes=None):
         if r != rep - 1:
             out = F.relu(out)
             j += 2
+        if se and not lcfg["residual"]:
+            out = squeeze_excite(out, lens, sd, f"{p}.{j}", se_mean)
+            j += 1
     if lcfg["residual"]:
         n_res = len(xs) if lcfg.get("residual_dense", False) else 1      # one residual conv per pane (jasper.py:152-161)
         for q in range(n_res):
             p = f"encoder.{i}.res.{q}"
             res, _ = masked_conv1d(xs[q], lens_orig, _t(sd[f"{p}.0.conv.weight"], x.dtype))
             res = _bn_eval(res, sd, f"{p}.1")
+            if se:
+                res = squeeze_excite(res, lens_orig, sd, f"{p}.2", se_mean)
             out = out + res                                                    # :438-439
     return F.relu(out), lens                                                   # :444 mout
 
 
-def encoder_forward(mel, length, sd, jasper_cfg, dtype=torch.float32):
+def encoder_forward(mel, length, sd, jasper_cfg, dtype=torch.float32, se_mean="rows"):
     """JasperEncoder.forward (jasper.py:198-204): Sequential of JasperBlocks passing a LIST of tensors.
     A block with residual_dense and a residual appends its output to the list it received (parts/jasper.py:446-447: the
     list grows by one pane per dense block); every other block passes on a list of its output alone.  The encoder returns
@@ -272,13 +303,14 @@ def encoder_forward(mel, length, sd, jasper_cfg, dtype=torch.float32):
     Returns (outputs [B,C,T'] f32, encoded_lengths [B] float32 -- quirk Q3).
     dtype=torch.float64 runs the SAME graph in double precision: not the reference's arithmetic (that is float32, the
     default) but the reference's function without its rounding -- the tests use it to tell a frame on which two float32
-    computations may legitimately disagree (a top-2 tie inside float32 rounding) from a wrong answer."""
+    computations may legitimately disagree (a top-2 tie inside float32 rounding) from a wrong answer.
+    se_mean: the time mean of squeeze-and-excitation blocks, see squeeze_excite."""
     x = torch.as_tensor(mel).to(dtype)
     lens = torch.as_tensor(length)
     xs = [x]
     with torch.no_grad():
         for i, l in enumerate(jasper_cfg):
-            out, lens = jasper_block_forward(xs[-1], lens, sd, i, l, panes=xs)
+            out, lens = jasper_block_forward(xs[-1], lens, sd, i, l, panes=xs, se_mean=se_mean)
             xs = xs + [out] if (l["residual"] and l.get("residual_dense", False)) else [out]
     return xs[-1], lens
 

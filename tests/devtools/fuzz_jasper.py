@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Randomised whole-path comparison of JASPER layouts against the oracle (dev tool, GPU):
 
-    python tests/devtools/fuzz_jasper.py [n_cases] [seed0] [max_seconds]
+    python tests/devtools/fuzz_jasper.py [n_cases] [seed0] [max_seconds] [se]
 
 The Jasper counterpart of fuzz_encoder.py.  Each case draws a layout the reference can run: a non-separable prologue (strided
 or not), ONE contiguous dense run of 1-4 blocks (every one residual and dense; its pane buffer and dense-residual GEMMs),
@@ -10,7 +10,8 @@ filters 128-384 (the library refuses widths that are not multiples of 128), kern
 of 1-5 / 6-20 / 21-72 rows of short clips with one very short row, so that the product's own choice of CONV tile is
 exercised, in a randomly drawn GEMM arithmetic.  Checks against oracle.quartznet_oracle (which runs dense residuals):
 log-probs within the goldens' tolerance, encoded lengths equal, predictions equal wherever the oracle's margin exceeds twice
-the tolerance, everything finite.  Prints one summary line."""
+the tolerance, everything finite.  A fourth argument "se" adds squeeze-and-excitation draws (draw_se: flag, ratio and
+excitation regime per case, from streams of their own, so the layouts stay those of the plain run).  Prints one summary line."""
 import os
 import sys
 import time
@@ -24,7 +25,8 @@ from viet_asr_amd import configs, synth  # noqa: E402
 from viet_asr_amd.engine import QuartzNetCTC  # noqa: E402
 from oracle import quartznet_oracle as O  # noqa: E402  (checker only)
 
-STATS = {"cases": 0, "rows": 0, "worst_err_over_tol": 0.0, "by_batch_class": [0, 0, 0], "dense_blocks": 0}
+STATS = {"cases": 0, "rows": 0, "worst_err_over_tol": 0.0, "by_batch_class": [0, 0, 0], "dense_blocks": 0, "se_blocks": 0}
+SE_REGIMES = ("synthetic", "mixed", "strong")
 FLOP_BUDGET = 1.5e10            # per case, for the oracle's float32 convolutions on the CPU
 
 
@@ -53,6 +55,31 @@ def random_jasper_layout(rng):
     return jas
 
 
+def draw_se(jas, case):
+    """Opt-in squeeze-and-excitation draws, from a stream of their own (the layout's draws are untouched): each block gets SE
+    with probability 0.6 and a ratio leaving 1 ... filters hidden units; one excitation regime per case.  -> regime."""
+    rng = np.random.default_rng(920000 + case)
+    for b in jas:
+        if rng.random() < 0.6:
+            b["se"] = True
+            b["se_reduction_ratio"] = int(rng.choice([1, 2, 5, 8, 16, 48, b["filters"]]))
+    return str(rng.choice(SE_REGIMES))
+
+
+def apply_se_regime(sd, regime, case):
+    """synthetic: synth's own SE weights (s close to 1); mixed: W1 ~ N(0, 1/C), W2 ~ N(0, 9/h) (s across (0, 1)); strong:
+    W2 ~ -|N(6, 3)| / sqrt(h) (most s far below 1 -- the republished fp16-split maxima carry the next layer)."""
+    rng = np.random.default_rng(930000 + case)
+    for k in sorted(sd):
+        if regime == "mixed" and k.endswith(".fc.0.weight"):
+            h, c = sd[k].shape
+            sd[k] = rng.normal(0, 1 / np.sqrt(c), (h, c)).astype(np.float32)
+        elif regime in ("mixed", "strong") and k.endswith(".fc.2.weight"):
+            c, h = sd[k].shape
+            w = rng.normal(0, 3, (c, h)) if regime == "mixed" else -np.abs(rng.normal(6, 3, (c, h)))
+            sd[k] = (w / np.sqrt(h)).astype(np.float32)
+
+
 def _flops(jas, T):
     c, f = 64, 0.0
     for b in jas:
@@ -61,7 +88,8 @@ def _flops(jas, T):
     return f
 
 
-def jasper_case(case):
+def jasper_case(case, se=False):
+    """se=True: SE drawn on top of the case's layout (draw_se / apply_se_regime); se=False draws exactly what it always did."""
     rng = np.random.default_rng(910000 + case)
     cls = int(rng.integers(0, 3))
     B = int(rng.integers(1, 6)) if cls == 0 else int(rng.integers(6, 21)) if cls == 1 else int(rng.integers(21, 73))
@@ -70,8 +98,12 @@ def jasper_case(case):
         jas = random_jasper_layout(rng)
         if _flops(jas, B * (1 + L // 160)) <= FLOP_BUDGET:
             break
+    regime = draw_se(jas, case) if se else None
     cfg = configs.jasper_definition(jas)
     enc_sd = synth.encoder_state_dict(jas, 64, case)
+    if se:
+        apply_se_regime(enc_sd, regime, case)
+        STATS["se_blocks"] += sum(1 for b in jas if b.get("se"))
     dec_sd = synth.decoder_state_dict(jas[-1]["filters"], len(cfg["labels"]) + 1, case)
     gemm = str(rng.choice(["f16x2", "f16x2", "bf16x3", "fp32"]))
     eng = QuartzNetCTC(cfg, enc_sd, dec_sd, gemm=gemm)
@@ -97,22 +129,23 @@ def jasper_case(case):
           and bool((r["pred"].cpu()[clear] == ref["pred"][clear]).all()))
     if ok:
         return None
-    return (f"jasper case {case}: gemm {gemm} B {B} L {L} err {err:.3e} tol {tol:.3e} blocks "
-            f"{[(b['filters'], b['kernel'][0], b['repeat'], b['stride'][0], b['dilation'][0], b['residual'], b.get('residual_dense', False)) for b in jas]}")
+    return (f"jasper case {case}: gemm {gemm} B {B} L {L} err {err:.3e} tol {tol:.3e} se {regime} blocks "
+            f"{[(b['filters'], b['kernel'][0], b['repeat'], b['stride'][0], b['dilation'][0], b['residual'], b.get('residual_dense', False), b.get('se_reduction_ratio', 0) if b.get('se') else 0) for b in jas]}")
 
 
 if __name__ == "__main__":
     N = int(sys.argv[1]) if len(sys.argv) > 1 else 30
     S0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     LIMIT = float(sys.argv[3]) if len(sys.argv) > 3 else 1e9
+    SE = len(sys.argv) > 4 and sys.argv[4] == "se"
     t0, bad = time.time(), 0
     for case in range(S0, S0 + N):
         if time.time() - t0 > LIMIT:
             break
-        msg = jasper_case(case)
+        msg = jasper_case(case, se=SE)
         if msg:
             bad += 1
             print("MISMATCH", msg, flush=True)
     print(f"{STATS['cases']} Jasper cases from {S0} ({STATS['rows']} rows; batches of 1-5 / 6-20 / 21-72 rows: {STATS['by_batch_class']}; "
-          f"{STATS['dense_blocks']} dense blocks), {bad} mismatches, worst error {STATS['worst_err_over_tol']:.2f} x the tolerance, "
+          f"{STATS['dense_blocks']} dense blocks, {STATS['se_blocks']} SE blocks), {bad} mismatches, worst error {STATS['worst_err_over_tol']:.2f} x the tolerance, "
           f"{time.time() - t0:.0f} s")

@@ -208,3 +208,113 @@ def test_float64_restatement_matches_the_reference_fixtures(name):
         assert float(np.abs(logp - want).max()) <= tol, (name, i)
         assert np.array_equal(logp.argmax(-1), g[f"pred64_{i}"]), (name, i)
         assert int(el[0]) == int(g[f"enc_len_{i}"][0])
+
+
+# ---- the oracle's SE (oracle.quartznet_oracle.squeeze_excite / jasper_block_forward): the three fixtures, ragged batches -----
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_oracle_in_float64_matches_the_reference_fixtures(name):
+    """oracle.encoder_forward (float64, row means) on each fixture row, as _encoder64 above: the oracle puts SE where the
+    reference does, on every layout the fixtures hold (residual panes, dense panes, after every non-residual sub-layer)."""
+    from viet_asr_amd import synth
+    from oracle import quartznet_oracle as O
+    g = _golden(name)
+    jas = json.loads(str(g["definition"]))
+    seed = int(g["seed"])
+    sd = synth.encoder_state_dict(jas, 64, seed)
+    dec = synth.decoder_state_dict(jas[-1]["filters"], 29, seed)
+    for i in range(len(g["lens"])):
+        mel = g[f"mel_{i}"]
+        lens = torch.tensor([mel.shape[2]])
+        e, el = O.encoder_forward(mel, lens, sd, jas, dtype=torch.float64)
+        e2, _ = _encoder64(mel, lens, sd, jas)
+        assert float((e - e2).abs().max()) <= 1e-9 * max(1.0, float(e2.abs().max())), (name, i)
+        logp = O.decoder_forward(e, dec).numpy()
+        want = g[f"logp_{i}"]
+        assert logp.shape == want.shape
+        tol = max(5e-4, 2e-5 * float(np.abs(want).max()))
+        assert float(np.abs(logp - want).max()) <= tol, (name, i)
+        assert np.array_equal(logp.argmax(-1), g[f"pred64_{i}"]), (name, i)
+        assert int(el[0]) == int(g[f"enc_len_{i}"][0])
+
+
+# layouts of every SE placement: separable residual, non-residual (SE after every sub-layer), a dense run, a strided K-tap
+# non-separable prologue (pooled at the strided lengths), a plain block behind an SE block
+SE_LAYOUT = [
+    dict(filters=128, repeat=2, kernel=[11], stride=[2], dilation=[1], dropout=0.0, residual=False, se=True,
+         se_reduction_ratio=8),
+    dict(filters=128, repeat=3, kernel=[7], stride=[1], dilation=[1], dropout=0.0, residual=True, separable=True, se=True,
+         se_reduction_ratio=4),
+    dict(filters=128, repeat=2, kernel=[5], stride=[1], dilation=[1], dropout=0.0, residual=True, residual_dense=True, se=True,
+         se_reduction_ratio=16),
+    dict(filters=128, repeat=1, kernel=[3], stride=[1], dilation=[1], dropout=0.0, residual=True, residual_dense=True, se=True,
+         se_reduction_ratio=128),
+    dict(filters=128, repeat=2, kernel=[9], stride=[1], dilation=[1], dropout=0.0, residual=False, separable=True, se=True,
+         se_reduction_ratio=1),
+    dict(filters=128, repeat=1, kernel=[13], stride=[1], dilation=[1], dropout=0.0, residual=True, separable=True),
+]
+
+
+def _ragged_mel(lens, T, seed):
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((len(lens), 64, T))
+    for b, n in enumerate(lens):
+        x[b, :, n:] = 3.0 * rng.standard_normal((64, T - n))      # garbage past each row's length: the masks must hide it
+    return x
+
+
+def test_oracle_row_means_make_a_ragged_batch_equal_its_rows_alone():
+    """Row means: every row of a ragged batch equals that row run alone at batch 1 (where the tensor is the row's own width),
+    to float64 round-off, valid frames compared.  Lengths 1 and 2 reach a 1-frame row through the stride-2 prologue."""
+    from viet_asr_amd import synth
+    from oracle import quartznet_oracle as O
+    sd = synth.encoder_state_dict(SE_LAYOUT, 64, 5)
+    lens = np.array([90, 1, 2, 37, 64, 89], dtype=np.int64)
+    x = _ragged_mel(lens, 90, 5)
+    y, yl = O.encoder_forward(x, torch.from_numpy(lens), sd, SE_LAYOUT, dtype=torch.float64)
+    for b, n in enumerate(lens):
+        one, ol = O.encoder_forward(x[b:b + 1, :, :n], torch.from_numpy(lens[b:b + 1]), sd, SE_LAYOUT, dtype=torch.float64)
+        f = int(ol[0])
+        assert f == int(yl[b]) and one.shape[2] == f
+        assert float((y[b, :, :f] - one[0]).abs().max()) <= 1e-12 * max(1.0, float(one.abs().max())), (b, n)
+
+
+def test_oracle_width_means_differ_on_a_ragged_batch():
+    """The reference's own mean (se_mean="width": the padded tensor width) is not the device's: on a ragged batch a short row
+    differs from its batch-1 call, while the longest row (as long as the tensor) and any batch-1 call agree in both modes --
+    the documented deviation (vasr.h vasr_set_block_se)."""
+    from viet_asr_amd import synth
+    from oracle import quartznet_oracle as O
+    sd = synth.encoder_state_dict(SE_LAYOUT, 64, 5)
+    lens = np.array([90, 37], dtype=np.int64)
+    x = _ragged_mel(lens, 90, 6)
+    L = torch.from_numpy(lens)
+    rows = O.encoder_forward(x, L, sd, SE_LAYOUT, dtype=torch.float64)[0]
+    width = O.encoder_forward(x, L, sd, SE_LAYOUT, dtype=torch.float64, se_mean="width")[0]
+    f = int(O.encoder_forward(x[1:, :, :37], L[1:], sd, SE_LAYOUT, dtype=torch.float64)[1][0])
+    scale = float(rows[1, :, :f].abs().max())
+    assert float((width[1, :, :f] - rows[1, :, :f]).abs().max()) > 1e-3 * scale
+    assert float((width[0] - rows[0]).abs().max()) <= 1e-12 * max(1.0, float(rows[0].abs().max()))
+    one_w = O.encoder_forward(x[1:, :, :37], L[1:], sd, SE_LAYOUT, dtype=torch.float64, se_mean="width")[0]
+    assert float((one_w[0] - rows[1, :, :f]).abs().max()) <= 1e-12 * max(1.0, scale)
+    with pytest.raises(ValueError):
+        O.encoder_forward(x, L, sd, SE_LAYOUT, dtype=torch.float64, se_mean="frames")
+
+
+def test_finalize_refuses_se_wider_than_1024_channels():
+    """1152 channels: past the two 1024-float LDS arrays of se_mlp_kernel -- VASR_ERR_UNSUPPORTED from vasr_finalize's first
+    check, before any weight is looked at or anything touches a device (this runs without one).  1024 passes that check and
+    stops at the missing weights instead (VASR_ERR_STATE).  The codes are read from include/vasr.h."""
+    import re
+    from viet_asr_amd import _lib, engine
+    codes = dict(re.findall(r"(VASR_ERR_\w+) = (-\d+)", open(os.path.join(HERE, "..", "include", "vasr.h")).read()))
+    unsupported, state = int(codes["VASR_ERR_UNSUPPORTED"]), int(codes["VASR_ERR_STATE"])
+    L = _lib.lib()
+    for filters, ratio, want in ((1152, 8, unsupported), (1152, 1152, unsupported), (1024, 1, state), (1024, 1024, state)):
+        jas = [dict(filters=filters, repeat=1, kernel=[1], stride=[1], dilation=[1], dropout=0.0, residual=False, se=True,
+                    se_reduction_ratio=ratio)]
+        h = _handle(engine.blocks_from_config(jas), engine.se_from_config(jas))
+        assert L.vasr_finalize(h.h) == want, (filters, ratio)
+        if want == unsupported:
+            assert "1152 channels" in L.vasr_last_error().decode()
+        h.close()

@@ -576,8 +576,10 @@ int build_encoder(vasr_handle* h) {
     if (d.filters % 128)
       return fail(VASR_ERR_UNSUPPORTED, "block %zu: filters %d is not a multiple of 128", i, d.filters);
     cin = d.filters;
-    // mid-pipeline buffers hold every block output but the last one, plus a last-block residual
-    if ((i + 1 < h->blocks.size() || B.has_res) && cin > h->c_mid_max) h->c_mid_max = cin;
+    // mid-pipeline buffers hold every block output but the last one, a last-block residual, and the sub-layer outputs (and
+    // their depthwise outputs in D) inside a last block of more than one sub-layer: only the last sub-layer of the last
+    // block writes the encoder output directly
+    if ((i + 1 < h->blocks.size() || B.has_res || B.subs.size() > 1) && cin > h->c_mid_max) h->c_mid_max = cin;
   }
   h->c_last = cin;
   return upload(h, h->steps, &h->d_steps);
