@@ -128,6 +128,25 @@ VASR_API int vasr_load_weight(vasr_handle* h, const char* key, const float* h_da
  * independent of its batch.  (ABI 8: a function, no layout change.) */
 VASR_API int vasr_set_block_se(vasr_handle* h, int block, int reduction_ratio);
 
+/* JasperBlock's groups / heads (parts/jasper.py:70-150, :329-400) for block `block`; groups 1 and heads -1 are the defaults.
+ * groups = G > 1: every main-branch conv of the block -- the 1x1 after each depthwise conv of a separable block, the K-tap (or
+ * 1x1) conv of a non-separable one -- is grouped, weight [filters][C_in / G][K], and followed (after its BN) by the
+ * reference's GroupShuffle: output channel j * G + g holds pre-shuffle channel g * (filters / G) + j.  The shuffle is its own
+ * ModuleList entry, so every later mconv index (and SE entry) moves by one per sub-layer.  Residual branches, dense panes
+ * included, are never grouped; they are added after the shuffle.  heads = H > 0: the depthwise weight of a separable block is
+ * [H][1][K] and channel c uses row c % H; on a block that is not separable heads is ignored, as the reference ignores it
+ * there (it never hands heads to a non-separable conv).  Between vasr_create and vasr_finalize.  vasr_finalize refuses,
+ * before it touches a device, groups that do not divide a sub-layer's in- and out-channels and C % heads != 0
+ * (VASR_ERR_INVALID), a grouped block whose filters are not a multiple of 128 (VASR_ERR_UNSUPPORTED, the rule for every
+ * block), and a grouped or shared conv weight that is missing (VASR_ERR_STATE) or not of the exact shape above
+ * (VASR_ERR_INVALID).  What runs where: in the split arithmetics (f16x2, bf16x3, bf16x2) a grouped layer whose per-group
+ * widths filters / G and C_in / G are multiples of 64 runs the grouped split GEMM (encoder_pw_split.hip: one workgroup per
+ * tile of one group, K = taps * C_in / G, the shuffle applied in its store).  Narrower groups -- e.g. a first block reading the 64 mel
+ * features at G >= 2 -- and every grouped layer in the fp32 mode run the dense kernels on the block-diagonal form of the
+ * weight (rows and BN permuted by the shuffle).  Grouped blocks never take the fused depthwise + pointwise kernel or the folded
+ * dual-source residual GEMM.  (ABI 8: a function, no layout change.) */
+VASR_API int vasr_set_block_groups(vasr_handle* h, int block, int groups, int heads);
+
 /* Checks that every tensor arrived, folds eval-mode BatchNorm1d(eps=1e-3)
  * (parts/jasper.py:392) into per-channel (scale, shift), packs the 1x1-conv weights
  * K-major for the MFMA kernels and uploads everything.  Needed before any compute call. */

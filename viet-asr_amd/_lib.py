@@ -67,6 +67,7 @@ SIGNATURES = {
     "vasr_set_row_independent": (C.c_int, [_P, C.c_int]),
     "vasr_set_busy_cus": (C.c_int, [_P, C.c_int]),
     "vasr_set_block_se": (C.c_int, [_P, C.c_int, C.c_int]),
+    "vasr_set_block_groups": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     "vasr_beam_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
     "vasr_beam_search_f32": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P,
                                        _P, _P, _P, _P, C.c_size_t, _P]),
@@ -168,8 +169,9 @@ def _fptr(a):
 class Handle:
     """Owns one vasr_handle: any subset of {front end, encoder, CTC head}."""
 
-    def __init__(self, frontend=None, feat_in=0, blocks=None, dec_feat_in=0, num_classes=0, se=None):
-        """se: per block, the squeeze-and-excitation reduction ratio (0 = none; engine.se_from_config)."""
+    def __init__(self, frontend=None, feat_in=0, blocks=None, dec_feat_in=0, num_classes=0, se=None, groups=None):
+        """se: per block, the squeeze-and-excitation reduction ratio (0 = none; engine.se_from_config).  groups: per block,
+        (groups, heads) (engine.groups_from_config; (1, -1) = none)."""
         L = lib()
         self._keep = []
         md = ModelDesc()
@@ -206,6 +208,9 @@ class Handle:
         for i, r in enumerate(se or []):
             if r:
                 check(L.vasr_set_block_se(h, i, int(r)))
+        for i, (g, hd) in enumerate(groups or []):
+            if g != 1 or hd != -1:
+                check(L.vasr_set_block_groups(h, i, int(g), int(hd)))
         self.num_classes = int(num_classes)
 
     def load_state_dict(self, sd):

@@ -16,7 +16,7 @@ from . import _lib, stages
 from .core import (AcousticEncodedRepresentation, AudioSignal, DataLayerNM, DeviceType, LengthsType,
                    LogprobsType, MelSpectrogramType, NeuralType, NonTrainableNM, PredictionsType,
                    SpectrogramType, TrainableNM)
-from .engine import blocks_from_config, check_dense_layout, se_from_config
+from .engine import blocks_from_config, check_dense_layout, groups_from_config, se_from_config
 from .frontend_tables import frontend_description
 
 __all__ = ["AudioToMelSpectrogramPreprocessor", "JasperEncoder", "JasperDecoderForCTC", "GreedyCTCDecoder",
@@ -119,17 +119,21 @@ class _SqueezeExciteParams(nn.Module):
 
 class _JasperBlockParams(nn.Module):
     """ModuleList skeleton of one JasperBlock (parts/jasper.py:214-288): same indices, parameters only.  se: the
-    SqueezeExcite reduction ratio (0: none)."""
+    SqueezeExcite reduction ratio (0: none); groups: of the main-branch convs, each followed by a GroupShuffle slot when > 1;
+    heads: rows of the shared depthwise weights (-1: none)."""
 
-    def __init__(self, inplanes, planes, repeat, kernel, separable, residual, residual_panes=(), se=0):
+    def __init__(self, inplanes, planes, repeat, kernel, separable, residual, residual_panes=(), se=0, groups=1, heads=-1):
         super().__init__()
         layers, c = [], inplanes
         for r in range(repeat):
             if separable:
-                layers += [_MaskedConvParams(c, c, kernel, groups=c), _MaskedConvParams(c, planes, 1)]
+                dw = _MaskedConvParams(heads, heads, kernel, groups=heads) if heads != -1 else _MaskedConvParams(c, c, kernel, groups=c)
+                layers += [dw, _MaskedConvParams(c, planes, 1, groups=groups)]
             else:
-                layers += [_MaskedConvParams(c, planes, kernel)]
+                layers += [_MaskedConvParams(c, planes, kernel, groups=groups)]
             layers.append(nn.BatchNorm1d(planes, eps=1e-3, momentum=0.1))
+            if groups > 1:
+                layers.append(nn.Identity())                  # GroupShuffle slot (parts/jasper.py:396-399)
             if r != repeat - 1:
                 layers += [nn.Identity(), nn.Identity()]      # activation, dropout slots
             if se and not residual:
@@ -198,6 +202,7 @@ class JasperEncoder(_HipWeights, TrainableNM):
                                       "residual_mode='add', conv_mask=True, frame_splicing=1")
         self._blocks = blocks_from_config(jasper)
         self._se = se_from_config(jasper)
+        self._groups = groups_from_config(jasper)
         self._feat_in = feat_in * frame_splicing
         check_dense_layout(self._blocks, self._feat_in)
         for b in self._blocks:
@@ -205,14 +210,14 @@ class JasperEncoder(_HipWeights, TrainableNM):
                 raise ValueError("Only stride OR dilation may be greater than 1")   # parts/jasper.py:61-62
         layers, c = [], self._feat_in
         residual_panes = []     # ONE list shared by the dense blocks, copied by each (jasper.py:152-161, parts/jasper.py:264)
-        for b, se in zip(self._blocks, self._se):
+        for b, se, (groups, heads) in zip(self._blocks, self._se, self._groups):
             k = b["kernel"] + (1 if b["kernel"] % 2 == 0 else 0)
             dense_res = []
             if b["residual_dense"]:
                 residual_panes.append(c)
                 dense_res = residual_panes
             layers.append(_JasperBlockParams(c, b["filters"], b["repeat"], k, bool(b["separable"]), bool(b["residual"]),
-                                             list(dense_res), se))
+                                             list(dense_res), se, groups, heads))
             c = b["filters"]
         self.encoder = nn.Sequential(*layers)
         self._c_out = c
@@ -223,7 +228,7 @@ class JasperEncoder(_HipWeights, TrainableNM):
         if self._handle is None:
             if not torch.cuda.is_available():
                 raise _no_gpu()
-            h = _lib.Handle(feat_in=self._feat_in, blocks=self._blocks, se=self._se)
+            h = _lib.Handle(feat_in=self._feat_in, blocks=self._blocks, se=self._se, groups=self._groups)
             h.load_state_dict(self.state_dict())
             h.finalize()
             self._handle = h

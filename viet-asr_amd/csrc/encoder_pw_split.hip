@@ -36,6 +36,13 @@
 // 64-row chunk lies inside one tap: its rows are x[c0 .. c0 + 63] read at the tap's column offset
 // t * stride + tap * dil - pad, zero outside [0, lens[b]) (the input mask).  Staging, splits, MFMAs and epilogue are the
 // 1x1 kernel's; only the addresses differ.
+//
+// GRP (PwArgs::groups > 1): a grouped convolution (nn.Conv1d groups = G, parts/jasper.py:329-400) followed by the
+// reference's GroupShuffle (:135-150).  The weights are the [M][K] matrix of the grouped conv ([C_out][taps * C_in / G]),
+// packed as for a dense layer; K is the per-group reduction.  The workgroup's rows m0 .. m0 + BM - 1 lie inside one group
+// g = m0 / (M / G) (the tile's BM divides M / G), whose inputs are channels g * C_in / G on.  The epilogue applies the BN of
+// pre-shuffle row m = g * (M / G) + j and stores (and adds the residual) at the shuffled row j * G + g.  Per group the
+// reduction is the dense kernel's: k-steps in ascending order over the group's own K rows.
 #include <cstdlib>
 #include <cstring>
 
@@ -132,7 +139,7 @@ struct Geom {
   static_assert(PATCHES % NT == 0 && PPT >= 1, "staging patches must divide evenly over the threads");
 };
 
-template <int NW, int TM, int TN, bool MASK, bool RES, bool DUAL, int ARITH, bool CONV = false>
+template <int NW, int TM, int TN, bool MASK, bool RES, bool DUAL, int ARITH, bool CONV = false, bool GRP = false>
 __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int blocks_m, int tiles_t, int n_blocks) {
   using G = Geom<NW, TM, TN, ARITH>;
   constexpr int BM = G::BM, BN = G::BN, NT = G::NT, PPT = G::PPT, PL = G::PL, PLW = G::PLW;
@@ -165,8 +172,10 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
   float xs = 1.f, out_scale = 1.f;
 
   const int K1 = DUAL ? a.K1 : a.K;
-  const float* __restrict__ xb = CONV ? a.x + (int64_t)b * a.conv_cin * a.ldx
-                                     : a.x + (a.bsx ? (int64_t)b * a.bsx : (int64_t)b * K1 * a.ldx) + t0;
+  // GRP: the workgroup's group, its rows per group, and the groups of one utterance's input channels
+  const int ng = GRP ? a.groups : 1, mg = GRP ? a.M / a.groups : a.M, grp = GRP ? m0 / mg : 0;
+  const float* __restrict__ xb = CONV ? a.x + ((int64_t)b * ng + grp) * a.conv_cin * a.ldx
+                                     : a.x + (a.bsx ? (int64_t)b * a.bsx : (int64_t)b * K1 * ng * a.ldx) + (int64_t)grp * K1 * a.ldx + t0;
   const float* __restrict__ xb2 = DUAL ? a.x2 + (int64_t)b * (a.K - K1) * a.ldx2 + t0 : nullptr;
   // A fragments [M/32][K/16][PLW][64] uint4
   const int ksteps = a.K / 16;
@@ -444,6 +453,8 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
     ymax = (t < ylen && u > ymax) ? u : ymax;
   };
   const float relu_floor = (a.relu & 1) ? 0.f : -__builtin_inff();   // max(v, floor): ReLU or nothing, without a branch
+  // GRP: pre-shuffle row m = grp * mg + j is stored at row j * G + grp (GroupShuffle); otherwise at m
+  auto orow = [&](int m) { return GRP ? (m - grp * mg) * ng + grp : m; };
   const bool full = (t0 + BN <= a.store_cols) && (m0 + BM <= a.m_store);
   const bool vec = full && ((a.ldy | a.ldr) & 3) == 0 && ((reinterpret_cast<uintptr_t>(a.y) | reinterpret_cast<uintptr_t>(a.res)) & 15) == 0;
   if (vec) {
@@ -491,7 +502,7 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
         for (int k = 0; k < F4; ++k) {
           const int f = lane + 64 * k, row = f / (BN / 4), c4 = f % (BN / 4);
           pv[k] = *reinterpret_cast<const v4f*>(buf + row * BN + 4 * c4);
-          if (RES) rv[k] = *reinterpret_cast<const v4f*>(a.res + ((int64_t)b * a.M + mq + row) * a.ldr + t0 + 4 * c4);
+          if (RES) rv[k] = *reinterpret_cast<const v4f*>(a.res + ((int64_t)b * a.M + orow(mq + row)) * a.ldr + t0 + 4 * c4);
         }
 #pragma unroll
         for (int k = 0; k < F4; ++k) {
@@ -500,7 +511,7 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
           v4f v = pv[k];
           if (RES) v += rv[k];
           v = __builtin_elementwise_max(v, v4f{relu_floor, relu_floor, relu_floor, relu_floor});
-          v4f* dstp = reinterpret_cast<v4f*>(a.y + ((int64_t)b * a.m_store + m) * a.ldy + t);
+          v4f* dstp = reinterpret_cast<v4f*>(a.y + ((int64_t)b * a.m_store + orow(m)) * a.ldy + t);
           *dstp = v;   // (non-temporal stores for outputs beyond the Infinity Cache: measured, no gain)
 #pragma unroll
           for (int e = 0; e < 4; ++e) track(v[e], t + e);
@@ -524,10 +535,10 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
             float v = acc[i][j][4 * q + rr];
             if constexpr (ARITH == kF16x2) v *= out_scale;
             v = fmaf(v, sc[rr], sh[rr]);
-            if (RES) v += a.res[((int64_t)b * a.M + m) * a.ldr + t];
+            if (RES) v += a.res[((int64_t)b * a.M + orow(m)) * a.ldr + t];
             if (a.relu & 1) v = fmaxf(v, 0.f);
             if (full || (t < a.store_cols && m < a.m_store)) {
-              a.y[((int64_t)b * a.m_store + m) * a.ldy + t] = v;
+              a.y[((int64_t)b * a.m_store + orow(m)) * a.ldy + t] = v;
               if (a.amax_y.p) track(v, t);
             }
           }
@@ -538,7 +549,7 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
   if (a.amax_y.p) amax_publish(a.amax_y.p, a.amax_y.stride, b, (mb * tiles_t + nt % tiles_t) * NW + wave, ymax, lane);
 }
 
-template <int NW, int TM, int TN, bool MASK, bool RES, bool DUAL, int ARITH, bool CONV = false>
+template <int NW, int TM, int TN, bool MASK, bool RES, bool DUAL, int ARITH, bool CONV = false, bool GRP = false>
 int launch_k(const PwArgs& a, hipStream_t st, int* amax_n) {
   using G = Geom<NW, TM, TN, ARITH>;
   const int blocks_m = a.M / G::BM;
@@ -549,7 +560,8 @@ int launch_k(const PwArgs& a, hipStream_t st, int* amax_n) {
     if (n > a.amax_y.stride) return (int)hipErrorInvalidValue;
     if (amax_n) *amax_n = n;
   }
-  auto kern = pw_gemm_split_kernel<NW, TM, TN, MASK, RES, DUAL, ARITH, CONV>;
+  if (GRP && (a.groups < 2 || a.M % a.groups || (a.M / a.groups) % G::BM || a.m_store != a.M)) return (int)hipErrorInvalidValue;
+  auto kern = pw_gemm_split_kernel<NW, TM, TN, MASK, RES, DUAL, ARITH, CONV, GRP>;
   static std::atomic<uint64_t> lds_opted{0};   // per device (dyn_lds_opt_in)
   const hipError_t attr = dyn_lds_opt_in(reinterpret_cast<const void*>(kern), (int)G::LDS, lds_opted);
   if (attr != hipSuccess) return (int)attr;
@@ -560,6 +572,17 @@ int launch_k(const PwArgs& a, hipStream_t st, int* amax_n) {
 template <int NW, int TM, int TN, int ARITH>
 int launch_l(const PwArgs& a, hipStream_t st, int* amax_n) {
   const bool mask = a.lens != nullptr, res = a.res != nullptr, dual = a.x2 != nullptr;
+  if (a.groups > 1) {   // grouped + shuffled: never dual
+    if (dual) return (int)hipErrorInvalidValue;
+    if (a.conv_cin) {
+      if (res) return launch_k<NW, TM, TN, true, true, false, ARITH, true, true>(a, st, amax_n);
+      return launch_k<NW, TM, TN, true, false, false, ARITH, true, true>(a, st, amax_n);
+    }
+    if (mask && res) return launch_k<NW, TM, TN, true, true, false, ARITH, false, true>(a, st, amax_n);
+    if (mask) return launch_k<NW, TM, TN, true, false, false, ARITH, false, true>(a, st, amax_n);
+    if (res) return launch_k<NW, TM, TN, false, true, false, ARITH, false, true>(a, st, amax_n);
+    return launch_k<NW, TM, TN, false, false, false, ARITH, false, true>(a, st, amax_n);
+  }
   if (a.conv_cin) {   // K-tap convolution: always masked (lens = the input's), never dual
     if (res) return launch_k<NW, TM, TN, true, true, false, ARITH, true>(a, st, amax_n);
     return launch_k<NW, TM, TN, true, false, false, ARITH, true>(a, st, amax_n);
@@ -596,6 +619,13 @@ bool pointwise_split_supported(int M, int K, int K1) {
 // a chunk of the implicit-GEMM convolution must lie inside one tap
 bool conv_split_supported(int M, int cin) { return M % 64 == 0 && cin % BKC == 0; }
 
+// the grouped form: every group's output rows and its input channels (per tap) a multiple of 64, and cout a multiple of 128 --
+// the packs pad M to that, and a padded M would no longer split into groups (launch_k refuses it)
+bool grouped_split_supported(int cout, int cin, int groups) {
+  return groups > 1 && cout % 128 == 0 && cout % groups == 0 && cin % groups == 0 && (cout / groups) % 64 == 0 &&
+         (cin / groups) % BKC == 0;
+}
+
 // arith: 0 = 3 x bf16 (six products), 1 = 2 x bf16 (three products, reduced), 2 = 2 x fp16 scaled (three products; needs
 // a.amax_x (and a.amax_x2 for a dual source), a.w_inv_scale and the fp16 weight pack).  Returns 0 or a hipError_t.
 // the smallest tile (64 x 32 on two wavefronts) uses the most slots: (M / 64) * (ld / 32) * 2
@@ -609,13 +639,16 @@ int launch_pointwise_split(const PwArgs& args, int arith, hipStream_t st, int* a
   const int64_t cols = a.conv_cin ? a.conv_cols : a.ldx;   // output columns tiled
   auto blocks = [&](int bm, int bn) { return (int64_t)(a.M / bm) * ((cols + bn - 1) / bn) * a.batch; };
   const int rows[6] = {0, 512, 256, 128, 64, 256};
+  // a grouped layer's tile lies inside one group: the tile rows must divide the rows per group (the workgroup count is the
+  // layer's, M / bm, as for a dense layer of M rows)
+  const int mg = a.groups > 1 ? a.M / a.groups : a.M;
   int tile = 4;
-  if (a.M % 512 == 0 && blocks(512, 128) >= 192) tile = 1;
-  else if (a.M % 256 == 0 && blocks(256, 128) >= 192) tile = 2;
-  else if (a.M % 128 == 0 && blocks(128, 64) >= 192) tile = 3;
+  if (mg % 512 == 0 && blocks(512, 128) >= 192) tile = 1;
+  else if (mg % 256 == 0 && blocks(256, 128) >= 192) tile = 2;
+  else if (mg % 128 == 0 && blocks(128, 64) >= 192) tile = 3;
   // 256-channel layers: 256 x 64 tiles put two or three workgroups on a CU (49 KB of LDS each), which hides more of
   // one workgroup's prologue / epilogue behind another's main loop: 30.0 -> 28.7 us at K = 256, 49.1 -> 48.1 at K = 512
-  if (tile == 2 && a.M == 256 && blocks(256, 64) >= 384) tile = 5;
+  if (tile == 2 && mg == 256 && blocks(256, 64) >= 384) tile = 5;
   // (for the 512-channel layers both 256 x 64 and 512 x 64 measured slower than 512 x 128: 88-91 / 94-97 vs 86 us)
   // ... when the 512 x 128 workgroups fill whole rounds of the chip (one per CU).  T' = 516 (a 10.3 s clip) is five
   // 128-column tiles per utterance: 320 workgroups = two rounds, the second a quarter full.  256 x 64 tiles (two per CU,
@@ -632,11 +665,11 @@ int launch_pointwise_split(const PwArgs& args, int arith, hipStream_t st, int* a
     const int64_t n1 = blocks(512, 128), rounds = (n1 + cus - 1) / cus;
     if ((double)n1 < 0.85 * (double)(rounds * cus)) tile = 5;
   }
-  if (force >= 1 && force <= 5 && a.M % rows[force] == 0) tile = force;
+  if (force >= 1 && force <= 5 && mg % rows[force] == 0) tile = force;
   // Small batches (the 64 x 32 tile's territory: <= 5 utterances of 10 s at 512 channels): the whole K range in ONE trip to
   // memory instead of K / 64 dependent chunk steps -- encoder_pw_lat.hip, same bits.  (Devtools: VASR_PW_LAT=0 keeps the chunked
   // kernel.)
-  if (arith == kF16x2 && !force && dev_switches().pw_lat > 0 && tile == 4 && !a.conv_cin && !a.bsx && pointwise_latency_supported(a.M, a.K, a.x2 ? a.K1 : 0)) {
+  if (arith == kF16x2 && !force && dev_switches().pw_lat > 0 && tile == 4 && !a.conv_cin && !a.bsx && a.groups <= 1 && pointwise_latency_supported(a.M, a.K, a.x2 ? a.K1 : 0)) {
     const int e = launch_pointwise_latency(a, st, amax_n);
     if (e >= 0) return e;
   }

@@ -61,6 +61,8 @@ struct ConvLayer {
   float* d_shift = nullptr;  // [m_pad]
   int step = -1;             // index in the MaskedConv1d length chain
   int conv_cin = 0;          // non-separable K-tap conv (implicit GEMM over k = tap * conv_cin + c; cin = kernel * conv_cin)
+  int groups = 1;            // > 1: grouped conv + channel shuffle on the grouped split GEMM (PwArgs::groups); cin, conv_cin
+                             // per group, split packs only (no fp32 pack: the fp32 mode runs SubBlock::pw_bd)
 };
 
 // squeeze-and-excitation (parts/jasper.py:152-168): fc.0 [hidden][c], fc.2 [c][hidden] (encoder_se.hip)
@@ -73,6 +75,9 @@ struct SeLayer {
 struct SubBlock {
   bool separable = true;
   ConvLayer dw, pw;
+  // pw grouped (pw.groups > 1): the same layer as a dense block-diagonal GEMM whose rows and BN are permuted by the channel
+  // shuffle -- what the fp32 mode runs (encoder_pw.hip has no grouped form)
+  ConvLayer pw_bd;
   SeLayer se;               // se and not residual: after this sub-layer (d_w1 == nullptr: none)
 };
 
@@ -97,6 +102,9 @@ struct Block {
   // residual then always takes the separate-GEMM form, and a dense one runs one GEMM per pane (res_panes[p], channels
   // res_pane_off[p] .. + res_panes[p].cin of the pane buffer) whose SE-scaled results are summed into R
   int se_r = 0;
+  // groups / heads (vasr_set_block_groups): every main-branch conv grouped (groups > 1) and followed by a GroupShuffle; the
+  // depthwise weights of a separable block shared by channel c % heads (heads > 0)
+  int groups = 1, heads = 0;
   std::vector<SeLayer> res_se;
   std::vector<ConvLayer> res_panes;
   std::vector<int> res_pane_off;
@@ -184,6 +192,7 @@ const vasr::DevSwitches& vasr::dev_switches() {
     s.fused_tile = num("VASR_FUSED_TILE", 0, {0, 64, 128});
     s.fused_residual = num("VASR_NO_FUSED_RESIDUAL", 0, {0, 1}) == 0;
     s.beam_group = num("VASR_BEAM_GROUP", -1, {-1, 0, 1, 4});
+    s.no_grouped = num("VASR_NO_GROUPED", 0, {0, 1}) != 0;
     return s;
   }();
   return sw;
@@ -233,7 +242,8 @@ int need(const vasr_handle* h, const std::string& key, size_t numel, const HostT
 }
 
 // eval-mode BatchNorm1d(eps=1e-3) -> y = x * scale + shift  (parts/jasper.py:392)
-int fold_bn(vasr_handle* h, const std::string& prefix, int c, int c_pad, ConvLayer* L) {
+// perm (optional): channel i's affine goes to row perm[i] (a grouped layer's block-diagonal form: the channel shuffle)
+int fold_bn(vasr_handle* h, const std::string& prefix, int c, int c_pad, ConvLayer* L, const std::vector<int>* perm = nullptr) {
   const HostTensor *g, *b, *m, *v;
   int rc;
   if ((rc = need(h, prefix + ".weight", c, &g))) return rc;
@@ -245,8 +255,9 @@ int fold_bn(vasr_handle* h, const std::string& prefix, int c, int c_pad, ConvLay
     // same association as ATen's CPU eval path: alpha = w * invstd, beta = b - mean * alpha (fp32)
     const float invstd = 1.0f / std::sqrt(v->data[i] + 1e-3f);
     const float alpha = g->data[i] * invstd;
-    sc[i] = alpha;
-    sh[i] = b->data[i] - m->data[i] * alpha;
+    const int o = perm ? (*perm)[i] : i;
+    sc[o] = alpha;
+    sh[o] = b->data[i] - m->data[i] * alpha;
   }
   if ((rc = upload(h, sc, &L->d_scale))) return rc;
   return upload(h, sh, &L->d_shift);
@@ -306,11 +317,11 @@ int pack_sum_1x1(vasr_handle* h, const std::vector<SumSrc>& src, int cout, int k
   return upload(h, sh, &L->d_shift);
 }
 
-// [cout][cin][kernel] -> the implicit GEMM's [cout][kernel * cin] (k = tap * cin + c) -> the three fragment packs
-int pack_conv(vasr_handle* h, const std::string& key, int cout, int cin, int kernel, ConvLayer* L) {
-  const HostTensor* w;
+// [cout][cin][kernel] -> the implicit GEMM's [cout][kernel * cin] (k = tap * cin + c) -> the three fragment packs (fp32: no
+// fp32 pack)
+int pack_conv_data(vasr_handle* h, const float* w, const std::string& key, int cout, int cin, int kernel, ConvLayer* L,
+                   bool fp32 = true, bool split = true) {
   int rc;
-  if ((rc = need(h, key, (size_t)cout * cin * kernel, &w))) return rc;
   L->m_pad = (int)align_up(cout, 128);
   if (!conv_split_supported(L->m_pad, cin))
     return fail(VASR_ERR_UNSUPPORTED, "%s: in_channels %d of a %d-tap conv is not a multiple of 64", key.c_str(), cin, kernel);
@@ -319,44 +330,121 @@ int pack_conv(vasr_handle* h, const std::string& key, int cout, int cin, int ker
   L->cout = cout;
   L->conv_cin = cin;
   std::vector<float> g((size_t)cout * K);
-  pack_conv_gemm_weights(w->data.data(), cout, cin, kernel, g.data());
+  pack_conv_gemm_weights(w, cout, cin, kernel, g.data());
+  if (split) {
+    std::vector<unsigned short> w3((size_t)K * L->m_pad * 3);
+    pack_pointwise_weights_bf16x3(g.data(), cout, K, L->m_pad, w3.data());
+    if ((rc = upload(h, w3, &L->d_w3))) return rc;
+    std::vector<unsigned short> w16((size_t)K * L->m_pad * 2);
+    L->w16_inv = pack_pointwise_weights_f16x2(g.data(), cout, K, L->m_pad, w16.data());
+    if ((rc = upload(h, w16, &L->d_w16))) return rc;
+  }
+  if (!fp32) return 0;
   std::vector<float> wt((size_t)K * L->m_pad, 0.f);
   pack_pointwise_weights(g.data(), cout, K, L->m_pad, wt.data());
-  std::vector<unsigned short> w3((size_t)K * L->m_pad * 3);
-  pack_pointwise_weights_bf16x3(g.data(), cout, K, L->m_pad, w3.data());
-  if ((rc = upload(h, w3, &L->d_w3))) return rc;
-  std::vector<unsigned short> w16((size_t)K * L->m_pad * 2);
-  L->w16_inv = pack_pointwise_weights_f16x2(g.data(), cout, K, L->m_pad, w16.data());
-  if ((rc = upload(h, w16, &L->d_w16))) return rc;
   return upload(h, wt, &L->d_w);
 }
 
-// [cout][cin][1] -> MFMA A-fragment order
-int pack_pointwise(vasr_handle* h, const std::string& key, int cout, int cin, ConvLayer* L) {
+int pack_conv(vasr_handle* h, const std::string& key, int cout, int cin, int kernel, ConvLayer* L) {
   const HostTensor* w;
   int rc;
-  if ((rc = need(h, key, (size_t)cout * cin, &w))) return rc;
+  if ((rc = need(h, key, (size_t)cout * cin * kernel, &w))) return rc;
+  return pack_conv_data(h, w->data.data(), key, cout, cin, kernel, L);
+}
+
+// [cout][cin][1] -> MFMA A-fragment order (fp32: no fp32 pack)
+int pack_pointwise_data(vasr_handle* h, const float* w, const std::string& key, int cout, int cin, ConvLayer* L,
+                        bool fp32 = true, bool split = true) {
+  int rc;
   // (a K depth of 32 would select the 128 x 256 tile of the fp32 kernel, whose last time tile assumes a 256-frame pitch)
   if (cin % 64) return fail(VASR_ERR_UNSUPPORTED, "%s: in_channels %d is not a multiple of 64", key.c_str(), cin);
   L->cin = cin;
   L->cout = cout;
   L->m_pad = (int)align_up(cout, 128);
-  std::vector<float> wt((size_t)cin * L->m_pad, 0.f);
-  pack_pointwise_weights(w->data.data(), cout, cin, L->m_pad, wt.data());
-  if (pointwise_split_supported(L->m_pad, cin, 0)) {
+  if (split && pointwise_split_supported(L->m_pad, cin, 0)) {
     std::vector<unsigned short> w3((size_t)cin * L->m_pad * 3);
-    pack_pointwise_weights_bf16x3(w->data.data(), cout, cin, L->m_pad, w3.data());
+    pack_pointwise_weights_bf16x3(w, cout, cin, L->m_pad, w3.data());
     if ((rc = upload(h, w3, &L->d_w3))) return rc;
     std::vector<unsigned short> w16((size_t)cin * L->m_pad * 2);
-    L->w16_inv = pack_pointwise_weights_f16x2(w->data.data(), cout, cin, L->m_pad, w16.data());
+    L->w16_inv = pack_pointwise_weights_f16x2(w, cout, cin, L->m_pad, w16.data());
     if ((rc = upload(h, w16, &L->d_w16))) return rc;
   }
+  if (!fp32) return 0;
+  std::vector<float> wt((size_t)cin * L->m_pad, 0.f);
+  pack_pointwise_weights(w, cout, cin, L->m_pad, wt.data());
   return upload(h, wt, &L->d_w);
+}
+
+int pack_pointwise(vasr_handle* h, const std::string& key, int cout, int cin, ConvLayer* L) {
+  const HostTensor* w;
+  int rc;
+  if ((rc = need(h, key, (size_t)cout * cin, &w))) return rc;
+  return pack_pointwise_data(h, w->data.data(), key, cout, cin, L);
+}
+
+// A grouped main-branch conv, weight [cout][cin / groups][kernel] under `key`, BN under `bn`, followed by the reference's
+// GroupShuffle (parts/jasper.py:135-150, :396-399: output channel j * G + g = pre-shuffle channel g * (cout / G) + j).
+//   BD: the block-diagonal dense form -- weight [cout][cin][kernel], zero outside each group's block, its rows and its folded
+//       BN permuted by the shuffle, so that the dense kernels store the shuffled order directly (beside a grouped L: the fp32
+//       pack only, for the fp32 mode);
+//   L:  the grouped split GEMM's packs (L->groups = G; the [cout][kernel * cin / G] matrix, BN in pre-shuffle order) when
+//       grouped_split_supported and not VASR_NO_GROUPED, else a copy of BD.
+// conv: the implicit-GEMM form (a K-tap or strided conv), else a 1x1.
+int pack_grouped(vasr_handle* h, const std::string& key, const std::string& bn, int cout, int cin, int kernel, int G, bool conv,
+                 ConvLayer* L, ConvLayer* BD) {
+  const HostTensor* w;
+  int rc;
+  const int cg = cin / G, mg = cout / G;
+  if ((rc = need(h, key, (size_t)cout * cg * kernel, &w))) return rc;
+  std::vector<float> dense((size_t)cout * cin * kernel, 0.f);
+  std::vector<int> perm(cout);
+  for (int p = 0; p < cout; ++p) {
+    const int g = p / mg, o = (p % mg) * G + g;
+    perm[p] = o;
+    for (int c = 0; c < cg; ++c)
+      for (int t = 0; t < kernel; ++t)
+        dense[((size_t)o * cin + g * cg + c) * kernel + t] = w->data[((size_t)p * cg + c) * kernel + t];
+  }
+  // grouped: BD only serves the fp32 mode -- its fp32 pack alone; else BD is the product form, every pack
+  const bool grouped = !h->sw.no_grouped && grouped_split_supported(cout, cin, G);
+  if ((rc = conv ? pack_conv_data(h, dense.data(), key, cout, cin, kernel, BD, true, !grouped)
+                 : pack_pointwise_data(h, dense.data(), key, cout, cin, BD, true, !grouped)) ||
+      (rc = fold_bn(h, bn, cout, BD->m_pad, BD, &perm)))
+    return rc;
+  if (!grouped) {
+    *L = *BD;
+    *BD = ConvLayer{};
+    return 0;
+  }
+  if ((rc = conv ? pack_conv_data(h, w->data.data(), key, cout, cg, kernel, L, false)
+                 : pack_pointwise_data(h, w->data.data(), key, cout, cg, L, false)) ||
+      (rc = fold_bn(h, bn, cout, L->m_pad, L)))
+    return rc;
+  L->groups = G;
+  return 0;
 }
 
 // State-dict prefixes of block i's SqueezeExcite modules in the reference's construction order (parts/jasper.py:214-288):
 // with residual, entry 2 of every residual pane's list (conv, BN, SE); without, the entry after each sub-layer's conv + BN
 // (+ activation and dropout, except after the last one) -- which shifts the mconv indices of everything behind it.
+// ModuleList indices of block B's sub-layers (encoder.{i}.mconv.{j}) in the reference's construction order
+// (parts/jasper.py:214-288, :329-400): per sub-layer its conv -- a separable one's depthwise conv, then the 1x1 at conv + 1 --,
+// the BN, a GroupShuffle when groups > 1, activation + dropout except after the last sub-layer, and a SqueezeExcite when the
+// block has SE and no residual.  The one place this arithmetic lives: weight checks, SE prefixes and build_encoder read it.
+struct SubKeys { int conv, bn, se; };   // se = -1: none
+std::vector<SubKeys> mconv_layout(const Block& B) {
+  std::vector<SubKeys> out;
+  int j = 0;
+  for (int r = 0; r < B.d.repeat; ++r) {
+    SubKeys k{j, j + (B.d.separable ? 2 : 1), -1};
+    j = k.bn + 1 + (B.groups > 1 ? 1 : 0);
+    if (r != B.d.repeat - 1) j += 2;
+    if (B.se_r && !B.d.residual) k.se = j++;
+    out.push_back(k);
+  }
+  return out;
+}
+
 std::vector<std::string> se_prefixes(const vasr_handle* h, size_t i) {
   const Block& B = h->blocks[i];
   std::vector<std::string> out;
@@ -370,13 +458,9 @@ std::vector<std::string> se_prefixes(const vasr_handle* h, size_t i) {
     }
     return out;
   }
-  int j = 0;
-  for (int r = 0; r < B.d.repeat; ++r) {
-    j += B.d.separable ? 3 : 2;
-    if (r != B.d.repeat - 1) j += 2;
-    snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, j);
+  for (const SubKeys& k : mconv_layout(B)) {
+    snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, k.se);
     out.push_back(key);
-    j += 1;
   }
   return out;
 }
@@ -397,6 +481,60 @@ int check_se(vasr_handle* h) {
     for (const std::string& pre : se_prefixes(h, i))
       if ((rc = need(h, pre + ".fc.0.weight", (size_t)hid * c, &t)) || (rc = need(h, pre + ".fc.2.weight", (size_t)c * hid, &t)))
         return rc;
+  }
+  return 0;
+}
+
+// a weight present with exactly this shape (missing: VASR_ERR_STATE, any other shape: VASR_ERR_INVALID)
+int need_shape(const vasr_handle* h, const std::string& key, std::initializer_list<int64_t> shape, const HostTensor** out) {
+  const HostTensor* t = find(h, key);
+  if (!t) return fail(VASR_ERR_STATE, "missing weight '%s'", key.c_str());
+  if (!std::equal(t->shape.begin(), t->shape.end(), shape.begin(), shape.end())) {
+    std::string want, got;
+    for (int64_t d : shape) want += (want.empty() ? "" : ", ") + std::to_string(d);
+    for (int64_t d : t->shape) got += (got.empty() ? "" : ", ") + std::to_string(d);
+    return fail(VASR_ERR_INVALID, "weight '%s' has shape [%s], expected [%s]", key.c_str(), got.c_str(), want.c_str());
+  }
+  *out = t;
+  return 0;
+}
+
+// vasr_finalize's check of groups / heads (before anything touches the device): nn.Conv1d's divisibility (C_in and C_out by
+// groups), heads dividing the channels of a separable block (the reference's view(-1, heads, T); on a block that is not
+// separable the reference never hands heads to a conv, and neither does this library), the encoder's width rule for grouped
+// blocks (filters a multiple of 128, as build_encoder requires of every block), and every main-branch conv weight present
+// in its grouped / shared shape under the key the shuffle entries shift it to
+int check_groups(vasr_handle* h) {
+  int cin = h->feat_in;
+  for (size_t i = 0; i < h->blocks.size(); ++i) {
+    const Block& B = h->blocks[i];
+    const vasr_block_desc& d = B.d;
+    const int G = B.groups, H = d.separable ? B.heads : 0, k = d.kernel % 2 ? d.kernel : d.kernel + 1;
+    if (G > 1 || H > 0) {
+      if (G > 1 && d.filters % 128)
+        return fail(VASR_ERR_UNSUPPORTED, "block %zu: filters %d is not a multiple of 128", i, d.filters);
+      const std::vector<SubKeys> lay = mconv_layout(B);
+      int c = cin;
+      char key[160];
+      const HostTensor* t;
+      int rc;
+      for (int r = 0; r < d.repeat; ++r) {
+        if (c % G || d.filters % G)
+          return fail(VASR_ERR_INVALID, "block %zu: groups %d does not divide in_channels %d and out_channels %d", i, G, c, d.filters);
+        if (H > 0 && c % H)
+          return fail(VASR_ERR_INVALID, "block %zu: heads %d does not divide the %d channels", i, H, c);
+        snprintf(key, sizeof key, "encoder.%zu.mconv.%d.conv.weight", i, lay[r].conv);
+        if (d.separable) {
+          if ((rc = need_shape(h, key, {H > 0 ? H : c, 1, k}, &t))) return rc;
+          snprintf(key, sizeof key, "encoder.%zu.mconv.%d.conv.weight", i, lay[r].conv + 1);
+          if ((rc = need_shape(h, key, {d.filters, c / G, 1}, &t))) return rc;
+        } else if ((rc = need_shape(h, key, {d.filters, c / G, k}, &t))) {
+          return rc;
+        }
+        c = d.filters;
+      }
+    }
+    cin = d.filters;
   }
   return 0;
 }
@@ -464,60 +602,83 @@ int build_encoder(vasr_handle* h) {
     if ((rc = same_pad(k, d.stride, d.dilation, &pad))) return rc;
     B.first_step = step;
     B.subs.resize(d.repeat);
-    int c = cin, j = 0;
+    int c = cin;
     char key[160];
+    const std::vector<SubKeys> lay = mconv_layout(B);
     for (int r = 0; r < d.repeat; ++r) {
       SubBlock& S = B.subs[r];
+      const int j = lay[r].conv, jbn = lay[r].bn;
       S.separable = d.separable != 0;
       if (S.separable) {
         const HostTensor* w;
         snprintf(key, sizeof key, "encoder.%zu.mconv.%d.conv.weight", i, j);
-        if ((rc = need(h, key, (size_t)c * k, &w))) return rc;
+        if ((rc = need(h, key, (size_t)(B.heads > 0 ? B.heads : c) * k, &w))) return rc;
+        // heads: the [H][1][K] weight shared by channel c % H (MaskedConv1d's view(-1, heads, T)), expanded to [C][K] here so
+        // that every depthwise kernel, tap table and the fused kernel's taps see per-channel weights
+        std::vector<float> dw_heads;
+        if (B.heads > 0) {
+          dw_heads.resize((size_t)c * k);
+          for (int ch = 0; ch < c; ++ch)
+            std::copy_n(&w->data[(size_t)(ch % B.heads) * k], k, &dw_heads[(size_t)ch * k]);
+        }
+        const std::vector<float>& dwv = B.heads > 0 ? dw_heads : w->data;
         S.dw.cin = S.dw.cout = c;
         S.dw.kernel = k; S.dw.stride = d.stride; S.dw.dilation = d.dilation; S.dw.pad = pad;
         S.dw.step = step++;
         h->steps.push_back(LenStep{k, d.stride, d.dilation, pad});
-        if ((rc = upload(h, w->data, &S.dw.d_w))) return rc;
+        if ((rc = upload(h, dwv, &S.dw.d_w))) return rc;
         S.dw.tap_tsz = d.stride == 1 ? depthwise_mfma_table_size(k, d.dilation) : 0;
         if (S.dw.tap_tsz) {
           std::vector<unsigned int> tab((size_t)c * S.dw.tap_tsz);
           std::vector<float> inv(c);
           for (int ch = 0; ch < c; ++ch)
-            inv[ch] = pack_depthwise_taps_f16x2(&w->data[(size_t)ch * k], k, d.dilation, S.dw.tap_tsz, &tab[(size_t)ch * S.dw.tap_tsz]);
+            inv[ch] = pack_depthwise_taps_f16x2(&dwv[(size_t)ch * k], k, d.dilation, S.dw.tap_tsz, &tab[(size_t)ch * S.dw.tap_tsz]);
           if ((rc = upload(h, tab, &S.dw.d_taps)) || (rc = upload(h, inv, &S.dw.d_tap_inv))) return rc;
         }
         if (fused_dwpw_supported(c, d.filters, k, d.stride, d.dilation)) {
           std::vector<float> ft((size_t)(c / 2) * fused_dwpw_taps_per_pair(k) * 2);
-          S.dw.f_l1 = pack_fused_taps(w->data.data(), c, k, ft.data());
+          S.dw.f_l1 = pack_fused_taps(dwv.data(), c, k, ft.data());
           if ((rc = upload(h, ft, &S.dw.d_ftaps))) return rc;
         }
         snprintf(key, sizeof key, "encoder.%zu.mconv.%d.conv.weight", i, j + 1);
-        if ((rc = pack_pointwise(h, key, d.filters, c, &S.pw))) return rc;
-        S.pw.step = step++;
-        h->steps.push_back(LenStep{1, 1, 1, 0});
-        snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, j + 2);
-        if ((rc = fold_bn(h, key, d.filters, S.pw.m_pad, &S.pw))) return rc;
-        j += 3;
-      } else {
-        snprintf(key, sizeof key, "encoder.%zu.mconv.%d.conv.weight", i, j);
-        if (k == 1 && d.stride == 1) {
-          if ((rc = pack_pointwise(h, key, d.filters, c, &S.pw))) return rc;
-          h->steps.push_back(LenStep{1, 1, 1, 0});
-        } else {   // K-tap / strided: implicit GEMM (encoder_pw_split.hip, encoder_pw.hip CONV)
-          if ((rc = pack_conv(h, key, d.filters, c, k, &S.pw))) return rc;
-          S.pw.kernel = k; S.pw.stride = d.stride; S.pw.dilation = d.dilation; S.pw.pad = pad;
-          h->steps.push_back(LenStep{k, d.stride, d.dilation, pad});
+        if (B.groups > 1) {
+          char bn[160];
+          snprintf(bn, sizeof bn, "encoder.%zu.mconv.%d", i, jbn);
+          if ((rc = pack_grouped(h, key, bn, d.filters, c, 1, B.groups, false, &S.pw, &S.pw_bd))) return rc;
+        } else if ((rc = pack_pointwise(h, key, d.filters, c, &S.pw))) {
+          return rc;
         }
         S.pw.step = step++;
-        snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, j + 1);
-        if ((rc = fold_bn(h, key, d.filters, S.pw.m_pad, &S.pw))) return rc;
-        j += 2;
+        h->steps.push_back(LenStep{1, 1, 1, 0});
+        snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, jbn);
+        if (B.groups == 1 && (rc = fold_bn(h, key, d.filters, S.pw.m_pad, &S.pw))) return rc;
+      } else {
+        snprintf(key, sizeof key, "encoder.%zu.mconv.%d.conv.weight", i, j);
+        const bool conv = !(k == 1 && d.stride == 1);   // K-tap / strided: implicit GEMM (encoder_pw_split.hip, encoder_pw.hip CONV)
+        if (B.groups > 1) {
+          char bn[160];
+          snprintf(bn, sizeof bn, "encoder.%zu.mconv.%d", i, jbn);
+          if ((rc = pack_grouped(h, key, bn, d.filters, c, k, B.groups, conv, &S.pw, &S.pw_bd))) return rc;
+        } else if ((rc = conv ? pack_conv(h, key, d.filters, c, k, &S.pw) : pack_pointwise(h, key, d.filters, c, &S.pw))) {
+          return rc;
+        }
+        if (conv) {
+          S.pw.kernel = k; S.pw.stride = d.stride; S.pw.dilation = d.dilation; S.pw.pad = pad;
+          h->steps.push_back(LenStep{k, d.stride, d.dilation, pad});
+        } else {
+          h->steps.push_back(LenStep{1, 1, 1, 0});
+        }
+        S.pw.step = step++;
+        snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, jbn);
+        if (B.groups == 1 && (rc = fold_bn(h, key, d.filters, S.pw.m_pad, &S.pw))) return rc;
       }
-      if (r != d.repeat - 1) j += 2;  // activation + dropout entries of the ModuleList
-      if (B.se_r && !d.residual) {      // SqueezeExcite entry (parts/jasper.py:233-234, :250-251)
-        snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, j);
+      if (S.pw_bd.d_w) {          // the block-diagonal form runs the same geometry
+        S.pw_bd.kernel = S.pw.kernel; S.pw_bd.stride = S.pw.stride; S.pw_bd.dilation = S.pw.dilation; S.pw_bd.pad = S.pw.pad;
+        S.pw_bd.step = S.pw.step;
+      }
+      if (lay[r].se >= 0) {      // SqueezeExcite entry (parts/jasper.py:233-234, :250-251)
+        snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, lay[r].se);
         if ((rc = load_se(h, key, d.filters, B.se_r, &S.se))) return rc;
-        j += 1;
       }
       c = d.filters;
     }
@@ -560,12 +721,12 @@ int build_encoder(vasr_handle* h) {
       const SubBlock& last = B.subs.back();
       const int k1 = last.pw.cin, k2 = cin;
       const int chunk = d.filters % 512 == 0 ? 128 : (d.filters % 256 == 0 ? 64 : 32);
+      // (grouped blocks: the main branch's grouped reduction and the residual's dense one share no K)
       if (d.stride == 1 && k1 % chunk == 0 && k2 % chunk == 0 && h->sw.fused_residual && !last.pw.conv_cin && !B.res_pane0 &&
-          !B.se_r) {
+          !B.se_r && B.groups == 1) {
         char w1[160], bn1[160], w2[160], bn2[160];
-        const int jl = j - (last.separable ? 3 : 2);
-        snprintf(w1, sizeof w1, "encoder.%zu.mconv.%d.conv.weight", i, jl + (last.separable ? 1 : 0));
-        snprintf(bn1, sizeof bn1, "encoder.%zu.mconv.%d", i, jl + (last.separable ? 2 : 1));
+        snprintf(w1, sizeof w1, "encoder.%zu.mconv.%d.conv.weight", i, lay.back().conv + (last.separable ? 1 : 0));
+        snprintf(bn1, sizeof bn1, "encoder.%zu.mconv.%d", i, lay.back().bn);
         snprintf(w2, sizeof w2, "encoder.%zu.res.0.0.conv.weight", i);
         snprintf(bn2, sizeof bn2, "encoder.%zu.res.0.1", i);
         if ((rc = pack_sum_1x1(h, {SumSrc{w1, bn1, k1}, SumSrc{w2, bn2, k2}}, d.filters, k1, &B.fused))) return rc;
@@ -920,7 +1081,7 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
       // round differently -- that mode promises bit-identical rows whatever the batch)
       // (a sub-layer whose output feeds an SE: the fused kernel does not produce its row sums)
       if (fused_on && !h->row_independent && S.separable && S.dw.d_ftaps && h->gemm_mode == 3 && want_amax && cur_amax.p && WF.d_w16 &&
-          !S.se.d_w1 &&
+          !S.se.d_w1 && B.groups == 1 &&   // (no grouped form of the fused kernel)
           !(last_sub && B.has_res && !B.fused_res) &&
           // a folded residual must come from a 256-channel block input (K = 256 + 256): the kernel's second K range is 4 chunks
           (fuse_res ? (blk_amax.p && blk_ld == cur_ld && WF.cin == 2 * S.dw.cin && B.fused_k1 == S.dw.cin) : WF.cin == S.dw.cin) &&
@@ -975,10 +1136,11 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
         g_lens = lens(S.pw.step);  // block input is unmasked: predicate inside the GEMM
         if (S.pw.conv_cin) {
           g_T = conv_out_frames(cur_T, S.pw);
-          // fp16 split: an encoder input no kernel published maxima of (the mel features) gets them here
+          // fp16 split: an encoder input no kernel published maxima of (the mel features) gets them here -- over all of its
+          // channels (a grouped conv's conv_cin is one group's)
           if (want_amax && !gx_amax.p) {
             gx_amax = free_tab(AmaxTab{});
-            launch_amax(cur, cur_ld, S.pw.conv_cin, (int)cur_T, g_lens, batch, &gx_amax, st);
+            launch_amax(cur, cur_ld, S.pw.conv_cin * S.pw.groups, (int)cur_T, g_lens, batch, &gx_amax, st);
           }
         }
       }
@@ -988,8 +1150,10 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
       int64_t dst_ld = S.pw.conv_cin ? pad_frames(g_T) : gx_ld;
       if (last_block && last_sub) { dst = out; dst_ld = out_ld; }
       const bool fuse = last_sub && B.fused_res;
-      const ConvLayer& W = fuse ? B.fused : S.pw;
+      // a grouped layer in the fp32 mode: its block-diagonal form (encoder_pw.hip has no grouped kernel)
+      const ConvLayer& W = fuse ? B.fused : (S.pw.groups > 1 && h->gemm_mode == 0 ? S.pw_bd : S.pw);
       PwArgs a{};
+      a.groups = W.groups;
       a.busy_cus = h->busy_cus;
       a.wt = W.d_w; a.x = gx; a.lens = g_lens; a.scale = W.d_scale; a.shift = W.d_shift;
       a.res = (last_sub && B.has_res && !B.fused_res) ? R : nullptr;
@@ -1208,10 +1372,22 @@ int vasr_set_block_se(vasr_handle* h, int block, int reduction_ratio) {
   return 0;
 }
 
+int vasr_set_block_groups(vasr_handle* h, int block, int groups, int heads) {
+  if (!h) return fail(VASR_ERR_INVALID, "null handle");
+  if (h->finalized) return fail(VASR_ERR_STATE, "handle already finalized");
+  if (block < 0 || block >= (int)h->blocks.size()) return fail(VASR_ERR_INVALID, "block %d of %zu", block, h->blocks.size());
+  if (groups < 1) return fail(VASR_ERR_INVALID, "groups %d is not positive", groups);
+  if (heads == 0 || heads < -1) return fail(VASR_ERR_INVALID, "heads %d: -1 (none) or a positive count", heads);
+  h->blocks[block].groups = groups;
+  h->blocks[block].heads = heads > 0 ? heads : 0;
+  return 0;
+}
+
 int vasr_finalize(vasr_handle* h) {
   if (!h) return fail(VASR_ERR_INVALID, "null handle");
   if (h->finalized) return 0;
   int rc;
+  if (h->has_encoder && (rc = check_groups(h))) return rc;
   if (h->has_encoder && (rc = check_se(h))) return rc;
   if (h->has_frontend && (rc = build_frontend(h))) return rc;
   if (h->has_encoder && (rc = build_encoder(h))) return rc;

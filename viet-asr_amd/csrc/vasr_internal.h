@@ -27,6 +27,7 @@ struct DevSwitches {
   int fused_tile = 0;           // VASR_FUSED_TILE=64|128: pins the fused kernel's tile width
   bool fused_residual = true;   // VASR_NO_FUSED_RESIDUAL=1: a block's residual branch as its own GEMM, not as a second K range
   int beam_group = -1;          // VASR_BEAM_GROUP=0|1: always one wavefront per utterance, 4: always four
+  bool no_grouped = false;      // VASR_NO_GROUPED=1: every grouped layer as its block-diagonal dense form (no grouped GEMM)
 };
 #ifdef VASR_DEVTOOLS
 const DevSwitches& dev_switches();
@@ -193,6 +194,11 @@ struct PwArgs {
   int32_t conv_cin, conv_stride, conv_dil, conv_pad;
   int64_t conv_cols;
   int64_t bsx;            // batch stride of x in elements (0: K * ldx) -- the dense-residual pane buffer holds more channels
+  // grouped convolution + channel shuffle (split kernels only; 0 or 1: dense): wt is the [M][K] weight of a conv with `groups`
+  // groups, K its per-group reduction (taps * C_in / groups), x holds groups * K / taps channels per utterance; rows of group
+  // g = m / (M / groups) read channels g * K / taps on, and pre-shuffle row g * (M / groups) + j is stored (residual added) at
+  // row j * groups + g.  Needs m_store == M and grouped_split_supported.
+  int32_t groups;
 };
 void launch_pointwise(const PwArgs& a, hipStream_t st);
 // host: [cout][cin] row-major -> fragment order [m_pad/32][cin/8][64][4] (zero rows past cout)
@@ -203,6 +209,8 @@ void pack_pointwise_weights(const float* w, int cout, int cin, int m_pad, float*
 // (three; needs amax_x / w_inv_scale and the fp16 pack).  Returns 0 or a hipError_t.
 bool pointwise_split_supported(int M, int K, int K1);
 bool conv_split_supported(int M, int cin);
+// grouped split GEMM (PwArgs::groups): cout / groups and cin / groups (per tap) multiples of 64, cout of 128
+bool grouped_split_supported(int cout, int cin, int groups);
 // host: [cout][cin][kernel] -> the implicit GEMM's [cout][kernel * cin] (k = tap * cin + c), input of the pointwise packers
 void pack_conv_gemm_weights(const float* w, int cout, int cin, int kernel, float* out);
 double launch_mfma_sustained(int gemm_mode, int n_cu, int steps, float* sink, hipStream_t st);

@@ -23,15 +23,24 @@ def _require_gpu():
                              "there is no CPU fallback for this path")
 
 
+def compute_new_kernel_size(kernel_size, kernel_width):
+    """JasperBlock's kernel_size_factor (parts/jasper.py:52-57): max(int(K * f), 1), plus one if that is even."""
+    k = max(int(kernel_size * kernel_width), 1)
+    return k + 1 if k % 2 == 0 else k
+
+
 def blocks_from_config(jasper_cfg):
-    """YAML block list (configs/*.yaml JasperEncoder.jasper) -> vasr_block_desc dicts."""
+    """YAML block list (configs/*.yaml JasperEncoder.jasper) -> vasr_block_desc dicts.  ``kernel_size_factor`` is applied to
+    the kernel here; groups and heads are read by groups_from_config."""
     def one(v):
         return int(v[0] if isinstance(v, (list, tuple)) else v)
     out = []
     for l in jasper_cfg:
-        if l.get("groups", 1) != 1 or l.get("heads", -1) != -1 or float(l.get("kernel_size_factor", 1.0)) != 1.0:
-            raise NotImplementedError("groups/heads/kernel_size_factor other than the defaults are not implemented")
-        out.append(dict(filters=int(l["filters"]), repeat=int(l["repeat"]), kernel=one(l["kernel"]),
+        k = one(l["kernel"])
+        f = float(l.get("kernel_size_factor", 1.0))
+        if f != 1.0:
+            k = compute_new_kernel_size(k, f)
+        out.append(dict(filters=int(l["filters"]), repeat=int(l["repeat"]), kernel=k,
                         stride=one(l["stride"]), dilation=one(l["dilation"]),
                         residual=int(bool(l["residual"])), separable=int(bool(l.get("separable", False))),
                         residual_dense=int(bool(l.get("residual_dense", False)))))
@@ -54,6 +63,22 @@ def se_from_config(jasper_cfg):
             raise ValueError(f"se_reduction_ratio {r} leaves no hidden unit of {l['filters']} channels "
                              "(the reference builds a zero-width Linear)")
         out.append(int(r))
+    return out
+
+
+def groups_from_config(jasper_cfg):
+    """Per block of a YAML block list: (groups, heads) -- JasperBlock's grouped main-branch convs followed by a channel shuffle
+    (default 1) and the depthwise weights shared by ``heads`` rows (default -1: none), the arguments of vasr_set_block_groups.
+    heads is -1 for a block that is not separable: the reference hands heads to the depthwise conv of a separable block only
+    (parts/jasper.py:353-386) and ignores it elsewhere."""
+    out = []
+    for l in jasper_cfg:
+        g, h = l.get("groups", 1), l.get("heads", -1)
+        if int(g) != g or g < 1:
+            raise ValueError(f"groups must be a positive integer, got {g!r}")
+        if int(h) != h or (h != -1 and h < 1):
+            raise ValueError(f"heads must be -1 or a positive integer, got {h!r}")
+        out.append((int(g), int(h) if l.get("separable", False) else -1))
     return out
 
 
@@ -108,10 +133,11 @@ class QuartzNetCTC:
         self.hop = self.frontend["hop_length"]
         self._blocks = blocks_from_config(jas)
         self._se = se_from_config(jas)
+        self._groups = groups_from_config(jas)
         with torch.cuda.device(self.device):
             self.handle = _lib.Handle(frontend=self.frontend, feat_in=pre.get("features", 64),
                                       blocks=blocks_from_config(jas), dec_feat_in=jas[-1]["filters"],
-                                      num_classes=len(self.labels) + 1, se=self._se)
+                                      num_classes=len(self.labels) + 1, se=self._se, groups=self._groups)
             self.handle.load_state_dict(encoder_state)
             self.handle.load_state_dict(decoder_state)
             self.handle.finalize()

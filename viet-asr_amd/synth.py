@@ -49,7 +49,7 @@ def _bn(prefix, seed, c, out):
 
 
 def kernel_of(lcfg):
-    """Effective (odd) kernel width of a block (parts/jasper.py:52-57, kernel_size_factor=1)."""
+    """Effective (odd) kernel width of a block, its kernel_size_factor applied (parts/jasper.py:52-57)."""
     k = lcfg["kernel"]
     k = k[0] if isinstance(k, (list, tuple)) else k
     f = float(lcfg.get("kernel_size_factor", 1.0))
@@ -72,20 +72,25 @@ def encoder_state_dict(jasper_cfg, feat_in, seed=0):
         cout, rep, k = l["filters"], l["repeat"], kernel_of(l)
         sep = l.get("separable", False)
         se = l.get("se_reduction_ratio", 16) if l.get("se", False) else 0
+        groups, heads = int(l.get("groups", 1)), int(l.get("heads", -1))
         c = cin
         j = 0
         for r in range(rep):
             p = f"encoder.{i}.mconv"
             if sep:
-                sd[f"{p}.{j}.conv.weight"] = _conv_weight(f"{p}.{j}.conv.weight", seed, c, 1, k, gain=G_MAIN)
-                sd[f"{p}.{j + 1}.conv.weight"] = _conv_weight(f"{p}.{j + 1}.conv.weight", seed, cout, c, 1, gain=G_MAIN)
+                # heads: one [heads, 1, K] weight shared by the channels; groups: [cout, c / groups, 1] (fan-in scaled)
+                sd[f"{p}.{j}.conv.weight"] = _conv_weight(f"{p}.{j}.conv.weight", seed, heads if heads != -1 else c, 1, k,
+                                                          gain=G_MAIN)
+                sd[f"{p}.{j + 1}.conv.weight"] = _conv_weight(f"{p}.{j + 1}.conv.weight", seed, cout, c // groups, 1, gain=G_MAIN)
                 _bn(f"{p}.{j + 2}", seed, cout, sd)
                 j += 3
             else:
-                sd[f"{p}.{j}.conv.weight"] = _conv_weight(f"{p}.{j}.conv.weight", seed, cout, c, k,
+                sd[f"{p}.{j}.conv.weight"] = _conv_weight(f"{p}.{j}.conv.weight", seed, cout, c // groups, k,
                                                           gain=G_MAIN if k == 1 else G_CONV)
                 _bn(f"{p}.{j + 1}", seed, cout, sd)
                 j += 2
+            if groups > 1:
+                j += 1  # GroupShuffle slot
             if r != rep - 1:
                 j += 2  # activation + dropout slots
             if se and not l["residual"]:
