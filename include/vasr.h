@@ -147,6 +147,23 @@ VASR_API int vasr_set_block_se(vasr_handle* h, int block, int reduction_ratio);
  * dual-source residual GEMM.  (ABI 8: a function, no layout change.) */
 VASR_API int vasr_set_block_groups(vasr_handle* h, int block, int groups, int heads);
 
+/* JasperEncoder's normalization_mode / norm_groups (jasper.py:136-186, parts/jasper.py:385-391) for block `block`:
+ * norm_groups 0 = eval-mode BatchNorm1d(eps=1e-3) (the default, folded into the GEMM epilogues), G > 0 = nn.GroupNorm(G,
+ * filters) after every conv of the block -- "group" with norm_groups (-1: filters), "instance" = G filters, "layer" = G 1.
+ * GroupNorm: y = gamma[c] * (x - mean) / sqrt(var + 1e-5) + beta[c], mean and the BIASED variance per utterance and norm
+ * group (filters / G consecutive channels, counted before a grouped block's GroupShuffle), weights <prefix>.weight /
+ * <prefix>.bias [filters] at the BatchNorm's keys (no running statistics).  Order as in the reference: conv -> norm ->
+ * GroupShuffle -> activation (not on the last sub-layer) -> SE; each residual pane conv -> norm (-> SE), its own pass; the
+ * block output act(main + sum of the panes).  Between vasr_create and vasr_finalize.  vasr_finalize refuses, before it
+ * touches a device, a G that does not divide filters and a gamma / beta that is missing or not of shape [filters]
+ * (VASR_ERR_INVALID).  The one deliberate difference: the statistics are taken over each row's OWN frames at that layer
+ * (t < len_b), not over the padded tensor width as nn.GroupNorm does -- equal whenever the row is as long as the tensor
+ * (every batch-1 call with pad_to = 0 whose length is not a multiple of the hop), and what keeps a row's result independent
+ * of its batch.  Normalized blocks store their convs' raw outputs and take two device passes per norm (statistics, apply;
+ * encoder_norm.hip); they never take the fused depthwise + pointwise kernel or a folded residual.  (ABI 8: a function, no
+ * layout change.) */
+VASR_API int vasr_set_block_norm(vasr_handle* h, int block, int norm_groups);
+
 /* Checks that every tensor arrived, folds eval-mode BatchNorm1d(eps=1e-3)
  * (parts/jasper.py:392) into per-channel (scale, shift), packs the 1x1-conv weights
  * K-major for the MFMA kernels and uploads everything.  Needed before any compute call. */

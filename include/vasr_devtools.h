@@ -67,6 +67,14 @@ VASR_API int vasr_pack_pointwise_bf16x3(const float* h_w, int cout, int cin, int
 VASR_API int vasr_bench_pointwise_bf16x3(const float* d_x, const uint16_t* d_w3, const float* d_scale, const float* d_shift,
                                 int batch, int cin, int cout, int64_t frames, float* d_y, vasr_stream stream);
 
+/* GroupNorm's two device passes (encoder_norm.hip) in isolation: x, y [B][C][vasr_padded_frames(frames)], statistics over
+ * t < d_lens[b] (and < frames), y = act(gamma (x - mean) rstd + beta), columns past the row's length stored as 0.
+ * gamma / beta [C] on the host in PRE-shuffle order; shuffle = G_s > 1: the channels are stored after a GroupShuffle(G_s)
+ * (stored channel j * G_s + g holds pre-shuffle channel g * (C / G_s) + j), 1: no shuffle.  Synchronous (allocates its own
+ * tables).  VASR_ERR_INVALID when norm_groups does not divide C. */
+VASR_API int vasr_bench_groupnorm(const float* d_x, const int32_t* d_lens, int batch, int channels, int64_t frames,
+                                  int norm_groups, int shuffle, const float* h_gamma, const float* h_beta, int relu, float* d_y,
+                                  vasr_stream stream);
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,7 @@ SIGNATURES = {
     "vasr_set_row_independent": (C.c_int, [_P, C.c_int]),
     "vasr_set_busy_cus": (C.c_int, [_P, C.c_int]),
     "vasr_set_block_se": (C.c_int, [_P, C.c_int, C.c_int]),
+    "vasr_set_block_norm": (C.c_int, [_P, C.c_int, C.c_int]),
     "vasr_set_block_groups": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     "vasr_beam_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
     "vasr_beam_search_f32": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P,
@@ -107,6 +108,7 @@ DEV_SIGNATURES = {
     "vasr_bench_mfma_sustained": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_double), _P]),
     "vasr_bench_depthwise": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, _P, _P]),
     "vasr_bench_pointwise": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P]),
+    "vasr_bench_groupnorm": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
 }
 
 ABI_VERSION = 8          # VASR_ABI_VERSION of the include/vasr.h these signatures were written against
@@ -169,9 +171,10 @@ def _fptr(a):
 class Handle:
     """Owns one vasr_handle: any subset of {front end, encoder, CTC head}."""
 
-    def __init__(self, frontend=None, feat_in=0, blocks=None, dec_feat_in=0, num_classes=0, se=None, groups=None):
+    def __init__(self, frontend=None, feat_in=0, blocks=None, dec_feat_in=0, num_classes=0, se=None, groups=None, norm=None):
         """se: per block, the squeeze-and-excitation reduction ratio (0 = none; engine.se_from_config).  groups: per block,
-        (groups, heads) (engine.groups_from_config; (1, -1) = none)."""
+        (groups, heads) (engine.groups_from_config; (1, -1) = none).  norm: per block, the GroupNorm group count (0 =
+        BatchNorm; engine.norm_from_config)."""
         L = lib()
         self._keep = []
         md = ModelDesc()
@@ -211,6 +214,9 @@ class Handle:
         for i, (g, hd) in enumerate(groups or []):
             if g != 1 or hd != -1:
                 check(L.vasr_set_block_groups(h, i, int(g), int(hd)))
+        for i, g in enumerate(norm or []):
+            if g:
+                check(L.vasr_set_block_norm(h, i, int(g)))
         self.num_classes = int(num_classes)
 
     def load_state_dict(self, sd):

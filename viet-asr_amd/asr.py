@@ -16,7 +16,7 @@ from . import _lib, stages
 from .core import (AcousticEncodedRepresentation, AudioSignal, DataLayerNM, DeviceType, LengthsType,
                    LogprobsType, MelSpectrogramType, NeuralType, NonTrainableNM, PredictionsType,
                    SpectrogramType, TrainableNM)
-from .engine import blocks_from_config, check_dense_layout, groups_from_config, se_from_config
+from .engine import blocks_from_config, check_dense_layout, norm_from_config, groups_from_config, se_from_config
 from .frontend_tables import frontend_description
 
 __all__ = ["AudioToMelSpectrogramPreprocessor", "JasperEncoder", "JasperDecoderForCTC", "GreedyCTCDecoder",
@@ -120,10 +120,15 @@ class _SqueezeExciteParams(nn.Module):
 class _JasperBlockParams(nn.Module):
     """ModuleList skeleton of one JasperBlock (parts/jasper.py:214-288): same indices, parameters only.  se: the
     SqueezeExcite reduction ratio (0: none); groups: of the main-branch convs, each followed by a GroupShuffle slot when > 1;
-    heads: rows of the shared depthwise weights (-1: none)."""
+    heads: rows of the shared depthwise weights (-1: none); norm: GroupNorm's group count in every norm slot (0: BatchNorm)."""
 
-    def __init__(self, inplanes, planes, repeat, kernel, separable, residual, residual_panes=(), se=0, groups=1, heads=-1):
+    def __init__(self, inplanes, planes, repeat, kernel, separable, residual, residual_panes=(), se=0, groups=1, heads=-1,
+                 norm=0):
         super().__init__()
+
+        def norm_layer():   # parts/jasper.py:385-393
+            return nn.GroupNorm(norm, planes) if norm else nn.BatchNorm1d(planes, eps=1e-3, momentum=0.1)
+
         layers, c = [], inplanes
         for r in range(repeat):
             if separable:
@@ -131,7 +136,7 @@ class _JasperBlockParams(nn.Module):
                 layers += [dw, _MaskedConvParams(c, planes, 1, groups=groups)]
             else:
                 layers += [_MaskedConvParams(c, planes, kernel, groups=groups)]
-            layers.append(nn.BatchNorm1d(planes, eps=1e-3, momentum=0.1))
+            layers.append(norm_layer())
             if groups > 1:
                 layers.append(nn.Identity())                  # GroupShuffle slot (parts/jasper.py:396-399)
             if r != repeat - 1:
@@ -142,8 +147,7 @@ class _JasperBlockParams(nn.Module):
         self.mconv = nn.ModuleList(layers)
         self.res = None
         if residual:   # one 1x1 conv + BN (+ SE) per pane (parts/jasper.py:264-288); no dense panes: the block input alone
-            self.res = nn.ModuleList([nn.ModuleList([_MaskedConvParams(ip, planes, 1),
-                                                     nn.BatchNorm1d(planes, eps=1e-3, momentum=0.1)]
+            self.res = nn.ModuleList([nn.ModuleList([_MaskedConvParams(ip, planes, 1), norm_layer()]
                                                     + ([_SqueezeExciteParams(planes, se)] if se else []))
                                       for ip in (list(residual_panes) or [inplanes])])
 
@@ -196,11 +200,11 @@ class JasperEncoder(_HipWeights, TrainableNM):
         super().__init__()
         if activation not in ("hardtanh", "relu", "selu"):
             raise KeyError(activation)
-        if activation != "relu" or normalization_mode != "batch" or residual_mode != "add" or not conv_mask \
-                or frame_splicing != 1:
-            raise NotImplementedError("implemented: activation='relu', normalization_mode='batch', "
-                                      "residual_mode='add', conv_mask=True, frame_splicing=1")
+        if activation != "relu" or residual_mode != "add" or not conv_mask or frame_splicing != 1:
+            raise NotImplementedError("implemented: activation='relu', residual_mode='add', conv_mask=True, frame_splicing=1")
         self._blocks = blocks_from_config(jasper)
+        # (unknown modes and group counts that do not divide a block's filters: ValueError, as the reference raises)
+        self._norm = norm_from_config(dict(normalization_mode=normalization_mode, norm_groups=norm_groups), jasper)
         self._se = se_from_config(jasper)
         self._groups = groups_from_config(jasper)
         self._feat_in = feat_in * frame_splicing
@@ -210,14 +214,14 @@ class JasperEncoder(_HipWeights, TrainableNM):
                 raise ValueError("Only stride OR dilation may be greater than 1")   # parts/jasper.py:61-62
         layers, c = [], self._feat_in
         residual_panes = []     # ONE list shared by the dense blocks, copied by each (jasper.py:152-161, parts/jasper.py:264)
-        for b, se, (groups, heads) in zip(self._blocks, self._se, self._groups):
+        for b, se, (groups, heads), norm in zip(self._blocks, self._se, self._groups, self._norm):
             k = b["kernel"] + (1 if b["kernel"] % 2 == 0 else 0)
             dense_res = []
             if b["residual_dense"]:
                 residual_panes.append(c)
                 dense_res = residual_panes
             layers.append(_JasperBlockParams(c, b["filters"], b["repeat"], k, bool(b["separable"]), bool(b["residual"]),
-                                             list(dense_res), se, groups, heads))
+                                             list(dense_res), se, groups, heads, norm))
             c = b["filters"]
         self.encoder = nn.Sequential(*layers)
         self._c_out = c
@@ -228,7 +232,7 @@ class JasperEncoder(_HipWeights, TrainableNM):
         if self._handle is None:
             if not torch.cuda.is_available():
                 raise _no_gpu()
-            h = _lib.Handle(feat_in=self._feat_in, blocks=self._blocks, se=self._se, groups=self._groups)
+            h = _lib.Handle(feat_in=self._feat_in, blocks=self._blocks, se=self._se, groups=self._groups, norm=self._norm)
             h.load_state_dict(self.state_dict())
             h.finalize()
             self._handle = h

@@ -72,6 +72,17 @@ struct SeLayer {
   int c = 0, hidden = 0;
 };
 
+// GroupNorm (parts/jasper.py:385-391; encoder_norm.hip) after a convolution whose GEMM stores its raw output: gamma / beta
+// and the group of every STORED channel (a grouped block stores them shuffled), members = the stored channels of each group
+// in pre-shuffle order (d_gamma == nullptr: none -- BatchNorm, folded into the GEMM's epilogue)
+struct NormLayer {
+  float* d_gamma = nullptr;
+  float* d_beta = nullptr;
+  int32_t* d_group_of = nullptr;
+  int32_t* d_members = nullptr;
+  int c = 0, groups = 0;
+};
+
 struct SubBlock {
   bool separable = true;
   ConvLayer dw, pw;
@@ -79,6 +90,7 @@ struct SubBlock {
   // shuffle -- what the fp32 mode runs (encoder_pw.hip has no grouped form)
   ConvLayer pw_bd;
   SeLayer se;               // se and not residual: after this sub-layer (d_w1 == nullptr: none)
+  NormLayer norm;           // GroupNorm of the conv's output (the GEMM then stores it raw)
 };
 
 struct Block {
@@ -105,6 +117,11 @@ struct Block {
   // groups / heads (vasr_set_block_groups): every main-branch conv grouped (groups > 1) and followed by a GroupShuffle; the
   // depthwise weights of a separable block shared by channel c % heads (heads > 0)
   int groups = 1, heads = 0;
+  // norm_g (vasr_set_block_norm): 0 = BatchNorm (folded into the epilogues), else GroupNorm(norm_g, filters) after every conv
+  // of the block: its GEMMs store raw output, each residual pane is its own GEMM normalized on its own (res_norm[p]), and
+  // the last sub-layer's normalization adds the residual sum and applies the output activation
+  int norm_g = 0;
+  std::vector<NormLayer> res_norm;
   std::vector<SeLayer> res_se;
   std::vector<ConvLayer> res_panes;
   std::vector<int> res_pane_off;
@@ -136,6 +153,7 @@ struct vasr_handle {
   std::vector<Block> blocks;
   int pane_c_max = 0;   // channels of the dense-residual pane buffer (0: no dense residual GEMM)
   int se_c_max = 0;     // widest squeeze-and-excitation (0: the model has none)
+  int norm_c_max = 0, norm_g_max = 0;   // widest GroupNorm, most groups (0: the model has none)
   std::vector<LenStep> steps;
   std::map<std::string, HostTensor> weights;
   std::vector<void*> dev_allocs;
@@ -261,6 +279,54 @@ int fold_bn(vasr_handle* h, const std::string& prefix, int c, int c_pad, ConvLay
   }
   if ((rc = upload(h, sc, &L->d_scale))) return rc;
   return upload(h, sh, &L->d_shift);
+}
+
+// a normalized block's GEMMs store their raw output: scale 1, shift 0 (GroupNorm follows in encoder_norm.hip)
+int unit_affine(vasr_handle* h, int c, int c_pad, ConvLayer* L) {
+  std::vector<float> sc(c_pad, 0.f), sh(c_pad, 0.f);
+  std::fill_n(sc.begin(), c, 1.f);
+  int rc;
+  if ((rc = upload(h, sc, &L->d_scale))) return rc;
+  return upload(h, sh, &L->d_shift);
+}
+
+// BatchNorm under `prefix` folded into L's epilogue, or (norm_g > 0) the unit affine of a layer GroupNorm follows
+int conv_affine(vasr_handle* h, int norm_g, const std::string& prefix, int c, int c_pad, ConvLayer* L,
+                const std::vector<int>* perm = nullptr) {
+  return norm_g ? unit_affine(h, c, c_pad, L) : fold_bn(h, prefix, c, c_pad, L, perm);
+}
+
+// GroupNorm(G, c) under `prefix` (weight / bias [c]); perm (optional): pre-shuffle channel p is stored at row perm[p]
+int load_norm(vasr_handle* h, const std::string& prefix, int c, int G, const std::vector<int>* perm, NormLayer* L) {
+  const HostTensor *g, *b;
+  int rc;
+  if ((rc = need(h, prefix + ".weight", c, &g)) || (rc = need(h, prefix + ".bias", c, &b))) return rc;
+  const int cpg = c / G;
+  std::vector<float> gs(c), bs(c);
+  std::vector<int32_t> group_of(c), members(c);
+  for (int p = 0; p < c; ++p) {
+    const int o = perm ? (*perm)[p] : p;
+    gs[o] = g->data[p];
+    bs[o] = b->data[p];
+    group_of[o] = p / cpg;
+    members[p] = o;
+  }
+  L->c = c;
+  L->groups = G;
+  h->norm_c_max = std::max(h->norm_c_max, c);
+  h->norm_g_max = std::max(h->norm_g_max, G);
+  if ((rc = upload(h, gs, &L->d_gamma)) || (rc = upload(h, bs, &L->d_beta)) || (rc = upload(h, group_of, &L->d_group_of)))
+    return rc;
+  return upload(h, members, &L->d_members);
+}
+
+// the channel shuffle of a grouped block (parts/jasper.py:135-150): pre-shuffle channel p = g * (c / G) + j is stored at
+// j * G + g
+std::vector<int> shuffle_perm(int c, int G) {
+  std::vector<int> perm(c);
+  const int mg = c / G;
+  for (int p = 0; p < c; ++p) perm[p] = (p % mg) * G + p / mg;
+  return perm;
 }
 
 int bn_affine(vasr_handle* h, const std::string& prefix, int c, std::vector<float>* alpha, std::vector<float>* beta) {
@@ -391,16 +457,15 @@ int pack_pointwise(vasr_handle* h, const std::string& key, int cout, int cin, Co
 //       grouped_split_supported and not VASR_NO_GROUPED, else a copy of BD.
 // conv: the implicit-GEMM form (a K-tap or strided conv), else a 1x1.
 int pack_grouped(vasr_handle* h, const std::string& key, const std::string& bn, int cout, int cin, int kernel, int G, bool conv,
-                 ConvLayer* L, ConvLayer* BD) {
+                 ConvLayer* L, ConvLayer* BD, int norm_g) {
   const HostTensor* w;
   int rc;
   const int cg = cin / G, mg = cout / G;
   if ((rc = need(h, key, (size_t)cout * cg * kernel, &w))) return rc;
   std::vector<float> dense((size_t)cout * cin * kernel, 0.f);
-  std::vector<int> perm(cout);
+  const std::vector<int> perm = shuffle_perm(cout, G);
   for (int p = 0; p < cout; ++p) {
-    const int g = p / mg, o = (p % mg) * G + g;
-    perm[p] = o;
+    const int g = p / mg, o = perm[p];
     for (int c = 0; c < cg; ++c)
       for (int t = 0; t < kernel; ++t)
         dense[((size_t)o * cin + g * cg + c) * kernel + t] = w->data[((size_t)p * cg + c) * kernel + t];
@@ -409,7 +474,7 @@ int pack_grouped(vasr_handle* h, const std::string& key, const std::string& bn, 
   const bool grouped = !h->sw.no_grouped && grouped_split_supported(cout, cin, G);
   if ((rc = conv ? pack_conv_data(h, dense.data(), key, cout, cin, kernel, BD, true, !grouped)
                  : pack_pointwise_data(h, dense.data(), key, cout, cin, BD, true, !grouped)) ||
-      (rc = fold_bn(h, bn, cout, BD->m_pad, BD, &perm)))
+      (rc = conv_affine(h, norm_g, bn, cout, BD->m_pad, BD, &perm)))
     return rc;
   if (!grouped) {
     *L = *BD;
@@ -418,7 +483,7 @@ int pack_grouped(vasr_handle* h, const std::string& key, const std::string& bn, 
   }
   if ((rc = conv ? pack_conv_data(h, w->data.data(), key, cout, cg, kernel, L, false)
                  : pack_pointwise_data(h, w->data.data(), key, cout, cg, L, false)) ||
-      (rc = fold_bn(h, bn, cout, L->m_pad, L)))
+      (rc = conv_affine(h, norm_g, bn, cout, L->m_pad, L)))
     return rc;
   L->groups = G;
   return 0;
@@ -539,6 +604,48 @@ int check_groups(vasr_handle* h) {
   return 0;
 }
 
+// State-dict prefixes of block i's GroupNorms: each main-branch conv's norm entry (mconv_layout), then each residual pane's
+// entry 1 (conv, norm (, SE))
+std::vector<std::string> norm_prefixes(const vasr_handle* h, size_t i) {
+  const Block& B = h->blocks[i];
+  std::vector<std::string> out;
+  char key[160];
+  for (const SubKeys& k : mconv_layout(B)) {
+    snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, k.bn);
+    out.push_back(key);
+  }
+  if (B.d.residual) {
+    const int panes = B.dense_panes >= 2 ? B.dense_panes : 1;
+    for (int q = 0; q < panes; ++q) {
+      snprintf(key, sizeof key, "encoder.%zu.res.%d.1", i, q);
+      out.push_back(key);
+    }
+  }
+  return out;
+}
+
+// vasr_finalize's check of GroupNorm blocks (before anything touches the device): the group count divides the block's
+// filters (nn.GroupNorm's ValueError), and every norm's weight and bias are there with shape [filters] -- both refusals
+// VASR_ERR_INVALID
+int check_norm(vasr_handle* h) {
+  for (size_t i = 0; i < h->blocks.size(); ++i) {
+    const Block& B = h->blocks[i];
+    if (!B.norm_g) continue;
+    const int c = B.d.filters;
+    if (!norm_supported(c, B.norm_g))
+      return fail(VASR_ERR_INVALID, "block %zu: norm_groups %d does not divide the %d channels", i, B.norm_g, c);
+    for (const std::string& pre : norm_prefixes(h, i))
+      for (const char* leaf : {".weight", ".bias"}) {
+        const std::string key = pre + leaf;
+        const HostTensor* t = find(h, key);
+        if (!t) return fail(VASR_ERR_INVALID, "block %zu: missing GroupNorm weight '%s'", i, key.c_str());
+        if (t->shape.size() != 1 || t->shape[0] != c)
+          return fail(VASR_ERR_INVALID, "block %zu: GroupNorm weight '%s' is not of shape [%d]", i, key.c_str(), c);
+      }
+  }
+  return 0;
+}
+
 int load_se(vasr_handle* h, const std::string& pre, int c, int ratio, SeLayer* L) {
   const HostTensor *w1, *w2;
   int rc;
@@ -644,21 +751,21 @@ int build_encoder(vasr_handle* h) {
         if (B.groups > 1) {
           char bn[160];
           snprintf(bn, sizeof bn, "encoder.%zu.mconv.%d", i, jbn);
-          if ((rc = pack_grouped(h, key, bn, d.filters, c, 1, B.groups, false, &S.pw, &S.pw_bd))) return rc;
+          if ((rc = pack_grouped(h, key, bn, d.filters, c, 1, B.groups, false, &S.pw, &S.pw_bd, B.norm_g))) return rc;
         } else if ((rc = pack_pointwise(h, key, d.filters, c, &S.pw))) {
           return rc;
         }
         S.pw.step = step++;
         h->steps.push_back(LenStep{1, 1, 1, 0});
         snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, jbn);
-        if (B.groups == 1 && (rc = fold_bn(h, key, d.filters, S.pw.m_pad, &S.pw))) return rc;
+        if (B.groups == 1 && (rc = conv_affine(h, B.norm_g, key, d.filters, S.pw.m_pad, &S.pw))) return rc;
       } else {
         snprintf(key, sizeof key, "encoder.%zu.mconv.%d.conv.weight", i, j);
         const bool conv = !(k == 1 && d.stride == 1);   // K-tap / strided: implicit GEMM (encoder_pw_split.hip, encoder_pw.hip CONV)
         if (B.groups > 1) {
           char bn[160];
           snprintf(bn, sizeof bn, "encoder.%zu.mconv.%d", i, jbn);
-          if ((rc = pack_grouped(h, key, bn, d.filters, c, k, B.groups, conv, &S.pw, &S.pw_bd))) return rc;
+          if ((rc = pack_grouped(h, key, bn, d.filters, c, k, B.groups, conv, &S.pw, &S.pw_bd, B.norm_g))) return rc;
         } else if ((rc = conv ? pack_conv(h, key, d.filters, c, k, &S.pw) : pack_pointwise(h, key, d.filters, c, &S.pw))) {
           return rc;
         }
@@ -670,11 +777,16 @@ int build_encoder(vasr_handle* h) {
         }
         S.pw.step = step++;
         snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, jbn);
-        if (B.groups == 1 && (rc = fold_bn(h, key, d.filters, S.pw.m_pad, &S.pw))) return rc;
+        if (B.groups == 1 && (rc = conv_affine(h, B.norm_g, key, d.filters, S.pw.m_pad, &S.pw))) return rc;
       }
       if (S.pw_bd.d_w) {          // the block-diagonal form runs the same geometry
         S.pw_bd.kernel = S.pw.kernel; S.pw_bd.stride = S.pw.stride; S.pw_bd.dilation = S.pw.dilation; S.pw_bd.pad = S.pw.pad;
         S.pw_bd.step = S.pw.step;
+      }
+      if (B.norm_g) {            // GroupNorm entry, before the GroupShuffle: its channels are stored shuffled
+        snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, jbn);
+        const std::vector<int> perm = shuffle_perm(d.filters, B.groups);
+        if ((rc = load_norm(h, key, d.filters, B.norm_g, B.groups > 1 ? &perm : nullptr, &S.norm))) return rc;
       }
       if (lay[r].se >= 0) {      // SqueezeExcite entry (parts/jasper.py:233-234, :250-251)
         snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, lay[r].se);
@@ -690,14 +802,23 @@ int build_encoder(vasr_handle* h) {
       for (size_t q = 0; q < pre.size(); ++q)
         if ((rc = load_se(h, pre[q], d.filters, B.se_r, &B.res_se[q]))) return rc;
     }
-    if (B.has_res && B.se_r && B.dense_panes >= 2) {
+    if (B.has_res && B.norm_g) {
+      // one GroupNorm per residual pane (not grouped, not shuffled)
+      const int panes = B.dense_panes >= 2 ? B.dense_panes : 1;
+      B.res_norm.resize(panes);
+      for (int q = 0; q < panes; ++q) {
+        snprintf(key, sizeof key, "encoder.%zu.res.%d.1", i, q);
+        if ((rc = load_norm(h, key, d.filters, B.norm_g, nullptr, &B.res_norm[q]))) return rc;
+      }
+    }
+    if (B.has_res && (B.se_r || B.norm_g) && B.dense_panes >= 2) {
       B.res_panes.resize(B.dense_panes);
       for (int q = 0; q < B.dense_panes; ++q) {
         const Block& P = h->blocks[i - B.dense_panes + 1 + q];
         snprintf(key, sizeof key, "encoder.%zu.res.%d.0.conv.weight", i, q);
         if ((rc = pack_pointwise(h, key, d.filters, P.pane_c, &B.res_panes[q]))) return rc;
         snprintf(key, sizeof key, "encoder.%zu.res.%d.1", i, q);
-        if ((rc = fold_bn(h, key, d.filters, B.res_panes[q].m_pad, &B.res_panes[q]))) return rc;
+        if ((rc = conv_affine(h, B.norm_g, key, d.filters, B.res_panes[q].m_pad, &B.res_panes[q]))) return rc;
         B.res_pane_off.push_back(P.pane_off);
       }
     } else if (B.has_res && B.dense_panes >= 2) {
@@ -716,14 +837,14 @@ int build_encoder(vasr_handle* h) {
       snprintf(key, sizeof key, "encoder.%zu.res.0.0.conv.weight", i);
       if ((rc = pack_pointwise(h, key, d.filters, cin, &B.res))) return rc;
       snprintf(key, sizeof key, "encoder.%zu.res.0.1", i);
-      if ((rc = fold_bn(h, key, d.filters, B.res.m_pad, &B.res))) return rc;
+      if ((rc = conv_affine(h, B.norm_g, key, d.filters, B.res.m_pad, &B.res))) return rc;
       // fold the residual branch into the last sub-block's GEMM when both reductions tile evenly
       const SubBlock& last = B.subs.back();
       const int k1 = last.pw.cin, k2 = cin;
       const int chunk = d.filters % 512 == 0 ? 128 : (d.filters % 256 == 0 ? 64 : 32);
       // (grouped blocks: the main branch's grouped reduction and the residual's dense one share no K)
       if (d.stride == 1 && k1 % chunk == 0 && k2 % chunk == 0 && h->sw.fused_residual && !last.pw.conv_cin && !B.res_pane0 &&
-          !B.se_r && B.groups == 1) {
+          !B.se_r && B.groups == 1 && !B.norm_g) {
         char w1[160], bn1[160], w2[160], bn2[160];
         snprintf(w1, sizeof w1, "encoder.%zu.mconv.%d.conv.weight", i, lay.back().conv + (last.separable ? 1 : 0));
         snprintf(bn1, sizeof bn1, "encoder.%zu.mconv.%d", i, lay.back().bn);
@@ -759,7 +880,7 @@ int build_decoder(vasr_handle* h) {
 
 // ---------------- workspace plan ----------------
 struct WsPlan {
-  size_t lens_tab, amax, se, seq, melp, bufP, bufQ, bufD, bufR, bufS, pane, encp, logits, pred, total;
+  size_t lens_tab, amax, se, norm, seq, melp, bufP, bufQ, bufD, bufR, bufS, pane, encp, logits, pred, total;
   int64_t T, Tp0, T1, Tp1;
   int amax_stride;   // slots per utterance of one maxima table (kAmaxTabs tables: [tab][B][amax_stride] u32)
 };
@@ -802,9 +923,12 @@ WsPlan plan_ws(const vasr_handle* h, int batch, int64_t T) {
       }
     if (h->pane_c_max) p.amax_stride = std::max(p.amax_stride, 256);   // launch_amax over the pane buffer
     if (h->se_c_max) p.amax_stride = std::max(p.amax_stride, 256);     // launch_se republishes up to 256 slots
+    if (h->norm_c_max) p.amax_stride = std::max(p.amax_stride, 256);   // launch_norm too
   }
   p.amax = take((size_t)kAmaxTabs * batch * p.amax_stride * 4);
   p.se = take((size_t)2 * batch * h->se_c_max * 4);   // SE row sums and scales, [B][c] each
+  // GroupNorm row means and M2 [B][c] each, group means and 1 / std [B][G] each
+  p.norm = take((size_t)2 * batch * (h->norm_c_max + h->norm_g_max) * 4);
   p.seq = take((size_t)batch * 8);
   p.melp = take((size_t)batch * (h->has_encoder ? h->feat_in : 64) * p.Tp0 * 4);
   const size_t mid = (size_t)batch * h->c_mid_max * std::max(tp_mid, p.Tp1) * 4;
@@ -943,6 +1067,27 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
     if (e) return fail(VASR_ERR_HIP, "squeeze-and-excitation: %s", hipGetErrorString((hipError_t)e));
     return 0;
   };
+  // GroupNorm of a tensor [B][L.c][ld] a GEMM has just stored raw (encoder_norm.hip): statistics over t < stat_lens[b],
+  // then y = act(norm(x) (+ add)) over the stored columns, zero from zero_lens[b] on (nullptr: none); add has pitch add_ld
+  float* nrm_ws = reinterpret_cast<float*>(ws + p.norm);
+  auto run_norm = [&](const NormLayer& L, const float* nx, float* ny, const float* add, int64_t ld, int64_t add_ld,
+                      int64_t frames, int store_cols, const int32_t* stat_lens, const int32_t* zero_lens, int relu, AmaxTab* am,
+                      const int32_t* lens_y) -> int {
+    NormLaunch a{};
+    a.x = nx; a.y = ny; a.add = add; a.ld = ld; a.ld_add = add_ld; a.bs = 0;
+    a.channels = L.c; a.groups = L.groups; a.batch = batch; a.frames = (int)frames; a.store_cols = store_cols;
+    a.lens = stat_lens; a.group_of = L.d_group_of; a.members = L.d_members; a.gamma = L.d_gamma; a.beta = L.d_beta;
+    a.row_mean = nrm_ws; a.row_m2 = nrm_ws + (size_t)batch * h->norm_c_max;
+    a.g_mean = nrm_ws + (size_t)2 * batch * h->norm_c_max; a.g_rstd = a.g_mean + (size_t)batch * h->norm_g_max;
+    a.zero_lens = zero_lens; a.relu = relu; a.amax_y = am; a.lens_y = lens_y;
+    // (counted with the depthwise class, as the SE passes are: statistics and affine, ~5 flops per element; two reads for
+    // the statistics, a read and a write to apply)
+    ProfScope ps(h, kProfDepthwise, st, 5.0 * L.c * (double)frames * batch,
+                 4.0 * (add ? 5.0 : 4.0) * L.c * (double)store_cols * batch);
+    const int e = launch_norm(a, st);
+    if (e) return fail(VASR_ERR_HIP, "group norm: %s", hipGetErrorString((hipError_t)e));
+    return 0;
+  };
   for (size_t i = 0; i < h->blocks.size(); ++i) {
     Block& B = h->blocks[i];
     const bool last_block = i + 1 == h->blocks.size();
@@ -967,9 +1112,11 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
       HIP_TRY(hipMemcpy2DAsync(panes + (int64_t)B.pane_off * cur_ld, (size_t)pane_bs * 4, cur, (size_t)B.pane_c * cur_ld * 4,
                                (size_t)B.pane_c * cur_ld * 4, batch, hipMemcpyDeviceToDevice, st));
     }
-    if (B.has_res && B.se_r && B.dense_panes >= 2) {
-      // dense residual with SE: sum_p SE_p(BN_p(W_p mask(x_p))) (parts/jasper.py:428-439) -- pane 0's GEMM writes R and is
-      // rescaled in place, every later pane's goes through D and is scaled onto R
+    // residual panes' masks: the block input lengths; a last block's residual keeps its padding columns (the encoder output's)
+    const int32_t* res_zero = last_block ? nullptr : lens(B.first_step);
+    if (B.has_res && (B.se_r || B.norm_g) && B.dense_panes >= 2) {
+      // dense residual with SE or GroupNorm: sum_p SE_p(N_p(W_p mask(x_p))) (parts/jasper.py:428-439) -- pane 0's GEMM writes R
+      // and is normalized / rescaled in place, every later pane's goes through D and is added onto R by its last pass
       for (int q = 0; q < B.dense_panes; ++q) {
         const ConvLayer& W = B.res_panes[q];
         float* Rq = q == 0 ? R : D;
@@ -988,8 +1135,11 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
           ProfScope ps(h, kProfPointwise, st, 2.0 * W.cin * W.cout * (double)cur_T * batch, 4.0 * W.m_pad * (double)cur_ld * batch);
           if (run_pointwise(h, a, W, st) < 0) return VASR_ERR_HIP;
         }
-        if (run_se(B.res_se[q], Rq, R, cur_ld, cur_T, (int)cur_ld, lens(B.first_step), last_block ? nullptr : lens(B.first_step),
-                   0, q > 0, nullptr, nullptr))
+        if (B.norm_g && run_norm(B.res_norm[q], Rq, B.se_r ? Rq : R, (!B.se_r && q > 0) ? R : nullptr, cur_ld, cur_ld, cur_T,
+                                 (int)cur_ld, lens(B.first_step), res_zero, 0, nullptr, nullptr))
+          return VASR_ERR_HIP;
+        if (B.se_r && run_se(B.res_se[q], Rq, R, cur_ld, cur_T, (int)cur_ld, lens(B.first_step), res_zero, 0, q > 0, nullptr,
+                             nullptr))
           return VASR_ERR_HIP;
       }
     } else if (B.has_res && B.dense_panes >= 2) {
@@ -1030,7 +1180,10 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
                      4.0 * B.res.m_pad * (double)cur_ld * batch);   // bytes of class 2 = what the GEMM STORES (its epilogue's share of the time)
         if (run_pointwise(h, a, B.res, st) < 0) return VASR_ERR_HIP;
       }
-      // se and residual: the residual branch's SqueezeExcite, in place on R (parts/jasper.py:279-280)
+      // GroupNorm, then (se and residual) the residual branch's SqueezeExcite, in place on R (parts/jasper.py:275-280)
+      if (B.norm_g && run_norm(B.res_norm[0], R, R, nullptr, cur_ld, cur_ld, cur_T, (int)cur_ld, lens(B.first_step), res_zero, 0,
+                               nullptr, nullptr))
+        return VASR_ERR_HIP;
       if (B.se_r && run_se(B.res_se[0], R, R, cur_ld, cur_T, (int)cur_ld, lens(B.first_step),
                            last_block ? nullptr : lens(B.first_step), 0, 0, nullptr, nullptr))
         return VASR_ERR_HIP;
@@ -1081,7 +1234,7 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
       // round differently -- that mode promises bit-identical rows whatever the batch)
       // (a sub-layer whose output feeds an SE: the fused kernel does not produce its row sums)
       if (fused_on && !h->row_independent && S.separable && S.dw.d_ftaps && h->gemm_mode == 3 && want_amax && cur_amax.p && WF.d_w16 &&
-          !S.se.d_w1 && B.groups == 1 &&   // (no grouped form of the fused kernel)
+          !S.se.d_w1 && B.groups == 1 && !S.norm.d_gamma &&   // (no grouped form of the fused kernel, no raw store)
           !(last_sub && B.has_res && !B.fused_res) &&
           // a folded residual must come from a 256-channel block input (K = 256 + 256): the kernel's second K range is 4 chunks
           (fuse_res ? (blk_amax.p && blk_ld == cur_ld && WF.cin == 2 * S.dw.cin && B.fused_k1 == S.dw.cin) : WF.cin == S.dw.cin) &&
@@ -1156,11 +1309,14 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
       a.groups = W.groups;
       a.busy_cus = h->busy_cus;
       a.wt = W.d_w; a.x = gx; a.lens = g_lens; a.scale = W.d_scale; a.shift = W.d_shift;
-      a.res = (last_sub && B.has_res && !B.fused_res) ? R : nullptr;
+      // (a normalized block: the GEMM stores its raw output, the GroupNorm pass adds the residual)
+      const bool nrm = S.norm.d_gamma != nullptr;
+      a.res = (last_sub && B.has_res && !B.fused_res && !nrm) ? R : nullptr;
       a.y = dst; a.M = W.m_pad; a.K = W.cin; a.batch = batch;
       a.ldx = gx_ld; a.ldy = dst_ld; a.ldr = blk_ld; a.frames = (int)g_T; a.m_store = W.m_pad;
       // se and not residual: the last sub-layer's SE comes before the block's output activation (parts/jasper.py:250-251, mout)
-      a.relu = (last_sub && S.se.d_w1) ? 0 : 1;
+      const int act = (last_sub && S.se.d_w1) ? 0 : 1;
+      a.relu = nrm ? 0 : act;
       a.store_cols = (dst_ld % kTimeTile == 0) ? (int)dst_ld : (int)g_T;  // port tensors are not padded
       if (W.conv_cin) {
         a.conv_cin = W.conv_cin; a.conv_stride = W.stride; a.conv_dil = W.dilation; a.conv_pad = W.pad;
@@ -1169,7 +1325,7 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
       // the depthwise output is zero past its lens_out, a masked input past its mask: tiles out there skip their K loop
       a.zero_from = S.separable ? lens(S.dw.step + 1) : g_lens;
       if (fuse) { a.x2 = blk_in; a.lens2 = lens(B.first_step); a.K1 = B.fused_k1; a.ldx2 = blk_ld; }
-      if ((a.res || fuse) && (blk_ld != gx_ld || (W.conv_cin && g_T != cur_T)))
+      if ((a.res || fuse || (nrm && last_sub && B.has_res)) && (blk_ld != gx_ld || (W.conv_cin && g_T != cur_T)))
         return fail(VASR_ERR_UNSUPPORTED, "block %zu: residual across a strided block", i);
       a.amax_x = gx_amax;
       a.amax_x2 = fuse ? blk_amax : AmaxTab{};
@@ -1185,6 +1341,15 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
         published = run_pointwise(h, a, W, st);
       }
       if (published < 0) return VASR_ERR_HIP;
+      // GroupNorm of the conv's output over its own lengths, then the activation (the last sub-layer's: after the residual
+      // sum, or after its SE); the normalized tensor's maxima replace the ones the GEMM published
+      if (nrm) {
+        const bool enc_out = last_block && last_sub;
+        if (run_norm(S.norm, dst, dst, (last_sub && B.has_res) ? R : nullptr, dst_ld, blk_ld, g_T, a.store_cols,
+                     lens(S.pw.step + 1), enc_out ? nullptr : lens(S.pw.step + 1), act, published ? &a.amax_y : nullptr,
+                     a.lens_y))
+          return VASR_ERR_HIP;
+      }
       // se and not residual: SE after the sub-layer, pooled over the conv's output lengths; the rescaled tensor's maxima
       // replace the ones the GEMM published
       if (S.se.d_w1) {
@@ -1383,12 +1548,22 @@ int vasr_set_block_groups(vasr_handle* h, int block, int groups, int heads) {
   return 0;
 }
 
+int vasr_set_block_norm(vasr_handle* h, int block, int norm_groups) {
+  if (!h) return fail(VASR_ERR_INVALID, "null handle");
+  if (h->finalized) return fail(VASR_ERR_STATE, "handle already finalized");
+  if (block < 0 || block >= (int)h->blocks.size()) return fail(VASR_ERR_INVALID, "block %d of %zu", block, h->blocks.size());
+  if (norm_groups < 0) return fail(VASR_ERR_INVALID, "norm_groups %d is negative", norm_groups);
+  h->blocks[block].norm_g = norm_groups;
+  return 0;
+}
+
 int vasr_finalize(vasr_handle* h) {
   if (!h) return fail(VASR_ERR_INVALID, "null handle");
   if (h->finalized) return 0;
   int rc;
   if (h->has_encoder && (rc = check_groups(h))) return rc;
   if (h->has_encoder && (rc = check_se(h))) return rc;
+  if (h->has_encoder && (rc = check_norm(h))) return rc;
   if (h->has_frontend && (rc = build_frontend(h))) return rc;
   if (h->has_encoder && (rc = build_encoder(h))) return rc;
   if (h->has_decoder && (rc = build_decoder(h))) return rc;
@@ -1972,6 +2147,46 @@ int vasr_bench_pointwise_bf16x3(const float* d_x, const uint16_t* d_w3, const fl
   const int e = launch_pointwise_split(a, 0, static_cast<hipStream_t>(stream));
   if (e) return fail(VASR_ERR_HIP, "pointwise GEMM: %s", hipGetErrorString((hipError_t)e));
   return check_launch("bench_pointwise_bf16x3");
+}
+
+int vasr_bench_groupnorm(const float* d_x, const int32_t* d_lens, int batch, int channels, int64_t frames, int norm_groups,
+                         int shuffle, const float* h_gamma, const float* h_beta, int relu, float* d_y, vasr_stream stream) {
+  if (!d_x || !d_lens || !d_y || !h_gamma || !h_beta || batch < 1 || frames < 1 || shuffle < 1 || channels % shuffle ||
+      !norm_supported(channels, norm_groups))
+    return fail(VASR_ERR_INVALID, "bad argument");
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t ld = pad_frames(frames);
+  std::vector<float> gs(channels), bs(channels);
+  std::vector<int32_t> group_of(channels), members(channels);
+  const std::vector<int> perm = shuffle_perm(channels, shuffle);
+  for (int p = 0; p < channels; ++p) {
+    const int o = perm[p];
+    gs[o] = h_gamma[p];
+    bs[o] = h_beta[p];
+    group_of[o] = p / (channels / norm_groups);
+    members[p] = o;
+  }
+  char* buf = nullptr;
+  const size_t nc = (size_t)channels, ws = (size_t)2 * batch * (channels + norm_groups);
+  HIP_TRY(hipMalloc(&buf, (4 * nc + ws) * 4));
+  float* f = reinterpret_cast<float*>(buf);
+  int32_t* i32 = reinterpret_cast<int32_t*>(buf);
+  NormLaunch a{};
+  a.x = d_x; a.y = d_y; a.add = nullptr; a.ld = ld; a.ld_add = ld; a.bs = 0;
+  a.channels = channels; a.groups = norm_groups; a.batch = batch; a.frames = (int)frames; a.store_cols = (int)ld;
+  a.lens = d_lens; a.gamma = f; a.beta = f + nc; a.group_of = i32 + 2 * nc; a.members = i32 + 3 * nc;
+  a.row_mean = f + 4 * nc; a.row_m2 = a.row_mean + (size_t)batch * channels;
+  a.g_mean = a.row_m2 + (size_t)batch * channels; a.g_rstd = a.g_mean + (size_t)batch * norm_groups;
+  a.zero_lens = d_lens; a.relu = relu;
+  hipError_t e = hipMemcpyAsync(buf, gs.data(), nc * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(buf + nc * 4, bs.data(), nc * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(buf + 2 * nc * 4, group_of.data(), nc * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(buf + 3 * nc * 4, members.data(), nc * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = (hipError_t)launch_norm(a, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(buf);
+  if (e != hipSuccess) return fail(VASR_ERR_HIP, "bench_groupnorm: %s", hipGetErrorString(e));
+  return 0;
 }
 
 #endif  // VASR_DEVTOOLS

@@ -276,6 +276,28 @@ struct SeLaunch {
 bool se_supported(int channels, int hidden);   // channels and hidden in [1, 1024]
 int launch_se(const SeLaunch& a, hipStream_t st);   // 0 or a hipError_t
 
+// ---- GroupNorm (encoder_norm.hip) ----
+// y[b][c][t] = act(gamma[c] * (x[b][c][t] - mu[b][g]) * rstd[b][g] + beta[c] (+ add[b][c][t])), g = group_of[c] (add: [B][channels][ld_add]); mu and the
+// biased variance over the channels of group g x t < min(lens[b], frames), rstd = 1 / sqrt(var + 1e-5).  Columns
+// t >= zero_lens[b] (nullptr: none) of the stored range [0, store_cols) are stored as 0, every column of a row with no frames.
+// x, y and add may alias.  members: [groups][channels / groups] the stored channels of each group in pre-shuffle order
+// (a grouped block stores its channels shuffled).  amax_y (optional): republished over t < lens_y[b] (nullptr: < frames).
+struct NormLaunch {
+  const float* x; float* y; const float* add;
+  int64_t ld, ld_add, bs;         // pitches of x / y and of add; batch stride of x / y in elements (0: channels * ld)
+  int channels, groups, batch, frames, store_cols;
+  const int32_t* lens;            // statistics length
+  const int32_t* group_of; const int32_t* members;   // [channels] each
+  const float* gamma; const float* beta;             // [channels], in stored order
+  float* row_mean; float* row_m2;                    // workspace, [batch][channels] each
+  float* g_mean; float* g_rstd;                      // workspace, [batch][groups] each
+  const int32_t* zero_lens;
+  int relu;
+  AmaxTab* amax_y; const int32_t* lens_y;
+};
+bool norm_supported(int channels, int groups);   // groups divides channels
+int launch_norm(const NormLaunch& a, hipStream_t st);   // 0 or a hipError_t
+
 // ---- CTC head / decode (decode.hip) ----
 // logits [B][ldm rows][ld] (row v, column t) -> logp [B][T][V] (optional), pred [B][T] (optional)
 void launch_logsoftmax_argmax(const float* logits, int64_t row_ld, int64_t batch_stride, int batch, int frames,

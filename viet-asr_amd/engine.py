@@ -82,6 +82,32 @@ def groups_from_config(jasper_cfg):
     return out
 
 
+NORM_MODES = ("batch", "group", "instance", "layer")
+
+
+def norm_from_config(enc_cfg, jasper_cfg):
+    """Per block of a YAML block list: the GroupNorm group count of JasperEncoder's ``normalization_mode`` / ``norm_groups``
+    (jasper.py:136-186, parts/jasper.py:342-391) -- 0 for "batch" (BatchNorm1d), ``norm_groups`` for "group" (-1, the
+    default: the block's filters), the filters for "instance", 1 for "layer" -- the argument of vasr_set_block_norm.
+    ValueError, as the reference raises: an unknown mode, or a group count that does not divide a block's filters."""
+    mode = enc_cfg.get("normalization_mode", "batch")
+    if mode not in NORM_MODES:
+        raise ValueError(f"Normalization method ({mode}) does not match one of [batch, layer, group, instance].")
+    if mode == "batch":
+        return [0] * len(jasper_cfg)
+    ng = enc_cfg.get("norm_groups", -1)
+    if mode == "group" and (int(ng) != ng or (ng != -1 and ng < 1)):
+        raise ValueError(f"norm_groups must be -1 or a positive integer, got {ng!r}")
+    out = []
+    for i, l in enumerate(jasper_cfg):
+        c = int(l["filters"])
+        g = {"instance": c, "layer": 1}.get(mode, c if ng == -1 else int(ng))
+        if c % g:
+            raise ValueError(f"block {i}: num_channels ({c}) must be divisible by num_groups ({g})")   # nn.GroupNorm
+        out.append(g)
+    return out
+
+
 def check_dense_layout(blocks, feat_in=None):
     """Raise ValueError for the dense-residual layouts the reference builds but cannot run (JasperBlock.forward indexes
     xs[p] for every copied pane, parts/jasper.py:428-436, and only a dense block WITH residual hands xs + [out] on,
@@ -134,10 +160,12 @@ class QuartzNetCTC:
         self._blocks = blocks_from_config(jas)
         self._se = se_from_config(jas)
         self._groups = groups_from_config(jas)
+        self._norm = norm_from_config(enc_cfg, jas)
         with torch.cuda.device(self.device):
             self.handle = _lib.Handle(frontend=self.frontend, feat_in=pre.get("features", 64),
                                       blocks=blocks_from_config(jas), dec_feat_in=jas[-1]["filters"],
-                                      num_classes=len(self.labels) + 1, se=self._se, groups=self._groups)
+                                      num_classes=len(self.labels) + 1, se=self._se, groups=self._groups,
+                                      norm=self._norm)
             self.handle.load_state_dict(encoder_state)
             self.handle.load_state_dict(decoder_state)
             self.handle.finalize()
@@ -290,6 +318,10 @@ class QuartzNetCTC:
         if any(self._se):
             # the halo windows assume a finite receptive field; an SE's time mean makes it the whole recording
             raise NotImplementedError("forward_long: a model with squeeze-and-excitation (se) has no finite receptive field")
+        if any(self._norm):
+            # GroupNorm's statistics span each row's whole length, like an SE's time mean
+            raise NotImplementedError("forward_long: a model with group, instance or layer normalization has no finite "
+                                      "receptive field")
         if wav.dim() != 1 or wav.device.type != "cuda" or wav.dtype != torch.float32:
             raise ValueError("wav must be a 1-D float32 cuda tensor")
         h = self.handle

@@ -63,8 +63,9 @@ def first(v):
     return v[0] if isinstance(v, (list, tuple)) else v
 
 
-def encoder_state_dict(jasper_cfg, feat_in, seed=0):
-    """numpy state_dict for JasperEncoder(jasper=jasper_cfg, feat_in=feat_in)."""
+def encoder_state_dict(jasper_cfg, feat_in, seed=0, norm=None):
+    """numpy state_dict for JasperEncoder(jasper=jasper_cfg, feat_in=feat_in).  norm: per block, the GroupNorm group count
+    (engine.norm_from_config; None or 0: BatchNorm)."""
     sd = {}
     cin = feat_in
     residual_panes = []    # JasperEncoder's shared list (jasper.py:152-161)
@@ -73,6 +74,7 @@ def encoder_state_dict(jasper_cfg, feat_in, seed=0):
         sep = l.get("separable", False)
         se = l.get("se_reduction_ratio", 16) if l.get("se", False) else 0
         groups, heads = int(l.get("groups", 1)), int(l.get("heads", -1))
+        nrm = _gn if norm and norm[i] else _bn
         c = cin
         j = 0
         for r in range(rep):
@@ -82,12 +84,12 @@ def encoder_state_dict(jasper_cfg, feat_in, seed=0):
                 sd[f"{p}.{j}.conv.weight"] = _conv_weight(f"{p}.{j}.conv.weight", seed, heads if heads != -1 else c, 1, k,
                                                           gain=G_MAIN)
                 sd[f"{p}.{j + 1}.conv.weight"] = _conv_weight(f"{p}.{j + 1}.conv.weight", seed, cout, c // groups, 1, gain=G_MAIN)
-                _bn(f"{p}.{j + 2}", seed, cout, sd)
+                nrm(f"{p}.{j + 2}", seed, cout, sd)
                 j += 3
             else:
                 sd[f"{p}.{j}.conv.weight"] = _conv_weight(f"{p}.{j}.conv.weight", seed, cout, c // groups, k,
                                                           gain=G_MAIN if k == 1 else G_CONV)
-                _bn(f"{p}.{j + 1}", seed, cout, sd)
+                nrm(f"{p}.{j + 1}", seed, cout, sd)
                 j += 2
             if groups > 1:
                 j += 1  # GroupShuffle slot
@@ -105,11 +107,18 @@ def encoder_state_dict(jasper_cfg, feat_in, seed=0):
             for q, ip in enumerate(panes):
                 p = f"encoder.{i}.res.{q}"
                 sd[f"{p}.0.conv.weight"] = _conv_weight(f"{p}.0.conv.weight", seed, cout, ip, 1, gain=G_RES / np.sqrt(len(panes)))
-                _bn(f"{p}.1", seed, cout, sd)
+                nrm(f"{p}.1", seed, cout, sd)
                 if se:
                     _se(f"{p}.2", seed, cout, se, sd)
         cin = cout
     return sd
+
+
+def _gn(prefix, seed, c, out):
+    """GroupNorm weight / bias [c] (no running statistics), from streams of their own: the BatchNorm draws of a model
+    without GroupNorm are what they were."""
+    out[prefix + ".weight"] = _rs(prefix + ".gn.weight", seed).uniform(0.8, 1.2, size=c).astype(np.float32)
+    out[prefix + ".bias"] = _rs(prefix + ".gn.bias", seed).normal(0.0, 0.2, size=c).astype(np.float32)
 
 
 def _se(prefix, seed, c, ratio, sd):
