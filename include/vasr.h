@@ -164,6 +164,23 @@ VASR_API int vasr_set_block_groups(vasr_handle* h, int block, int groups, int he
  * layout change.) */
 VASR_API int vasr_set_block_norm(vasr_handle* h, int block, int norm_groups);
 
+/* JasperEncoder's activation and residual_mode (jasper.py:136-190, parts/jasper.py:21-25, :428-448), one setting for the
+ * whole encoder as in the reference, which builds ONE activation module and hands it to every block.  activation: 0 = ReLU
+ * (the default), 1 = nn.Hardtanh() with its defaults, clamp(x, -1, 1), 2 = nn.SELU(): lambda * x for x > 0, else
+ * lambda * alpha * expm1(x), lambda = 1.0507009873554804934193349852946, alpha = 1.6732632423543772848170429916717.  It
+ * takes the place of ReLU everywhere the block applies one: after every sub-layer but the last (conv -> norm -> [shuffle]
+ * -> act -> [SE]) and on the block output act(combine(main, residual panes)).  SqueezeExcite's inner ReLU stays a ReLU
+ * whatever the activation (parts/jasper.py:152-168).  residual_mode: 0 = "add" (the default), out + res_p for each pane
+ * in turn; 1 = max, out = max(out, res_p) -- the reference treats every residual_mode other than "add" so, and the Python
+ * layer maps them here.  Max is taken with fmaxf: a NaN operand yields the other one (torch.max propagates NaN); the two
+ * agree wherever no NaN is present.  Between vasr_create and vasr_finalize.  Codes out of range: VASR_ERR_INVALID.
+ * vasr_finalize refuses residual_mode max together with any GroupNorm block (vasr_set_block_norm) with
+ * VASR_ERR_UNSUPPORTED, before it touches a device.  What runs where: a max residual is never folded into the main GEMM
+ * (its residual GEMM stores R and the main GEMM's epilogue takes the maximum), and a dense residual runs one GEMM per pane,
+ * each combined into R by max.  Non-ReLU activations and max residuals take epilogue variants of the same kernels; ReLU / add
+ * models run exactly the kernels they ran before.  (ABI 8: a function, no layout change.) */
+VASR_API int vasr_set_activation(vasr_handle* h, int activation, int residual_mode);
+
 /* Checks that every tensor arrived, folds eval-mode BatchNorm1d(eps=1e-3)
  * (parts/jasper.py:392) into per-channel (scale, shift), packs the 1x1-conv weights
  * K-major for the MFMA kernels and uploads everything.  Needed before any compute call. */

@@ -68,6 +68,7 @@ SIGNATURES = {
     "vasr_set_busy_cus": (C.c_int, [_P, C.c_int]),
     "vasr_set_block_se": (C.c_int, [_P, C.c_int, C.c_int]),
     "vasr_set_block_norm": (C.c_int, [_P, C.c_int, C.c_int]),
+    "vasr_set_activation": (C.c_int, [_P, C.c_int, C.c_int]),
     "vasr_set_block_groups": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     "vasr_beam_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
     "vasr_beam_search_f32": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P,
@@ -171,10 +172,12 @@ def _fptr(a):
 class Handle:
     """Owns one vasr_handle: any subset of {front end, encoder, CTC head}."""
 
-    def __init__(self, frontend=None, feat_in=0, blocks=None, dec_feat_in=0, num_classes=0, se=None, groups=None, norm=None):
+    def __init__(self, frontend=None, feat_in=0, blocks=None, dec_feat_in=0, num_classes=0, se=None, groups=None, norm=None,
+                 activation=0, residual_mode=0):
         """se: per block, the squeeze-and-excitation reduction ratio (0 = none; engine.se_from_config).  groups: per block,
         (groups, heads) (engine.groups_from_config; (1, -1) = none).  norm: per block, the GroupNorm group count (0 =
-        BatchNorm; engine.norm_from_config)."""
+        BatchNorm; engine.norm_from_config).  activation (0 relu, 1 hardtanh, 2 selu), residual_mode (0 add, 1 max): the
+        encoder's, engine.activation_from_config; codes out of range raise ValueError."""
         L = lib()
         self._keep = []
         md = ModelDesc()
@@ -217,6 +220,8 @@ class Handle:
         for i, g in enumerate(norm or []):
             if g:
                 check(L.vasr_set_block_norm(h, i, int(g)))
+        if activation or residual_mode:
+            check(L.vasr_set_activation(h, int(activation), int(residual_mode)))
         self.num_classes = int(num_classes)
 
     def load_state_dict(self, sd):

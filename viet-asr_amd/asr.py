@@ -16,7 +16,8 @@ from . import _lib, stages
 from .core import (AcousticEncodedRepresentation, AudioSignal, DataLayerNM, DeviceType, LengthsType,
                    LogprobsType, MelSpectrogramType, NeuralType, NonTrainableNM, PredictionsType,
                    SpectrogramType, TrainableNM)
-from .engine import blocks_from_config, check_dense_layout, norm_from_config, groups_from_config, se_from_config
+from .engine import (activation_from_config, blocks_from_config, check_dense_layout, norm_from_config, groups_from_config,
+                     se_from_config)
 from .frontend_tables import frontend_description
 
 __all__ = ["AudioToMelSpectrogramPreprocessor", "JasperEncoder", "JasperDecoderForCTC", "GreedyCTCDecoder",
@@ -198,10 +199,12 @@ class JasperEncoder(_HipWeights, TrainableNM):
     def __init__(self, jasper, activation, feat_in, normalization_mode="batch", residual_mode="add", norm_groups=-1,
                  conv_mask=True, frame_splicing=1, init_mode="xavier_uniform"):
         super().__init__()
-        if activation not in ("hardtanh", "relu", "selu"):
-            raise KeyError(activation)
-        if activation != "relu" or residual_mode != "add" or not conv_mask or frame_splicing != 1:
-            raise NotImplementedError("implemented: activation='relu', residual_mode='add', conv_mask=True, frame_splicing=1")
+        # one activation for every block, as the reference's one module (jasper.py:150); unknown names: KeyError
+        self._act, self._res_mode = activation_from_config(dict(activation=activation, residual_mode=residual_mode))
+        if not conv_mask or frame_splicing != 1:
+            raise NotImplementedError("implemented: conv_mask=True, frame_splicing=1")
+        if self._res_mode and normalization_mode != "batch":
+            raise NotImplementedError("residual_mode='max' with group, instance or layer normalization is not implemented")
         self._blocks = blocks_from_config(jasper)
         # (unknown modes and group counts that do not divide a block's filters: ValueError, as the reference raises)
         self._norm = norm_from_config(dict(normalization_mode=normalization_mode, norm_groups=norm_groups), jasper)
@@ -232,7 +235,8 @@ class JasperEncoder(_HipWeights, TrainableNM):
         if self._handle is None:
             if not torch.cuda.is_available():
                 raise _no_gpu()
-            h = _lib.Handle(feat_in=self._feat_in, blocks=self._blocks, se=self._se, groups=self._groups, norm=self._norm)
+            h = _lib.Handle(feat_in=self._feat_in, blocks=self._blocks, se=self._se, groups=self._groups, norm=self._norm,
+                            activation=self._act, residual_mode=self._res_mode)
             h.load_state_dict(self.state_dict())
             h.finalize()
             self._handle = h

@@ -112,7 +112,8 @@ struct FusedArgs {
   float* y;                  // [B][256][ldy]
   int64_t ldy;
   int32_t frames;            // valid columns
-  int32_t relu;
+  int32_t relu;              // apply the activation act (kAct*)
+  int32_t act;
   AmaxTab amax_y;
   const int32_t* lens_y;
   // residual source (DUAL): K range [256, 512) = masked block input
@@ -143,7 +144,8 @@ __device__ __forceinline__ int bimg_slot(int n, int kh) { return (n & ~15) | ((n
 template <int BN>
 __device__ __forceinline__ constexpr int bimg_off(int buf, int plane, int ks) { return (((buf * 2 + plane) * 4 + ks) * 2) * BN * 16; }
 
-template <int K, bool DUAL, int BN>
+// EPI: epilogue_kind (vasr_internal.h): 0 = ReLU as a maximum with a uniform floor, 1 = Hardtanh as a clamp, 2 = SELU
+template <int K, bool DUAL, int BN, int EPI = 0>
 __global__ __launch_bounds__(FNT, 1) void dwpw_fused_kernel(FusedArgs a, int tiles_t, int n_blocks) {
   using G = FGeom<K, BN>;
   using TL = FTile<BN>;
@@ -282,6 +284,8 @@ __global__ __launch_bounds__(FNT, 1) void dwpw_fused_kernel(FusedArgs a, int til
     const int ylen = a.amax_y.p ? (a.lens_y ? a.lens_y[b] : a.frames) : 0;
     unsigned ymax = 0;
     const float relu_floor = (a.relu & 1) ? 0.f : -__builtin_inff();
+    float act_lo = 0.f, act_hi = 0.f;
+    if constexpr (EPI == 1) clamp_bounds(a.relu, a.act, act_lo, act_hi);
     float* stage = reinterpret_cast<float*>(wins + wave * kWWave);   // 2 x 8 rows x BN columns = 8 KB of 13 KB (4 of 9)
     // every pass's BN scale / shift BEFORE the first store: stores count in vmcnt like loads, so a load issued between
     // two passes makes its consumer wait (vmcnt(0)) for every store before it -- eight store round trips in series
@@ -319,7 +323,17 @@ __global__ __launch_bounds__(FNT, 1) void dwpw_fused_kernel(FusedArgs a, int til
         for (int k = 0; k < NT; ++k) {
           const int f = lane + 64 * k, row = f / (BN / 4), c4 = f % (BN / 4);
           const int m = mq + row, t = t0 + 4 * c4;
-          const v4f v = __builtin_elementwise_max(pv[k], v4f{relu_floor, relu_floor, relu_floor, relu_floor});
+          v4f v;
+          if constexpr (EPI == 1) {
+            v = __builtin_elementwise_min(__builtin_elementwise_max(pv[k], v4f{act_lo, act_lo, act_lo, act_lo}),
+                                          v4f{act_hi, act_hi, act_hi, act_hi});
+          } else if constexpr (EPI == 2) {
+            v = pv[k];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = selu(v[e]);
+          } else {
+            v = __builtin_elementwise_max(pv[k], v4f{relu_floor, relu_floor, relu_floor, relu_floor});
+          }
           *reinterpret_cast<v4f*>(a.y + ((int64_t)b * FC + m) * a.ldy + t) = v;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
@@ -506,9 +520,11 @@ int launch_fused_t(const FusedArgs& a, hipStream_t st, int* amax_n) {
     if (tiles_t * 4 > a.amax_y.stride) return (int)hipErrorInvalidValue;
     if (amax_n) *amax_n = tiles_t * 4;
   }
-  auto kern = dwpw_fused_kernel<K, DUAL, BN>;
-  static std::atomic<uint64_t> lds_opted{0};   // per device (dyn_lds_opt_in)
-  const hipError_t attr = dyn_lds_opt_in(reinterpret_cast<const void*>(kern), (int)G::LDS, lds_opted);
+  // Hardtanh and SELU take epilogue 1 or 2 (only add-mode residuals reach this kernel); the ReLU kernels stay as they were
+  const int epi = epilogue_kind(a.relu, a.act, false);
+  auto kern = epi == 2 ? dwpw_fused_kernel<K, DUAL, BN, 2> : epi == 1 ? dwpw_fused_kernel<K, DUAL, BN, 1> : dwpw_fused_kernel<K, DUAL, BN, 0>;
+  static std::atomic<uint64_t> lds_opted[3];   // per device and epilogue (dyn_lds_opt_in)
+  const hipError_t attr = dyn_lds_opt_in(reinterpret_cast<const void*>(kern), (int)G::LDS, lds_opted[epi]);
   if (attr != hipSuccess) return (int)attr;
   VASR_LAUNCH(kern, dim3(n_blocks), dim3(FNT), G::LDS, st, a, tiles_t, n_blocks);
   return 0;
@@ -542,7 +558,7 @@ int launch_fused_dwpw(const FusedLaunch& f, hipStream_t st, int* amax_n) {
   FusedArgs a{};
   a.x = f.x; a.ldx = f.ldx; a.lens_in = f.lens_in; a.lens_out = f.lens_out; a.taps = f.taps; a.dw_l1 = f.dw_l1;
   a.amax_x = f.amax_x; a.wt = reinterpret_cast<const uint4*>(f.wt); a.w_inv_scale = f.w_inv_scale; a.scale = f.scale;
-  a.shift = f.shift; a.y = f.y; a.ldy = f.ldy; a.frames = f.frames; a.relu = f.relu; a.amax_y = f.amax_y;
+  a.shift = f.shift; a.y = f.y; a.ldy = f.ldy; a.frames = f.frames; a.relu = f.relu; a.act = f.act; a.amax_y = f.amax_y;
   a.lens_y = f.lens_y; a.x2 = f.x2; a.ldx2 = f.ldx2; a.lens2 = f.lens2; a.amax_x2 = f.amax_x2; a.batch = f.batch;
   const bool dual = f.x2 != nullptr;
   if (f.tile_cols == 64) {

@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const float* x, float* 
                                                          const int32_t* __restrict__ group_of, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, const float* __restrict__ g_mean,
                                                          const float* __restrict__ g_rstd,
-                                                         const int32_t* __restrict__ zero_lens, int relu,
+                                                         const int32_t* __restrict__ zero_lens, int relu, int act,
                                                          unsigned* __restrict__ amax, int amax_stride,
                                                          const int32_t* __restrict__ lens_y) {
   const int b = blockIdx.y;
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const float* x, float* 
       if (t < zl) {
         v = fmaf(xr[t] - mu, a, be);
         if (ar) v += ar[t];
-        if (relu) v = v > 0.f ? v : 0.f;
+        if (relu) v = activate(v, act);
       }
       yr[t] = v;
       if (t < ny) m = max(m, abs_bits(v));
@@ -150,7 +150,7 @@ int launch_norm(const NormLaunch& a, hipStream_t st) {
   if (tab) a.amax_y->n = gx * 4;
   VASR_LAUNCH_PART(false, true, norm_apply_kernel, dim3(gx, a.batch), dim3(256), 0, st, a.x, a.y, a.add, a.ld, bs,
                    a.add ? a.ld_add : a.ld, a.channels, a.groups, a.store_cols, a.frames, a.lens, a.group_of, a.gamma, a.beta, a.g_mean, a.g_rstd,
-                   a.zero_lens, a.relu, tab, a.amax_y ? a.amax_y->stride : 0, a.lens_y);
+                   a.zero_lens, a.relu, a.act, tab, a.amax_y ? a.amax_y->stride : 0, a.lens_y);
   return (int)hipGetLastError();
 }
 

@@ -30,6 +30,7 @@
 #include <cstdlib>
 
 #include "vasr_internal.h"
+#include "vasr_device.h"
 
 namespace vasr {
 
@@ -55,7 +56,8 @@ struct PwGeom {
 // DUAL: the reduction runs over two activation tensors back to back -- rows [0, K1) from a.x, rows [K1, K)
 // from a.x2 (masked with a.lens2).  Used to fold a JasperBlock's residual 1x1 conv into its last sub-block's GEMM
 // (weights [s1*W1 | s2*W2] concatenated along K, shift h1 + h2), which removes the residual tensor round trip.
-template <int WM, int TM, bool MASK, bool RES, bool DUAL, bool CONV = false>
+// EPI: epilogue_kind (vasr_internal.h), as encoder_pw_split.hip's
+template <int WM, int TM, bool MASK, bool RES, bool DUAL, bool CONV = false, int EPI = 0>
 __global__ __launch_bounds__(512, 4) void pw_gemm_kernel(PwArgs a, int blocks_m, int tiles_t, int n_blocks) {
   using G = PwGeom<WM, TM>;
   __shared__ v4f Bs4[2][kChunkFloats / 4];
@@ -178,10 +180,12 @@ __global__ __launch_bounds__(512, 4) void pw_gemm_kernel(PwArgs a, int blocks_m,
     }
   }
 
-  // ---- epilogue: BN affine (+ residual) + ReLU; each half-wave writes 128-byte row segments ----
+  // ---- epilogue: BN affine (+ residual) + activation; each half-wave writes 128-byte row segments ----
   // C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
   if (a.relu & 2) return;  // debug: skip the epilogue (tools/bench_layers.py ablation)
   const bool full = (t0 + G::BN <= a.store_cols) && (m0 + G::BM <= a.m_store);
+  float act_lo = 0.f, act_hi = 0.f;
+  if constexpr (EPI == 1) clamp_bounds(a.relu, a.act, act_lo, act_hi);
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -196,8 +200,16 @@ __global__ __launch_bounds__(512, 4) void pw_gemm_kernel(PwArgs a, int blocks_m,
         for (int j = 0; j < 2; ++j) {
           const int t = t0 + wn + j * 32 + l31;
           float v = fmaf(acc[i][j][4 * q + rr], sc[rr], sh[rr]);
-          if (RES) v += a.res[((int64_t)b * a.M + m) * a.ldr + t];
-          if (a.relu & 1) v = fmaxf(v, 0.f);
+          if constexpr (EPI != 0) {
+            if (RES) {   // (res may be y: this thread reads the element before it stores it)
+              const float r = a.res[((int64_t)b * a.M + m) * a.ldr + t];
+              v = a.res_max ? fmaxf(v, r) : v + r;
+            }
+            v = EPI == 1 ? fminf(fmaxf(v, act_lo), act_hi) : selu(v);
+          } else {
+            if (RES) v += a.res[((int64_t)b * a.M + m) * a.ldr + t];
+            if (a.relu & 1) v = fmaxf(v, 0.f);
+          }
           if (full || (t < a.store_cols && m < a.m_store)) a.y[((int64_t)b * a.m_store + m) * a.ldy + t] = v;
         }
       }
@@ -205,21 +217,31 @@ __global__ __launch_bounds__(512, 4) void pw_gemm_kernel(PwArgs a, int blocks_m,
   }
 }
 
-template <int WM, int TM>
-void launch_t(const PwArgs& a, hipStream_t st) {
+template <int WM, int TM, int EPI>
+void launch_g(const PwArgs& a, hipStream_t st) {
   using G = PwGeom<WM, TM>;
   const int blocks_m = a.M / G::BM;
   const int tiles_t = (int)(((a.conv_cin ? a.conv_cols : a.ldx) + G::BN - 1) / G::BN);
   const int n_blocks = blocks_m * tiles_t * a.batch;
   dim3 grid(n_blocks), block(512);
   const bool mask = a.lens != nullptr, res = a.res != nullptr, dual = a.x2 != nullptr;
-  if (a.conv_cin && res) VASR_LAUNCH((pw_gemm_kernel<WM, TM, true, true, false, true>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
-  else if (a.conv_cin) VASR_LAUNCH((pw_gemm_kernel<WM, TM, true, false, false, true>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
-  else if (dual) VASR_LAUNCH((pw_gemm_kernel<WM, TM, false, false, true>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
-  else if (mask && res) VASR_LAUNCH((pw_gemm_kernel<WM, TM, true, true, false>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
-  else if (mask) VASR_LAUNCH((pw_gemm_kernel<WM, TM, true, false, false>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
-  else if (res) VASR_LAUNCH((pw_gemm_kernel<WM, TM, false, true, false>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
-  else VASR_LAUNCH((pw_gemm_kernel<WM, TM, false, false, false>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
+  if (a.conv_cin && res) VASR_LAUNCH((pw_gemm_kernel<WM, TM, true, true, false, true, EPI>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
+  else if (a.conv_cin) VASR_LAUNCH((pw_gemm_kernel<WM, TM, true, false, false, true, EPI>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
+  else if (dual) VASR_LAUNCH((pw_gemm_kernel<WM, TM, false, false, true, false, EPI>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
+  else if (mask && res) VASR_LAUNCH((pw_gemm_kernel<WM, TM, true, true, false, false, EPI>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
+  else if (mask) VASR_LAUNCH((pw_gemm_kernel<WM, TM, true, false, false, false, EPI>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
+  else if (res) VASR_LAUNCH((pw_gemm_kernel<WM, TM, false, true, false, false, EPI>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
+  else VASR_LAUNCH((pw_gemm_kernel<WM, TM, false, false, false, false, EPI>), grid, block, 0, st, a, blocks_m, tiles_t, n_blocks);
+}
+
+template <int WM, int TM>
+void launch_t(const PwArgs& a, hipStream_t st) {
+  // every activation but ReLU and a max residual take epilogue 1 or 2; the ReLU / add kernels stay as they were
+  switch (epilogue_kind(a.relu, a.act, a.res && a.res_max)) {
+    case 2: launch_g<WM, TM, 2>(a, st); break;
+    case 1: launch_g<WM, TM, 1>(a, st); break;
+    default: launch_g<WM, TM, 0>(a, st);
+  }
 }
 
 }  // namespace

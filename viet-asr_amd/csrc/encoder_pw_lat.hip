@@ -48,7 +48,8 @@ __device__ __forceinline__ void wave_fence() {
 // multipliers, which run its 16 k-steps while the next items are still arriving.  The roles keep the two request streams
 // on different wavefronts: s_waitcnt counts in order, and a multiplier that waited for its next weight fragments would
 // otherwise wait for every row requested before them.
-template <int KS, bool DUAL, bool RES>
+// EPI: epilogue_kind (vasr_internal.h), as pw_gemm_split_kernel's
+template <int KS, bool DUAL, bool RES, int EPI = 0>
 __global__ __launch_bounds__(LNT, 1) void pw_gemm_latency_kernel(PwArgs a, int blocks_m, int tiles_t, int n_blocks) {
   constexpr int PI = KS / 16;          // items per staging thread = phases
   constexpr int SPH = 16;              // k-steps per phase
@@ -202,7 +203,7 @@ __global__ __launch_bounds__(LNT, 1) void pw_gemm_latency_kernel(PwArgs a, int b
     __syncthreads();   // the epilogue reuses the LDS image
   }
 
-  // ---- epilogue: BN affine (+ residual) + ReLU, as pw_gemm_split_kernel with TM = TN = 1 ----
+  // ---- epilogue: BN affine (+ residual) + activation, as pw_gemm_split_kernel with TM = TN = 1 ----
   if (a.relu & 2) return;
   const int ylen = a.amax_y.p ? (a.lens_y ? a.lens_y[b] : a.frames) : 0;
   unsigned ymax = 0;
@@ -211,6 +212,8 @@ __global__ __launch_bounds__(LNT, 1) void pw_gemm_latency_kernel(PwArgs a, int b
     ymax = (t < ylen && u > ymax) ? u : ymax;
   };
   const float relu_floor = (a.relu & 1) ? 0.f : -__builtin_inff();
+  float act_lo = 0.f, act_hi = 0.f;
+  if constexpr (EPI == 1) clamp_bounds(a.relu, a.act, act_lo, act_hi);
   if (vec) {
     float* stage = reinterpret_cast<float*>(Bl) + wave * (2 * 8 * LBN);
     const int row = erow, c4 = ec4;
@@ -226,8 +229,19 @@ __global__ __launch_bounds__(LNT, 1) void pw_gemm_latency_kernel(PwArgs a, int b
       }
       wave_fence();
       v4f v = *reinterpret_cast<const v4f*>(buf + row * LBN + 4 * c4);
-      if (RES) v += rv[q];
-      v = __builtin_elementwise_max(v, v4f{relu_floor, relu_floor, relu_floor, relu_floor});
+      if constexpr (EPI != 0) {
+        if (RES) v = a.res_max ? __builtin_elementwise_max(v, rv[q]) : v + rv[q];
+        if constexpr (EPI == 1) {
+          v = __builtin_elementwise_min(__builtin_elementwise_max(v, v4f{act_lo, act_lo, act_lo, act_lo}),
+                                        v4f{act_hi, act_hi, act_hi, act_hi});
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = selu(v[e]);
+        }
+      } else {
+        if (RES) v += rv[q];
+        v = __builtin_elementwise_max(v, v4f{relu_floor, relu_floor, relu_floor, relu_floor});
+      }
       const int m = mq + row, t = t0 + 4 * c4;
       *reinterpret_cast<v4f*>(a.y + ((int64_t)b * a.m_store + m) * a.ldy + t) = v;
 #pragma unroll
@@ -243,8 +257,16 @@ __global__ __launch_bounds__(LNT, 1) void pw_gemm_latency_kernel(PwArgs a, int b
         const int m = mq + rr, t = t0 + l31;
         float v = acc[4 * q + rr] * out_scale;
         v = fmaf(v, sc[rr], sh[rr]);
-        if (RES) v += a.res[((int64_t)b * a.M + m) * a.ldr + t];
-        if (a.relu & 1) v = fmaxf(v, 0.f);
+        if constexpr (EPI != 0) {
+          if (RES) {
+            const float r = a.res[((int64_t)b * a.M + m) * a.ldr + t];
+            v = a.res_max ? fmaxf(v, r) : v + r;
+          }
+          v = EPI == 1 ? fminf(fmaxf(v, act_lo), act_hi) : selu(v);
+        } else {
+          if (RES) v += a.res[((int64_t)b * a.M + m) * a.ldr + t];
+          if (a.relu & 1) v = fmaxf(v, 0.f);
+        }
         if (full || (t < a.store_cols && m < a.m_store)) {
           a.y[((int64_t)b * a.m_store + m) * a.ldy + t] = v;
           if (a.amax_y.p) track(v, t);
@@ -266,9 +288,12 @@ int launch_lat_k(const PwArgs& a, hipStream_t st, int* amax_n) {
     if (amax_n) *amax_n = n;
   }
   constexpr size_t lds = (size_t)2 * KS * 2 * LBN * sizeof(uint4);   // >= the epilogue's 4 x 2 KB for every KS
-  auto kern = pw_gemm_latency_kernel<KS, DUAL, RES>;
-  static std::atomic<uint64_t> lds_opted{0};   // per device (dyn_lds_opt_in)
-  const hipError_t attr = dyn_lds_opt_in(reinterpret_cast<const void*>(kern), (int)lds, lds_opted);
+  // every activation but ReLU and a max residual take epilogue 1 or 2; the ReLU / add kernels stay as they were
+  const int epi = epilogue_kind(a.relu, a.act, RES && a.res_max);
+  auto kern = epi == 2 ? pw_gemm_latency_kernel<KS, DUAL, RES, 2>
+              : epi == 1 ? pw_gemm_latency_kernel<KS, DUAL, RES, 1> : pw_gemm_latency_kernel<KS, DUAL, RES, 0>;
+  static std::atomic<uint64_t> lds_opted[3];   // per device and epilogue (dyn_lds_opt_in)
+  const hipError_t attr = dyn_lds_opt_in(reinterpret_cast<const void*>(kern), (int)lds, lds_opted[epi]);
   if (attr != hipSuccess) return (int)attr;
   VASR_LAUNCH(kern, dim3(n_blocks), dim3(LNT), lds, st, a, blocks_m, tiles_t, n_blocks);
   return 0;

@@ -139,7 +139,9 @@ struct Geom {
   static_assert(PATCHES % NT == 0 && PPT >= 1, "staging patches must divide evenly over the threads");
 };
 
-template <int NW, int TM, int TN, bool MASK, bool RES, bool DUAL, int ARITH, bool CONV = false, bool GRP = false>
+// EPI (epilogue_kind, vasr_internal.h): 0 = the ReLU / add epilogue (relu flag: ReLU or nothing) the default models run;
+// 1 = a clamp to uniform bounds, 2 = SELU, both with the residual added or (a.res_max) combined by max.
+template <int NW, int TM, int TN, bool MASK, bool RES, bool DUAL, int ARITH, bool CONV = false, bool GRP = false, int EPI = 0>
 __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int blocks_m, int tiles_t, int n_blocks) {
   using G = Geom<NW, TM, TN, ARITH>;
   constexpr int BM = G::BM, BN = G::BN, NT = G::NT, PPT = G::PPT, PL = G::PL, PLW = G::PLW;
@@ -444,7 +446,7 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
     }
   }
 
-  // ---- epilogue (as encoder_pw.hip): BN affine (+ residual) + ReLU, 128-byte row segments per half-wave ----
+  // ---- epilogue (as encoder_pw.hip): BN affine (+ residual) + activation, 128-byte row segments per half-wave ----
   // max |y| over the utterance's VALID output frames, for the split of the next kF16x2 consumer of y
   const int ylen = a.amax_y.p ? (a.lens_y ? a.lens_y[b] : a.frames) : 0;
   unsigned ymax = 0;
@@ -453,6 +455,8 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
     ymax = (t < ylen && u > ymax) ? u : ymax;
   };
   const float relu_floor = (a.relu & 1) ? 0.f : -__builtin_inff();   // max(v, floor): ReLU or nothing, without a branch
+  float act_lo = 0.f, act_hi = 0.f;
+  if constexpr (EPI == 1) clamp_bounds(a.relu, a.act, act_lo, act_hi);
   // GRP: pre-shuffle row m = grp * mg + j is stored at row j * G + grp (GroupShuffle); otherwise at m
   auto orow = [&](int m) { return GRP ? (m - grp * mg) * ng + grp : m; };
   const bool full = (t0 + BN <= a.store_cols) && (m0 + BM <= a.m_store);
@@ -509,8 +513,19 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
           const int f = lane + 64 * k, row = f / (BN / 4), c4 = f % (BN / 4);
           const int m = mq + row, t = t0 + 4 * c4;
           v4f v = pv[k];
-          if (RES) v += rv[k];
-          v = __builtin_elementwise_max(v, v4f{relu_floor, relu_floor, relu_floor, relu_floor});
+          if constexpr (EPI != 0) {
+            if (RES) v = a.res_max ? __builtin_elementwise_max(v, rv[k]) : v + rv[k];   // (a uniform select)
+            if constexpr (EPI == 1) {
+              v = __builtin_elementwise_min(__builtin_elementwise_max(v, v4f{act_lo, act_lo, act_lo, act_lo}),
+                                            v4f{act_hi, act_hi, act_hi, act_hi});
+            } else {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) v[e] = selu(v[e]);
+            }
+          } else {
+            if (RES) v += rv[k];
+            v = __builtin_elementwise_max(v, v4f{relu_floor, relu_floor, relu_floor, relu_floor});
+          }
           v4f* dstp = reinterpret_cast<v4f*>(a.y + ((int64_t)b * a.m_store + orow(m)) * a.ldy + t);
           *dstp = v;   // (non-temporal stores for outputs beyond the Infinity Cache: measured, no gain)
 #pragma unroll
@@ -535,8 +550,16 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
             float v = acc[i][j][4 * q + rr];
             if constexpr (ARITH == kF16x2) v *= out_scale;
             v = fmaf(v, sc[rr], sh[rr]);
-            if (RES) v += a.res[((int64_t)b * a.M + orow(m)) * a.ldr + t];
-            if (a.relu & 1) v = fmaxf(v, 0.f);
+            if constexpr (EPI != 0) {
+              if (RES) {
+                const float r = a.res[((int64_t)b * a.M + orow(m)) * a.ldr + t];
+                v = a.res_max ? fmaxf(v, r) : v + r;
+              }
+              v = EPI == 1 ? fminf(fmaxf(v, act_lo), act_hi) : selu(v);
+            } else {
+              if (RES) v += a.res[((int64_t)b * a.M + orow(m)) * a.ldr + t];
+              if (a.relu & 1) v = fmaxf(v, 0.f);
+            }
             if (full || (t < a.store_cols && m < a.m_store)) {
               a.y[((int64_t)b * a.m_store + orow(m)) * a.ldy + t] = v;
               if (a.amax_y.p) track(v, t);
@@ -551,6 +574,8 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
 
 template <int NW, int TM, int TN, bool MASK, bool RES, bool DUAL, int ARITH, bool CONV = false, bool GRP = false>
 int launch_k(const PwArgs& a, hipStream_t st, int* amax_n) {
+  // every activation but ReLU and a max residual take epilogue 1 or 2; the ReLU / add kernels stay as they were
+  const int epi = epilogue_kind(a.relu, a.act, RES && a.res_max);
   using G = Geom<NW, TM, TN, ARITH>;
   const int blocks_m = a.M / G::BM;
   const int tiles_t = (int)(((CONV ? a.conv_cols : a.ldx) + G::BN - 1) / G::BN);
@@ -561,9 +586,11 @@ int launch_k(const PwArgs& a, hipStream_t st, int* amax_n) {
     if (amax_n) *amax_n = n;
   }
   if (GRP && (a.groups < 2 || a.M % a.groups || (a.M / a.groups) % G::BM || a.m_store != a.M)) return (int)hipErrorInvalidValue;
-  auto kern = pw_gemm_split_kernel<NW, TM, TN, MASK, RES, DUAL, ARITH, CONV, GRP>;
-  static std::atomic<uint64_t> lds_opted{0};   // per device (dyn_lds_opt_in)
-  const hipError_t attr = dyn_lds_opt_in(reinterpret_cast<const void*>(kern), (int)G::LDS, lds_opted);
+  auto kern = epi == 2 ? pw_gemm_split_kernel<NW, TM, TN, MASK, RES, DUAL, ARITH, CONV, GRP, 2>
+              : epi == 1 ? pw_gemm_split_kernel<NW, TM, TN, MASK, RES, DUAL, ARITH, CONV, GRP, 1>
+                         : pw_gemm_split_kernel<NW, TM, TN, MASK, RES, DUAL, ARITH, CONV, GRP, 0>;
+  static std::atomic<uint64_t> lds_opted[3];   // per device and epilogue (dyn_lds_opt_in)
+  const hipError_t attr = dyn_lds_opt_in(reinterpret_cast<const void*>(kern), (int)G::LDS, lds_opted[epi]);
   if (attr != hipSuccess) return (int)attr;
   VASR_LAUNCH(kern, dim3(n_blocks), dim3(G::NT), G::LDS, st, a, blocks_m, tiles_t, n_blocks);
   return 0;

@@ -69,10 +69,11 @@ __global__ __launch_bounds__(256) void se_mlp_kernel(const float* __restrict__ s
   }
 }
 
-// x and y may be the same tensor (in place); accumulate: y += x * s instead of y = x * s
+// x and y may be the same tensor (in place); accumulate 1: y += x * s, 2: y = max(y, x * s) (residual_mode "max"), instead
+// of y = x * s
 __global__ __launch_bounds__(256) void se_scale_kernel(const float* x, float* y, int64_t ld, int64_t bs, int channels,
                                                        int store_cols, const float* __restrict__ scale,
-                                                       const int32_t* __restrict__ zero_lens, int relu, int accumulate,
+                                                       const int32_t* __restrict__ zero_lens, int relu, int act, int accumulate,
                                                        unsigned* __restrict__ amax, int amax_stride,
                                                        const int32_t* __restrict__ lens_y, int frames) {
   const int b = blockIdx.y;
@@ -89,8 +90,9 @@ __global__ __launch_bounds__(256) void se_scale_kernel(const float* x, float* y,
       float v = 0.f;
       if (t < zl) {
         v = xr[t] * s;
-        if (accumulate) v += yr[t];
-        if (relu) v = v > 0.f ? v : 0.f;
+        if (accumulate == 2) v = fmaxf(v, yr[t]);
+        else if (accumulate) v += yr[t];
+        if (relu) v = activate(v, act);
       }
       yr[t] = v;
       if (t < ny) m = max(m, abs_bits(v));
@@ -117,7 +119,7 @@ int launch_se(const SeLaunch& a, hipStream_t st) {
   unsigned* tab = a.amax_y ? a.amax_y->p : nullptr;
   if (tab) a.amax_y->n = gx * 4;
   VASR_LAUNCH_PART(false, true, se_scale_kernel, dim3(gx, a.batch), dim3(256), 0, st, a.x, a.y, a.ld, bs, a.channels,
-                   a.store_cols, a.scale, a.zero_lens, a.relu, a.accumulate, tab, a.amax_y ? a.amax_y->stride : 0,
+                   a.store_cols, a.scale, a.zero_lens, a.relu, a.act, a.accumulate, tab, a.amax_y ? a.amax_y->stride : 0,
                    a.lens_y, a.frames);
   return (int)hipGetLastError();
 }

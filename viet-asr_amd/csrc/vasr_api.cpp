@@ -154,6 +154,9 @@ struct vasr_handle {
   int pane_c_max = 0;   // channels of the dense-residual pane buffer (0: no dense residual GEMM)
   int se_c_max = 0;     // widest squeeze-and-excitation (0: the model has none)
   int norm_c_max = 0, norm_g_max = 0;   // widest GroupNorm, most groups (0: the model has none)
+  // vasr_set_activation: the encoder's activation (kAct*) and residual_mode max (false: add)
+  int act = kActRelu;
+  bool res_max = false;
   std::vector<LenStep> steps;
   std::map<std::string, HostTensor> weights;
   std::vector<void*> dev_allocs;
@@ -811,7 +814,8 @@ int build_encoder(vasr_handle* h) {
         if ((rc = load_norm(h, key, d.filters, B.norm_g, nullptr, &B.res_norm[q]))) return rc;
       }
     }
-    if (B.has_res && (B.se_r || B.norm_g) && B.dense_panes >= 2) {
+    // (max mode: the panes are combined by max, which one GEMM over all of them cannot do)
+    if (B.has_res && (B.se_r || B.norm_g || h->res_max) && B.dense_panes >= 2) {
       B.res_panes.resize(B.dense_panes);
       for (int q = 0; q < B.dense_panes; ++q) {
         const Block& P = h->blocks[i - B.dense_panes + 1 + q];
@@ -844,7 +848,7 @@ int build_encoder(vasr_handle* h) {
       const int chunk = d.filters % 512 == 0 ? 128 : (d.filters % 256 == 0 ? 64 : 32);
       // (grouped blocks: the main branch's grouped reduction and the residual's dense one share no K)
       if (d.stride == 1 && k1 % chunk == 0 && k2 % chunk == 0 && h->sw.fused_residual && !last.pw.conv_cin && !B.res_pane0 &&
-          !B.se_r && B.groups == 1 && !B.norm_g) {
+          !B.se_r && B.groups == 1 && !B.norm_g && !h->res_max) {   // (the fold sums: add mode only)
         char w1[160], bn1[160], w2[160], bn2[160];
         snprintf(w1, sizeof w1, "encoder.%zu.mconv.%d.conv.weight", i, lay.back().conv + (last.separable ? 1 : 0));
         snprintf(bn1, sizeof bn1, "encoder.%zu.mconv.%d", i, lay.back().bn);
@@ -1059,7 +1063,7 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
     SeLaunch a{};
     a.x = sx; a.y = sy; a.ld = ld; a.bs = 0; a.channels = L.c; a.hidden = L.hidden; a.batch = batch;
     a.frames = (int)frames; a.store_cols = store_cols; a.lens = pool_lens; a.w1 = L.d_w1; a.w2 = L.d_w2;
-    a.sums = se_sums; a.scale = se_scale; a.zero_lens = zero_lens; a.relu = relu; a.accumulate = acc;
+    a.sums = se_sums; a.scale = se_scale; a.zero_lens = zero_lens; a.relu = relu; a.act = h->act; a.accumulate = acc;
     a.amax_y = am; a.lens_y = lens_y;
     ProfScope ps(h, kProfDepthwise, st, 4.0 * L.c * L.hidden * (double)batch,
                  4.0 * (acc ? 4.0 : 3.0) * L.c * (double)store_cols * batch);
@@ -1079,7 +1083,7 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
     a.lens = stat_lens; a.group_of = L.d_group_of; a.members = L.d_members; a.gamma = L.d_gamma; a.beta = L.d_beta;
     a.row_mean = nrm_ws; a.row_m2 = nrm_ws + (size_t)batch * h->norm_c_max;
     a.g_mean = nrm_ws + (size_t)2 * batch * h->norm_c_max; a.g_rstd = a.g_mean + (size_t)batch * h->norm_g_max;
-    a.zero_lens = zero_lens; a.relu = relu; a.amax_y = am; a.lens_y = lens_y;
+    a.zero_lens = zero_lens; a.relu = relu; a.act = h->act; a.amax_y = am; a.lens_y = lens_y;
     // (counted with the depthwise class, as the SE passes are: statistics and affine, ~5 flops per element; two reads for
     // the statistics, a read and a write to apply)
     ProfScope ps(h, kProfDepthwise, st, 5.0 * L.c * (double)frames * batch,
@@ -1114,12 +1118,16 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
     }
     // residual panes' masks: the block input lengths; a last block's residual keeps its padding columns (the encoder output's)
     const int32_t* res_zero = last_block ? nullptr : lens(B.first_step);
-    if (B.has_res && (B.se_r || B.norm_g) && B.dense_panes >= 2) {
-      // dense residual with SE or GroupNorm: sum_p SE_p(N_p(W_p mask(x_p))) (parts/jasper.py:428-439) -- pane 0's GEMM writes R
-      // and is normalized / rescaled in place, every later pane's goes through D and is added onto R by its last pass
+    if (B.has_res && (B.se_r || B.norm_g || h->res_max) && B.dense_panes >= 2) {
+      // dense residual with SE or GroupNorm, or combined by max: sum_p (max_p) SE_p(N_p(W_p mask(x_p))) (parts/jasper.py:428-441)
+      // -- pane 0's GEMM writes R and is normalized / rescaled in place, every later pane's goes through D and is combined
+      // onto R by its last pass; max without SE: every later pane's GEMM takes max(R, its result) into R itself (each element
+      // of R is read and then stored by the one thread that owns it, encoder_pw*.hip)
+      const int acc_mode = h->res_max ? 2 : 1;
       for (int q = 0; q < B.dense_panes; ++q) {
         const ConvLayer& W = B.res_panes[q];
-        float* Rq = q == 0 ? R : D;
+        const bool gemm_max = h->res_max && !B.se_r && q > 0;
+        float* Rq = (q == 0 || gemm_max) ? R : D;
         const float* px = panes + (int64_t)B.res_pane_off[q] * cur_ld;
         PwArgs a{};
         a.busy_cus = h->busy_cus;
@@ -1127,6 +1135,7 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
         a.res = nullptr; a.y = Rq; a.M = W.m_pad; a.K = W.cin; a.batch = batch;
         a.ldx = cur_ld; a.ldy = cur_ld; a.ldr = 0; a.frames = (int)cur_T; a.store_cols = (int)cur_ld;
         a.m_store = W.m_pad; a.relu = 0;
+        if (gemm_max) { a.res = R; a.ldr = cur_ld; a.res_max = 1; }
         if (want_amax) {
           a.amax_x = free_tab(AmaxTab{});
           launch_amax(px, cur_ld, W.cin, (int)cur_T, lens(B.first_step), batch, &a.amax_x, st, pane_bs);
@@ -1138,8 +1147,8 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
         if (B.norm_g && run_norm(B.res_norm[q], Rq, B.se_r ? Rq : R, (!B.se_r && q > 0) ? R : nullptr, cur_ld, cur_ld, cur_T,
                                  (int)cur_ld, lens(B.first_step), res_zero, 0, nullptr, nullptr))
           return VASR_ERR_HIP;
-        if (B.se_r && run_se(B.res_se[q], Rq, R, cur_ld, cur_T, (int)cur_ld, lens(B.first_step), res_zero, 0, q > 0, nullptr,
-                             nullptr))
+        if (B.se_r && run_se(B.res_se[q], Rq, R, cur_ld, cur_T, (int)cur_ld, lens(B.first_step), res_zero, 0,
+                             q > 0 ? acc_mode : 0, nullptr, nullptr))
           return VASR_ERR_HIP;
       }
     } else if (B.has_res && B.dense_panes >= 2) {
@@ -1246,7 +1255,7 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
         f.x = cur; f.ldx = cur_ld; f.lens_in = lens(S.dw.step); f.lens_out = lens(S.dw.step + 1);
         f.taps = S.dw.d_ftaps; f.dw_l1 = S.dw.f_l1; f.amax_x = cur_amax;
         f.wt = WF.d_w16; f.w_inv_scale = WF.w16_inv; f.scale = WF.d_scale; f.shift = WF.d_shift;
-        f.y = dst; f.ldy = cur_ld; f.frames = (int)cur_T; f.relu = 1;
+        f.y = dst; f.ldy = cur_ld; f.frames = (int)cur_T; f.relu = 1; f.act = h->act;
         f.amax_y = free_tab(cur_amax); f.lens_y = lens(S.pw.step + 1);
         if (fuse_res) { f.x2 = blk_in; f.ldx2 = blk_ld; f.lens2 = lens(B.first_step); f.amax_x2 = blk_amax; }
         f.batch = batch; f.kernel = S.dw.kernel;
@@ -1317,6 +1326,8 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
       // se and not residual: the last sub-layer's SE comes before the block's output activation (parts/jasper.py:250-251, mout)
       const int act = (last_sub && S.se.d_w1) ? 0 : 1;
       a.relu = nrm ? 0 : act;
+      a.act = h->act;
+      a.res_max = h->res_max;   // (max with GroupNorm is refused: vasr_finalize)
       a.store_cols = (dst_ld % kTimeTile == 0) ? (int)dst_ld : (int)g_T;  // port tensors are not padded
       if (W.conv_cin) {
         a.conv_cin = W.conv_cin; a.conv_stride = W.stride; a.conv_dil = W.dilation; a.conv_pad = W.pad;
@@ -1557,10 +1568,25 @@ int vasr_set_block_norm(vasr_handle* h, int block, int norm_groups) {
   return 0;
 }
 
+int vasr_set_activation(vasr_handle* h, int activation, int residual_mode) {
+  if (!h) return fail(VASR_ERR_INVALID, "null handle");
+  if (h->finalized) return fail(VASR_ERR_STATE, "handle already finalized");
+  if (activation < kActRelu || activation > kActSelu)
+    return fail(VASR_ERR_INVALID, "activation %d (0 relu, 1 hardtanh, 2 selu)", activation);
+  if (residual_mode < 0 || residual_mode > 1) return fail(VASR_ERR_INVALID, "residual_mode %d (0 add, 1 max)", residual_mode);
+  h->act = activation;
+  h->res_max = residual_mode == 1;
+  return 0;
+}
+
 int vasr_finalize(vasr_handle* h) {
   if (!h) return fail(VASR_ERR_INVALID, "null handle");
   if (h->finalized) return 0;
   int rc;
+  if (h->has_encoder && h->res_max)
+    for (size_t i = 0; i < h->blocks.size(); ++i)
+      if (h->blocks[i].norm_g)
+        return fail(VASR_ERR_UNSUPPORTED, "block %zu: residual_mode max with group, instance or layer normalization", i);
   if (h->has_encoder && (rc = check_groups(h))) return rc;
   if (h->has_encoder && (rc = check_se(h))) return rc;
   if (h->has_encoder && (rc = check_norm(h))) return rc;

@@ -18,6 +18,27 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
   return max(max(a, b), max(c, d));
 }
 
+// ---- the encoder's activation (vasr_set_activation; codes kAct* in vasr_internal.h) ----
+// jasper_activations (nemo/collections/asr/parts/jasper.py:21-25): nn.ReLU, nn.Hardtanh() = clamp(x, -1, 1) and nn.SELU.
+// SELU's negative side is lambda * alpha * expm1(x): exp(x) - 1 loses every significant bit near 0 (relative error up to 1
+// there; torch's CPU SELU is within 1.2e-7 of float64), so the accurate expm1f, never __expf(x) - 1.
+constexpr float kSeluLambda = 1.0507009873554804934193349852946f;
+constexpr float kSeluAlpha = 1.6732632423543772848170429916717f;
+__device__ __forceinline__ float selu(float v) {
+  return v > 0.f ? kSeluLambda * v : (kSeluLambda * kSeluAlpha) * expm1f(v);
+}
+// the clamp of epilogue kind 1 (epilogue_kind, vasr_internal.h): Hardtanh [-1, 1], ReLU [0, inf), nothing (relu flag clear)
+__device__ __forceinline__ void clamp_bounds(int relu, int act, float& lo, float& hi) {
+  lo = (relu & 1) ? (act == 1 ? -1.f : 0.f) : -__builtin_inff();
+  hi = ((relu & 1) && act == 1) ? 1.f : __builtin_inff();
+}
+// act: 0 ReLU, 1 Hardtanh, 2 SELU (uniform across the launch)
+__device__ __forceinline__ float activate(float v, int act) {
+  if (act == 2) return selu(v);
+  if (act == 1) return fminf(fmaxf(v, -1.f), 1.f);
+  return v > 0.f ? v : 0.f;
+}
+
 __device__ __forceinline__ unsigned abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
 
 // ---- per-utterance maxima (AmaxTab, vasr_internal.h) ----

@@ -156,6 +156,18 @@ int launch_depthwise_mfma(const float* x, int64_t ldx, const unsigned int* taps,
                           int channels, int kernel, int dilation, float* y, int64_t ldy, AmaxTab* amax_y,
                           hipStream_t st);
 
+// the encoder's activation (vasr_set_activation), applied where a launch's relu flag is set: 0 ReLU, 1 Hardtanh (clamp to
+// [-1, 1]), 2 SELU (vasr_device.h activate)
+enum : int32_t { kActRelu = 0, kActHardtanh = 1, kActSelu = 2 };
+
+// Which epilogue a GEMM or fused launch takes (template EPI of encoder_pw*.hip, encoder_fused.hip): 0 = ReLU or nothing,
+// residual added -- the kernels the ReLU / add models have always run; 1 = a clamp to uniform bounds (Hardtanh, or ReLU
+// under a max residual); 2 = SELU.  Under 1 and 2 the residual is added or, res_max, combined by max.
+inline int epilogue_kind(int relu, int act, bool res_max) {
+  if ((relu & 1) && act == kActSelu) return 2;
+  return (((relu & 1) && act != kActRelu) || res_max) ? 1 : 0;
+}
+
 struct PwArgs {
   const float* wt;        // weights in MFMA fragment order (pack_pointwise_weights), M % 128 == 0, K % 32 == 0
   const float* x;         // [B][K][ldx]  (dual source: [B][K1][ldx])
@@ -166,14 +178,16 @@ struct PwArgs {
   int64_t ldx2;
   const float* scale;     // [M]
   const float* shift;     // [M]
-  const float* res;       // [B][M][ldr] added before the ReLU (nullptr = none)
+  const float* res;       // [B][M][ldr] combined (res_max ? max : +) before the activation (nullptr = none); may equal y
   float* y;               // [B][M][ldy]
   int32_t M, K, batch;
   int64_t ldx, ldy, ldr;
   int32_t frames;         // valid columns
   int32_t store_cols;     // columns < store_cols are stored: ldy for padded internal buffers, frames for ports
   int32_t m_store;        // rows < m_store are stored (decoder: V+1 of 128)
-  int32_t relu;
+  int32_t relu;           // bit 0: apply the activation `act`; bit 1 (fp32 and latency kernels): skip the epilogue (ablation)
+  int32_t act;            // kAct*
+  int32_t res_max;        // residual_mode "max": y = act(max(affine, res)) instead of act(affine + res)
   // [B] (or nullptr): every input source of utterance b is zero at columns >= zero_from[b] (the depthwise kernel and
   // the masks guarantee it), so a time tile that starts there skips its K loop: its outputs are relu(shift (+ res)).
   // Ragged batches only -- full-length clips never hit it.  Honoured by the split-bf16 kernel.
@@ -234,7 +248,7 @@ struct FusedLaunch {
   AmaxTab amax_x;
   const void* wt; float w_inv_scale;           // f16x2 pack of the 1x1 conv (K = 256, or 512 with the residual folded in)
   const float* scale; const float* shift;
-  float* y; int64_t ldy; int32_t frames, relu;
+  float* y; int64_t ldy; int32_t frames, relu, act;   // act: kAct*, applied when relu != 0
   AmaxTab amax_y; const int32_t* lens_y;
   const float* x2; int64_t ldx2; const int32_t* lens2; AmaxTab amax_x2;   // residual source (nullptr = none)
   int32_t batch, kernel;
@@ -259,7 +273,8 @@ float pack_fused_taps(const float* w, int channels, int kernel, float* out);
 int launch_fused_dwpw(const FusedLaunch& f, hipStream_t st, int* amax_n);   // 0, a hipError_t, or -1 (shape not covered)
 
 // ---- squeeze-and-excitation (encoder_se.hip) ----
-// y[b][c][t] = act(x[b][c][t] * s[b][c]) (accumulate: y += x * s), s = sigmoid(W2 relu(W1 mean)), mean = the sum of x over
+// y[b][c][t] = act(x[b][c][t] * s[b][c]) (accumulate 1: y += x * s, 2: y = max(y, x * s)), s = sigmoid(W2 relu(W1 mean)) --
+// the inner ReLU is SqueezeExcite's own, whatever the encoder's activation, mean = the sum of x over
 // t < min(lens[b], frames) divided by that count; columns t >= zero_lens[b] (nullptr: none) of the stored range
 // [0, store_cols) are stored as 0.  x may equal y.  amax_y (optional): republished over t < lens_y[b] (nullptr: < frames).
 struct SeLaunch {
@@ -270,7 +285,7 @@ struct SeLaunch {
   const float* w1; const float* w2;   // [hidden][channels], [channels][hidden]
   float* sums; float* scale;      // workspace, [batch][channels] each
   const int32_t* zero_lens;
-  int relu, accumulate;
+  int relu, act, accumulate;      // relu != 0: apply the activation act (kAct*)
   AmaxTab* amax_y; const int32_t* lens_y;
 };
 bool se_supported(int channels, int hidden);   // channels and hidden in [1, 1024]
@@ -292,7 +307,7 @@ struct NormLaunch {
   float* row_mean; float* row_m2;                    // workspace, [batch][channels] each
   float* g_mean; float* g_rstd;                      // workspace, [batch][groups] each
   const int32_t* zero_lens;
-  int relu;
+  int relu, act;                  // relu != 0: apply the activation act (kAct*)
   AmaxTab* amax_y; const int32_t* lens_y;
 };
 bool norm_supported(int channels, int groups);   // groups divides channels

@@ -85,6 +85,18 @@ def groups_from_config(jasper_cfg):
 NORM_MODES = ("batch", "group", "instance", "layer")
 
 
+ACTIVATIONS = {"relu": 0, "hardtanh": 1, "selu": 2}   # jasper_activations (parts/jasper.py:21-25) -> vasr_set_activation
+
+
+def activation_from_config(enc_cfg):
+    """JasperEncoder's ``activation`` and ``residual_mode`` (jasper.py:136-150, parts/jasper.py:438-441) -> the arguments of
+    vasr_set_activation: (0 relu / 1 hardtanh / 2 selu, 0 add / 1 max).  An unknown activation raises KeyError, as the
+    reference's dictionary lookup does; every residual_mode other than "add" combines the panes by max, as the reference's
+    ``if self.residual_mode == "add": ... else: torch.max`` does."""
+    act = ACTIVATIONS[enc_cfg.get("activation", "relu")]
+    return act, 0 if enc_cfg.get("residual_mode", "add") == "add" else 1
+
+
 def norm_from_config(enc_cfg, jasper_cfg):
     """Per block of a YAML block list: the GroupNorm group count of JasperEncoder's ``normalization_mode`` / ``norm_groups``
     (jasper.py:136-186, parts/jasper.py:342-391) -- 0 for "batch" (BatchNorm1d), ``norm_groups`` for "group" (-1, the
@@ -153,19 +165,22 @@ class QuartzNetCTC:
         pre = dict(model_definition["AudioToMelSpectrogramPreprocessor"])
         jas = model_definition["JasperEncoder"]["jasper"]
         enc_cfg = model_definition["JasperEncoder"]
-        if enc_cfg.get("activation", "relu") != "relu" or not enc_cfg.get("conv_mask", True):
-            raise NotImplementedError("only activation='relu', conv_mask=True is implemented")
+        self._act, self._res_mode = activation_from_config(enc_cfg)
+        if not enc_cfg.get("conv_mask", True):
+            raise NotImplementedError("only conv_mask=True is implemented")
         self.frontend = frontend_description(pre)
         self.hop = self.frontend["hop_length"]
         self._blocks = blocks_from_config(jas)
         self._se = se_from_config(jas)
         self._groups = groups_from_config(jas)
         self._norm = norm_from_config(enc_cfg, jas)
+        if self._res_mode and any(self._norm):
+            raise NotImplementedError("residual_mode='max' with group, instance or layer normalization is not implemented")
         with torch.cuda.device(self.device):
             self.handle = _lib.Handle(frontend=self.frontend, feat_in=pre.get("features", 64),
                                       blocks=blocks_from_config(jas), dec_feat_in=jas[-1]["filters"],
                                       num_classes=len(self.labels) + 1, se=self._se, groups=self._groups,
-                                      norm=self._norm)
+                                      norm=self._norm, activation=self._act, residual_mode=self._res_mode)
             self.handle.load_state_dict(encoder_state)
             self.handle.load_state_dict(decoder_state)
             self.handle.finalize()

@@ -130,6 +130,15 @@ def _se(prefix, seed, c, ratio, sd):
     sd[f"{prefix}.fc.2.weight"] = _rs(f"{prefix}.fc.2.weight", seed).normal(3.0, 2.0, size=(c, h)).astype(np.float32) / np.float32(np.sqrt(h))
 
 
+def scale_conv_weights(sd, gain):
+    """A copy of an encoder state dict with every conv weight multiplied by ``gain`` (float32).  The gains above are tuned
+    for ReLU, which passes half of its input: an activation that passes negative values too (hardtanh, SELU) makes a deep
+    stack expand, and fp32 round-off then grows through 54 layers past any fixed tolerance.  A gain below 1 keeps such a
+    model contracting."""
+    g = np.float32(gain)
+    return {k: (v * g if k.endswith("conv.weight") else v) for k, v in sd.items()}
+
+
 def decoder_state_dict(feat_in, num_classes_with_blank, seed=0):
     sd = {}
     # gain 2 on O(1..6) activations: peaky posteriors, greedy argmax margins far above fp32 round-off
