@@ -8,21 +8,24 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <algorithm>
 #include <vector>
 
 #include "vasr.h"
-#include "vasr_devtools.h"
+#include "vasr_host.h"
 #include "vasr_internal.h"
 
 using namespace vasr;
 
-namespace vasr { thread_local LaunchProbe g_probe; }
-
 namespace {
-
 thread_local std::string g_err;
+}
+
+namespace vasr {
+
+thread_local LaunchProbe g_probe;
 
 int fail(int code, const char* fmt, ...) {
   char buf[512];
@@ -34,11 +37,28 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) return fail(VASR_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
+int check_launch(const char* what) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(VASR_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
+  return 0;
+}
+
+NormTables norm_tables(const float* gamma, const float* beta, int c, int G, int shuffle) {
+  NormTables t{std::vector<float>(c), std::vector<float>(c), std::vector<int32_t>(c), std::vector<int32_t>(c)};
+  const int cpg = c / G, mg = c / shuffle;
+  for (int p = 0; p < c; ++p) {
+    const int o = (p % mg) * shuffle + p / mg;
+    t.gamma[o] = gamma[p];
+    t.beta[o] = beta[p];
+    t.group_of[o] = p / cpg;
+    t.members[p] = o;
+  }
+  return t;
+}
+
+}  // namespace vasr
+
+namespace {
 
 struct HostTensor {
   std::vector<float> data;
@@ -93,38 +113,45 @@ struct SubBlock {
   NormLayer norm;           // GroupNorm of the conv's output (the GEMM then stores it raw)
 };
 
+// One 1x1 GEMM of a block's residual branch: the conv (+ its folded BatchNorm) of one source, then its GroupNorm and its
+// SqueezeExcite where the block has them (parts/jasper.py:264-288, :428-441)
+struct ResGemm {
+  ConvLayer w;
+  int pane_off = -1;        // the source: channels [pane_off, pane_off + w.cin) of the pane buffer; -1: the block input
+  NormLayer norm;           // d_gamma == nullptr: none
+  SeLayer se;               // d_w1 == nullptr: none
+};
+
 struct Block {
   vasr_block_desc d;
   std::vector<SubBlock> subs;
   bool has_res = false;
-  ConvLayer res;
-  bool fused_res = false;   // residual 1x1 conv folded into the last sub-block's GEMM (dual-source K)
+  // The residual GEMMs, summed (residual_mode max: combined by max) into the block's residual (build_encoder fills it, run_encoder
+  // runs it in order).  One entry: a plain residual reads the block input, a res_pane0 one pane 0, a dense one (dense_panes
+  // >= 2) channels [0, w.cin) of the pane buffer with w = [a_0 W_0 | a_1 W_1 | ...], scale 1, shift sum b_p.  With SE, GroupNorm
+  // or max a dense residual cannot be summed before those: dense_panes entries, one per pane.
+  std::vector<ResGemm> res;
+  bool fused_res = false;   // the (single) residual GEMM folded into the last sub-block's GEMM (dual-source K): res is not run
   ConvLayer fused;          // weights [s1*W1 | s2*W2], scale 1, shift h1 + h2; cin = K1 + K2
   int fused_k1 = 0;
   int first_step = 0;
   // dense residual (residual_dense): the block's input is pane `pane` of its run's pane buffer [B][pane_c][ld] (-1: not
-  // kept); with dense_panes >= 2 the residual is ONE 1x1 GEMM over channels [0, res.cin) of that buffer (`res` holds
-  // [a_0 W_0 | a_1 W_1 | ...], scale 1, shift sum b_p)
+  // kept); dense_panes: the panes this block's residual reads (0: not a dense residual)
   int pane = -1, pane_off = 0, pane_c = 0, dense_panes = 0;
   bool keep_input = false;   // a later block of the run (or this one) reads this block's input as a pane
   // a residual block that is NOT dense right after a dense run receives the run's pane list and takes its (single) residual
   // from pane 0, the run's input, not from its own input (parts/jasper.py:428-436: res_out = xs[0])
   bool res_pane0 = false;
-  // se (vasr_set_block_se): 0 = none, else the reduction ratio.  With residual, one SE per residual pane (res_se[p]); the
-  // residual then always takes the separate-GEMM form, and a dense one runs one GEMM per pane (res_panes[p], channels
-  // res_pane_off[p] .. + res_panes[p].cin of the pane buffer) whose SE-scaled results are summed into R
+  // se (vasr_set_block_se): 0 = none, else the reduction ratio.  With residual, one SE per residual pane (res[p].se); the
+  // residual then always takes the separate-GEMM form
   int se_r = 0;
   // groups / heads (vasr_set_block_groups): every main-branch conv grouped (groups > 1) and followed by a GroupShuffle; the
   // depthwise weights of a separable block shared by channel c % heads (heads > 0)
   int groups = 1, heads = 0;
   // norm_g (vasr_set_block_norm): 0 = BatchNorm (folded into the epilogues), else GroupNorm(norm_g, filters) after every conv
-  // of the block: its GEMMs store raw output, each residual pane is its own GEMM normalized on its own (res_norm[p]), and
+  // of the block: its GEMMs store raw output, each residual pane is its own GEMM normalized on its own (res[p].norm), and
   // the last sub-layer's normalization adds the residual sum and applies the output activation
   int norm_g = 0;
-  std::vector<NormLayer> res_norm;
-  std::vector<SeLayer> res_se;
-  std::vector<ConvLayer> res_panes;
-  std::vector<int> res_pane_off;
 };
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -165,7 +192,6 @@ struct vasr_handle {
   LenStep* d_steps = nullptr;
   ConvLayer dec;
   int c_mid_max = 0, c_last = 0;
-  // optional per-kernel-class HIP-event timing (vasr_profile_begin/end)
   // batch slicing across internal streams (vasr_set_slices)
   // measured on MI355X (QuartzNet15x5, B=64, 512x128 GEMM tiles pinned): 1 slice 7.35 ms, 2 slices 7.41 ms, 2 slices
   // phase-shifted by 40 / 100 / 300 us 7.39 / 7.34 / 7.68 ms -- the kernels of the two streams do not overlap in any
@@ -182,43 +208,12 @@ struct vasr_handle {
   // max error against fp64 slightly LOWER than mode 0's: 3.6e-6 vs 4.7e-6 at K = 512), 2 = reduced 2 x bf16 (opt-in),
   // 3 = 2 x fp16 scaled split operands on v_mfma_f32_32x32x16_f16 (half the matrix work of mode 1, see vasr.h)
   int gemm_mode = parse_gemm_mode(getenv("VASR_GEMM"));
+  // optional per-kernel-class HIP-event timing (vasr_profile_begin/end)
   bool profiling = false;
   struct ProfRec { hipEvent_t a, b; int cls; double flops, bytes; };
   std::vector<ProfRec> prof;
   std::vector<hipEvent_t> ev_pool;
 };
-
-#ifdef VASR_DEVTOOLS
-// The devtools build's kernel-selection switches (vasr_internal.h DevSwitches): the environment is read HERE, once per
-// process, and nowhere else; a value outside a switch's documented set aborts instead of silently meaning "default".
-const vasr::DevSwitches& vasr::dev_switches() {
-  static const DevSwitches sw = [] {
-    DevSwitches s;
-    auto num = [](const char* name, int dflt, std::initializer_list<int> allowed) {
-      const char* e = getenv(name);
-      if (!e) return dflt;
-      const int v = atoi(e);
-      for (int a : allowed) if (a == v) return v;
-      fprintf(stderr, "vasr (devtools build): %s=%s is not a documented value -- refusing to guess\n", name, e);
-      abort();
-      return dflt;   // (not reached)
-    };
-    s.pw3_tile = num("VASR_PW3_TILE", 0, {0, 1, 2, 3, 4, 5});
-    s.pw_lat = num("VASR_PW_LAT", 1, {0, 1});
-    s.dw_pair = num("VASR_DW_PAIR", 1, {0, 1}) != 0;
-    s.dw_mfma = num("VASR_DW_MFMA", 1, {0, 1}) != 0;
-    s.dw_upw = num("VASR_DW_UPW", 0, {0, 1, 2, 3, 4, 5, 6, 7, 8});
-    s.fused = num("VASR_FUSED", 1, {0, 1}) != 0;
-    s.fused_min_tiles = getenv("VASR_FUSED_MIN_TILES") ? atoi(getenv("VASR_FUSED_MIN_TILES")) : 0;
-    s.fused_tile = num("VASR_FUSED_TILE", 0, {0, 64, 128});
-    s.fused_residual = num("VASR_NO_FUSED_RESIDUAL", 0, {0, 1}) == 0;
-    s.beam_group = num("VASR_BEAM_GROUP", -1, {-1, 0, 1, 4});
-    s.no_grouped = num("VASR_NO_GROUPED", 0, {0, 1}) != 0;
-    return s;
-  }();
-  return sw;
-}
-#endif
 
 struct vasr_lm {
   BeamLm view{};
@@ -262,35 +257,47 @@ int need(const vasr_handle* h, const std::string& key, size_t numel, const HostT
   return 0;
 }
 
-// eval-mode BatchNorm1d(eps=1e-3) -> y = x * scale + shift  (parts/jasper.py:392)
-// perm (optional): channel i's affine goes to row perm[i] (a grouped layer's block-diagonal form: the channel shuffle)
-int fold_bn(vasr_handle* h, const std::string& prefix, int c, int c_pad, ConvLayer* L, const std::vector<int>* perm = nullptr) {
+// eval-mode BatchNorm1d(eps=1e-3) -> y = x * alpha + beta  (parts/jasper.py:392)
+int bn_affine(vasr_handle* h, const std::string& prefix, int c, std::vector<float>* alpha, std::vector<float>* beta) {
   const HostTensor *g, *b, *m, *v;
   int rc;
-  if ((rc = need(h, prefix + ".weight", c, &g))) return rc;
-  if ((rc = need(h, prefix + ".bias", c, &b))) return rc;
-  if ((rc = need(h, prefix + ".running_mean", c, &m))) return rc;
-  if ((rc = need(h, prefix + ".running_var", c, &v))) return rc;
-  std::vector<float> sc(c_pad, 0.f), sh(c_pad, 0.f);
+  if ((rc = need(h, prefix + ".weight", c, &g)) || (rc = need(h, prefix + ".bias", c, &b)) ||
+      (rc = need(h, prefix + ".running_mean", c, &m)) || (rc = need(h, prefix + ".running_var", c, &v)))
+    return rc;
+  alpha->resize(c);
+  beta->resize(c);
   for (int i = 0; i < c; ++i) {
     // same association as ATen's CPU eval path: alpha = w * invstd, beta = b - mean * alpha (fp32)
     const float invstd = 1.0f / std::sqrt(v->data[i] + 1e-3f);
-    const float alpha = g->data[i] * invstd;
-    const int o = perm ? (*perm)[i] : i;
-    sc[o] = alpha;
-    sh[o] = b->data[i] - m->data[i] * alpha;
+    (*alpha)[i] = g->data[i] * invstd;
+    (*beta)[i] = b->data[i] - m->data[i] * (*alpha)[i];
   }
-  if ((rc = upload(h, sc, &L->d_scale))) return rc;
-  return upload(h, sh, &L->d_shift);
+  return 0;
+}
+
+int upload_affine(vasr_handle* h, const std::vector<float>& scale, const std::vector<float>& shift, ConvLayer* L) {
+  const int rc = upload(h, scale, &L->d_scale);
+  return rc ? rc : upload(h, shift, &L->d_shift);
+}
+
+// the BatchNorm under `prefix` as L's epilogue, padded to c_pad rows
+// perm (optional): channel i's affine goes to row perm[i] (a grouped layer's block-diagonal form: the channel shuffle)
+int fold_bn(vasr_handle* h, const std::string& prefix, int c, int c_pad, ConvLayer* L, const std::vector<int>* perm = nullptr) {
+  std::vector<float> alpha, beta, sc(c_pad, 0.f), sh(c_pad, 0.f);
+  if (int rc = bn_affine(h, prefix, c, &alpha, &beta)) return rc;
+  for (int i = 0; i < c; ++i) {
+    const int o = perm ? (*perm)[i] : i;
+    sc[o] = alpha[i];
+    sh[o] = beta[i];
+  }
+  return upload_affine(h, sc, sh, L);
 }
 
 // a normalized block's GEMMs store their raw output: scale 1, shift 0 (GroupNorm follows in encoder_norm.hip)
 int unit_affine(vasr_handle* h, int c, int c_pad, ConvLayer* L) {
   std::vector<float> sc(c_pad, 0.f), sh(c_pad, 0.f);
   std::fill_n(sc.begin(), c, 1.f);
-  int rc;
-  if ((rc = upload(h, sc, &L->d_scale))) return rc;
-  return upload(h, sh, &L->d_shift);
+  return upload_affine(h, sc, sh, L);
 }
 
 // BatchNorm under `prefix` folded into L's epilogue, or (norm_g > 0) the unit affine of a layer GroupNorm follows
@@ -299,28 +306,19 @@ int conv_affine(vasr_handle* h, int norm_g, const std::string& prefix, int c, in
   return norm_g ? unit_affine(h, c, c_pad, L) : fold_bn(h, prefix, c, c_pad, L, perm);
 }
 
-// GroupNorm(G, c) under `prefix` (weight / bias [c]); perm (optional): pre-shuffle channel p is stored at row perm[p]
-int load_norm(vasr_handle* h, const std::string& prefix, int c, int G, const std::vector<int>* perm, NormLayer* L) {
+// GroupNorm(G, c) under `prefix` (weight / bias [c]); shuffle: the groups of a grouped block's channel shuffle (1: none)
+int load_norm(vasr_handle* h, const std::string& prefix, int c, int G, int shuffle, NormLayer* L) {
   const HostTensor *g, *b;
   int rc;
   if ((rc = need(h, prefix + ".weight", c, &g)) || (rc = need(h, prefix + ".bias", c, &b))) return rc;
-  const int cpg = c / G;
-  std::vector<float> gs(c), bs(c);
-  std::vector<int32_t> group_of(c), members(c);
-  for (int p = 0; p < c; ++p) {
-    const int o = perm ? (*perm)[p] : p;
-    gs[o] = g->data[p];
-    bs[o] = b->data[p];
-    group_of[o] = p / cpg;
-    members[p] = o;
-  }
+  const NormTables t = norm_tables(g->data.data(), b->data.data(), c, G, shuffle);
   L->c = c;
   L->groups = G;
   h->norm_c_max = std::max(h->norm_c_max, c);
   h->norm_g_max = std::max(h->norm_g_max, G);
-  if ((rc = upload(h, gs, &L->d_gamma)) || (rc = upload(h, bs, &L->d_beta)) || (rc = upload(h, group_of, &L->d_group_of)))
+  if ((rc = upload(h, t.gamma, &L->d_gamma)) || (rc = upload(h, t.beta, &L->d_beta)) || (rc = upload(h, t.group_of, &L->d_group_of)))
     return rc;
-  return upload(h, members, &L->d_members);
+  return upload(h, t.members, &L->d_members);
 }
 
 // the channel shuffle of a grouped block (parts/jasper.py:135-150): pre-shuffle channel p = g * (c / G) + j is stored at
@@ -332,20 +330,22 @@ std::vector<int> shuffle_perm(int c, int G) {
   return perm;
 }
 
-int bn_affine(vasr_handle* h, const std::string& prefix, int c, std::vector<float>* alpha, std::vector<float>* beta) {
-  const HostTensor *g, *b, *m, *v;
+// The fragment packs of a row-major [cout][K] matrix into L (L->m_pad rows): split -- the 3 x bf16 and 2 x fp16 packs of the
+// split GEMMs; fp32 -- the exact-fp32 kernel's pack
+int upload_packs(vasr_handle* h, const float* w, int cout, int K, ConvLayer* L, bool fp32, bool split) {
   int rc;
-  if ((rc = need(h, prefix + ".weight", c, &g)) || (rc = need(h, prefix + ".bias", c, &b)) ||
-      (rc = need(h, prefix + ".running_mean", c, &m)) || (rc = need(h, prefix + ".running_var", c, &v)))
-    return rc;
-  alpha->resize(c);
-  beta->resize(c);
-  for (int i = 0; i < c; ++i) {
-    const float invstd = 1.0f / std::sqrt(v->data[i] + 1e-3f);
-    (*alpha)[i] = g->data[i] * invstd;
-    (*beta)[i] = b->data[i] - m->data[i] * (*alpha)[i];
+  if (split) {
+    std::vector<unsigned short> w3((size_t)K * L->m_pad * 3);
+    pack_pointwise_weights_bf16x3(w, cout, K, L->m_pad, w3.data());
+    if ((rc = upload(h, w3, &L->d_w3))) return rc;
+    std::vector<unsigned short> w16((size_t)K * L->m_pad * 2);
+    L->w16_inv = pack_pointwise_weights_f16x2(w, cout, K, L->m_pad, w16.data());
+    if ((rc = upload(h, w16, &L->d_w16))) return rc;
   }
-  return 0;
+  if (!fp32) return 0;
+  std::vector<float> wt((size_t)K * L->m_pad, 0.f);
+  pack_pointwise_weights(w, cout, K, L->m_pad, wt.data());
+  return upload(h, wt, &L->d_w);
 }
 
 // 1x1 convs + BNs over sources concatenated along K as ONE reduction:
@@ -356,7 +356,10 @@ struct SumSrc { std::string w_key, bn; int k; };
 int pack_sum_1x1(vasr_handle* h, const std::vector<SumSrc>& src, int cout, int k1_split, ConvLayer* L) {
   int K = 0, rc;
   for (const SumSrc& s : src) K += s.k;
-  std::vector<float> w((size_t)cout * K), sh_sum(cout, 0.f);
+  L->cin = K;
+  L->cout = cout;
+  L->m_pad = (int)align_up(cout, 128);
+  std::vector<float> w((size_t)cout * K), sc(L->m_pad, 1.f), sh(L->m_pad, 0.f);
   int off = 0;
   for (const SumSrc& s : src) {
     const HostTensor* ws;
@@ -364,33 +367,18 @@ int pack_sum_1x1(vasr_handle* h, const std::vector<SumSrc>& src, int cout, int k
     if ((rc = need(h, s.w_key, (size_t)cout * s.k, &ws)) || (rc = bn_affine(h, s.bn, cout, &a, &b))) return rc;
     for (int m = 0; m < cout; ++m) {
       for (int k = 0; k < s.k; ++k) w[(size_t)m * K + off + k] = a[m] * ws->data[(size_t)m * s.k + k];
-      sh_sum[m] += b[m];
+      sh[m] += b[m];
     }
     off += s.k;
   }
-  L->cin = K;
-  L->cout = cout;
-  L->m_pad = (int)align_up(cout, 128);
-  std::vector<float> wt((size_t)K * L->m_pad, 0.f), sc(L->m_pad, 1.f), sh(L->m_pad, 0.f);
-  pack_pointwise_weights(w.data(), cout, K, L->m_pad, wt.data());
-  for (int m = 0; m < cout; ++m) sh[m] = sh_sum[m];
-  if (pointwise_split_supported(L->m_pad, K, k1_split)) {
-    std::vector<unsigned short> w3((size_t)K * L->m_pad * 3);
-    pack_pointwise_weights_bf16x3(w.data(), cout, K, L->m_pad, w3.data());
-    if ((rc = upload(h, w3, &L->d_w3))) return rc;
-    std::vector<unsigned short> w16((size_t)K * L->m_pad * 2);
-    L->w16_inv = pack_pointwise_weights_f16x2(w.data(), cout, K, L->m_pad, w16.data());
-    if ((rc = upload(h, w16, &L->d_w16))) return rc;
-  }
-  if ((rc = upload(h, wt, &L->d_w)) || (rc = upload(h, sc, &L->d_scale))) return rc;
-  return upload(h, sh, &L->d_shift);
+  if ((rc = upload_packs(h, w.data(), cout, K, L, true, pointwise_split_supported(L->m_pad, K, k1_split)))) return rc;
+  return upload_affine(h, sc, sh, L);
 }
 
 // [cout][cin][kernel] -> the implicit GEMM's [cout][kernel * cin] (k = tap * cin + c) -> the three fragment packs (fp32: no
 // fp32 pack)
 int pack_conv_data(vasr_handle* h, const float* w, const std::string& key, int cout, int cin, int kernel, ConvLayer* L,
                    bool fp32 = true, bool split = true) {
-  int rc;
   L->m_pad = (int)align_up(cout, 128);
   if (!conv_split_supported(L->m_pad, cin))
     return fail(VASR_ERR_UNSUPPORTED, "%s: in_channels %d of a %d-tap conv is not a multiple of 64", key.c_str(), cin, kernel);
@@ -400,18 +388,7 @@ int pack_conv_data(vasr_handle* h, const float* w, const std::string& key, int c
   L->conv_cin = cin;
   std::vector<float> g((size_t)cout * K);
   pack_conv_gemm_weights(w, cout, cin, kernel, g.data());
-  if (split) {
-    std::vector<unsigned short> w3((size_t)K * L->m_pad * 3);
-    pack_pointwise_weights_bf16x3(g.data(), cout, K, L->m_pad, w3.data());
-    if ((rc = upload(h, w3, &L->d_w3))) return rc;
-    std::vector<unsigned short> w16((size_t)K * L->m_pad * 2);
-    L->w16_inv = pack_pointwise_weights_f16x2(g.data(), cout, K, L->m_pad, w16.data());
-    if ((rc = upload(h, w16, &L->d_w16))) return rc;
-  }
-  if (!fp32) return 0;
-  std::vector<float> wt((size_t)K * L->m_pad, 0.f);
-  pack_pointwise_weights(g.data(), cout, K, L->m_pad, wt.data());
-  return upload(h, wt, &L->d_w);
+  return upload_packs(h, g.data(), cout, K, L, fp32, split);
 }
 
 int pack_conv(vasr_handle* h, const std::string& key, int cout, int cin, int kernel, ConvLayer* L) {
@@ -424,24 +401,12 @@ int pack_conv(vasr_handle* h, const std::string& key, int cout, int cin, int ker
 // [cout][cin][1] -> MFMA A-fragment order (fp32: no fp32 pack)
 int pack_pointwise_data(vasr_handle* h, const float* w, const std::string& key, int cout, int cin, ConvLayer* L,
                         bool fp32 = true, bool split = true) {
-  int rc;
   // (a K depth of 32 would select the 128 x 256 tile of the fp32 kernel, whose last time tile assumes a 256-frame pitch)
   if (cin % 64) return fail(VASR_ERR_UNSUPPORTED, "%s: in_channels %d is not a multiple of 64", key.c_str(), cin);
   L->cin = cin;
   L->cout = cout;
   L->m_pad = (int)align_up(cout, 128);
-  if (split && pointwise_split_supported(L->m_pad, cin, 0)) {
-    std::vector<unsigned short> w3((size_t)cin * L->m_pad * 3);
-    pack_pointwise_weights_bf16x3(w, cout, cin, L->m_pad, w3.data());
-    if ((rc = upload(h, w3, &L->d_w3))) return rc;
-    std::vector<unsigned short> w16((size_t)cin * L->m_pad * 2);
-    L->w16_inv = pack_pointwise_weights_f16x2(w, cout, cin, L->m_pad, w16.data());
-    if ((rc = upload(h, w16, &L->d_w16))) return rc;
-  }
-  if (!fp32) return 0;
-  std::vector<float> wt((size_t)cin * L->m_pad, 0.f);
-  pack_pointwise_weights(w, cout, cin, L->m_pad, wt.data());
-  return upload(h, wt, &L->d_w);
+  return upload_packs(h, w, cout, cin, L, fp32, split && pointwise_split_supported(L->m_pad, cin, 0));
 }
 
 int pack_pointwise(vasr_handle* h, const std::string& key, int cout, int cin, ConvLayer* L) {
@@ -492,9 +457,6 @@ int pack_grouped(vasr_handle* h, const std::string& key, const std::string& bn, 
   return 0;
 }
 
-// State-dict prefixes of block i's SqueezeExcite modules in the reference's construction order (parts/jasper.py:214-288):
-// with residual, entry 2 of every residual pane's list (conv, BN, SE); without, the entry after each sub-layer's conv + BN
-// (+ activation and dropout, except after the last one) -- which shifts the mconv indices of everything behind it.
 // ModuleList indices of block B's sub-layers (encoder.{i}.mconv.{j}) in the reference's construction order
 // (parts/jasper.py:214-288, :329-400): per sub-layer its conv -- a separable one's depthwise conv, then the 1x1 at conv + 1 --,
 // the BN, a GroupShuffle when groups > 1, activation + dropout except after the last sub-layer, and a SqueezeExcite when the
@@ -513,23 +475,33 @@ std::vector<SubKeys> mconv_layout(const Block& B) {
   return out;
 }
 
+// State-dict prefix of entry j of block i's main branch (mconv_layout), and of entry `entry` of its residual pane q's list:
+// 0 the 1x1 conv, 1 its BatchNorm or GroupNorm, 2 its SqueezeExcite (parts/jasper.py:264-288)
+std::string mconv_key(size_t i, int j) {
+  char key[64];
+  snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, j);
+  return key;
+}
+std::string res_key(size_t i, int q, int entry) {
+  char key[64];
+  snprintf(key, sizeof key, "encoder.%zu.res.%d.%d", i, q, entry);
+  return key;
+}
+// the 1x1 convs of block B's residual: one per pane a dense block sums, else one
+int residual_panes(const Block& B) { return B.dense_panes >= 2 ? B.dense_panes : 1; }
+
+// State-dict prefixes of block i's SqueezeExcite modules: with residual, entry 2 of every residual pane's list; without, the
+// entry after each sub-layer's conv + BN (+ activation and dropout, except after the last one) -- which shifts the mconv
+// indices of everything behind it
 std::vector<std::string> se_prefixes(const vasr_handle* h, size_t i) {
   const Block& B = h->blocks[i];
   std::vector<std::string> out;
   if (!B.se_r) return out;
-  char key[160];
   if (B.d.residual) {
-    const int panes = B.dense_panes >= 2 ? B.dense_panes : 1;
-    for (int q = 0; q < panes; ++q) {
-      snprintf(key, sizeof key, "encoder.%zu.res.%d.2", i, q);
-      out.push_back(key);
-    }
+    for (int q = 0; q < residual_panes(B); ++q) out.push_back(res_key(i, q, 2));
     return out;
   }
-  for (const SubKeys& k : mconv_layout(B)) {
-    snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, k.se);
-    out.push_back(key);
-  }
+  for (const SubKeys& k : mconv_layout(B)) out.push_back(mconv_key(i, k.se));
   return out;
 }
 
@@ -583,7 +555,6 @@ int check_groups(vasr_handle* h) {
         return fail(VASR_ERR_UNSUPPORTED, "block %zu: filters %d is not a multiple of 128", i, d.filters);
       const std::vector<SubKeys> lay = mconv_layout(B);
       int c = cin;
-      char key[160];
       const HostTensor* t;
       int rc;
       for (int r = 0; r < d.repeat; ++r) {
@@ -591,11 +562,11 @@ int check_groups(vasr_handle* h) {
           return fail(VASR_ERR_INVALID, "block %zu: groups %d does not divide in_channels %d and out_channels %d", i, G, c, d.filters);
         if (H > 0 && c % H)
           return fail(VASR_ERR_INVALID, "block %zu: heads %d does not divide the %d channels", i, H, c);
-        snprintf(key, sizeof key, "encoder.%zu.mconv.%d.conv.weight", i, lay[r].conv);
+        const std::string key = mconv_key(i, lay[r].conv) + ".conv.weight";
         if (d.separable) {
-          if ((rc = need_shape(h, key, {H > 0 ? H : c, 1, k}, &t))) return rc;
-          snprintf(key, sizeof key, "encoder.%zu.mconv.%d.conv.weight", i, lay[r].conv + 1);
-          if ((rc = need_shape(h, key, {d.filters, c / G, 1}, &t))) return rc;
+          if ((rc = need_shape(h, key, {H > 0 ? H : c, 1, k}, &t)) ||
+              (rc = need_shape(h, mconv_key(i, lay[r].conv + 1) + ".conv.weight", {d.filters, c / G, 1}, &t)))
+            return rc;
         } else if ((rc = need_shape(h, key, {d.filters, c / G, k}, &t))) {
           return rc;
         }
@@ -612,18 +583,9 @@ int check_groups(vasr_handle* h) {
 std::vector<std::string> norm_prefixes(const vasr_handle* h, size_t i) {
   const Block& B = h->blocks[i];
   std::vector<std::string> out;
-  char key[160];
-  for (const SubKeys& k : mconv_layout(B)) {
-    snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, k.bn);
-    out.push_back(key);
-  }
-  if (B.d.residual) {
-    const int panes = B.dense_panes >= 2 ? B.dense_panes : 1;
-    for (int q = 0; q < panes; ++q) {
-      snprintf(key, sizeof key, "encoder.%zu.res.%d.1", i, q);
-      out.push_back(key);
-    }
-  }
+  for (const SubKeys& k : mconv_layout(B)) out.push_back(mconv_key(i, k.bn));
+  if (B.d.residual)
+    for (int q = 0; q < residual_panes(B); ++q) out.push_back(res_key(i, q, 1));
   return out;
 }
 
@@ -713,16 +675,15 @@ int build_encoder(vasr_handle* h) {
     B.first_step = step;
     B.subs.resize(d.repeat);
     int c = cin;
-    char key[160];
     const std::vector<SubKeys> lay = mconv_layout(B);
     for (int r = 0; r < d.repeat; ++r) {
       SubBlock& S = B.subs[r];
-      const int j = lay[r].conv, jbn = lay[r].bn;
+      const int j = lay[r].conv;
+      const std::string bn = mconv_key(i, lay[r].bn);
       S.separable = d.separable != 0;
       if (S.separable) {
         const HostTensor* w;
-        snprintf(key, sizeof key, "encoder.%zu.mconv.%d.conv.weight", i, j);
-        if ((rc = need(h, key, (size_t)(B.heads > 0 ? B.heads : c) * k, &w))) return rc;
+        if ((rc = need(h, mconv_key(i, j) + ".conv.weight", (size_t)(B.heads > 0 ? B.heads : c) * k, &w))) return rc;
         // heads: the [H][1][K] weight shared by channel c % H (MaskedConv1d's view(-1, heads, T)), expanded to [C][K] here so
         // that every depthwise kernel, tap table and the fused kernel's taps see per-channel weights
         std::vector<float> dw_heads;
@@ -750,24 +711,18 @@ int build_encoder(vasr_handle* h) {
           S.dw.f_l1 = pack_fused_taps(dwv.data(), c, k, ft.data());
           if ((rc = upload(h, ft, &S.dw.d_ftaps))) return rc;
         }
-        snprintf(key, sizeof key, "encoder.%zu.mconv.%d.conv.weight", i, j + 1);
+        const std::string key = mconv_key(i, j + 1) + ".conv.weight";
         if (B.groups > 1) {
-          char bn[160];
-          snprintf(bn, sizeof bn, "encoder.%zu.mconv.%d", i, jbn);
           if ((rc = pack_grouped(h, key, bn, d.filters, c, 1, B.groups, false, &S.pw, &S.pw_bd, B.norm_g))) return rc;
         } else if ((rc = pack_pointwise(h, key, d.filters, c, &S.pw))) {
           return rc;
         }
         S.pw.step = step++;
         h->steps.push_back(LenStep{1, 1, 1, 0});
-        snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, jbn);
-        if (B.groups == 1 && (rc = conv_affine(h, B.norm_g, key, d.filters, S.pw.m_pad, &S.pw))) return rc;
       } else {
-        snprintf(key, sizeof key, "encoder.%zu.mconv.%d.conv.weight", i, j);
+        const std::string key = mconv_key(i, j) + ".conv.weight";
         const bool conv = !(k == 1 && d.stride == 1);   // K-tap / strided: implicit GEMM (encoder_pw_split.hip, encoder_pw.hip CONV)
         if (B.groups > 1) {
-          char bn[160];
-          snprintf(bn, sizeof bn, "encoder.%zu.mconv.%d", i, jbn);
           if ((rc = pack_grouped(h, key, bn, d.filters, c, k, B.groups, conv, &S.pw, &S.pw_bd, B.norm_g))) return rc;
         } else if ((rc = conv ? pack_conv(h, key, d.filters, c, k, &S.pw) : pack_pointwise(h, key, d.filters, c, &S.pw))) {
           return rc;
@@ -779,82 +734,62 @@ int build_encoder(vasr_handle* h) {
           h->steps.push_back(LenStep{1, 1, 1, 0});
         }
         S.pw.step = step++;
-        snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, jbn);
-        if (B.groups == 1 && (rc = conv_affine(h, B.norm_g, key, d.filters, S.pw.m_pad, &S.pw))) return rc;
       }
+      // (pack_grouped has folded a grouped layer's BN, in both of its forms)
+      if (B.groups == 1 && (rc = conv_affine(h, B.norm_g, bn, d.filters, S.pw.m_pad, &S.pw))) return rc;
       if (S.pw_bd.d_w) {          // the block-diagonal form runs the same geometry
         S.pw_bd.kernel = S.pw.kernel; S.pw_bd.stride = S.pw.stride; S.pw_bd.dilation = S.pw.dilation; S.pw_bd.pad = S.pw.pad;
         S.pw_bd.step = S.pw.step;
       }
-      if (B.norm_g) {            // GroupNorm entry, before the GroupShuffle: its channels are stored shuffled
-        snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, jbn);
-        const std::vector<int> perm = shuffle_perm(d.filters, B.groups);
-        if ((rc = load_norm(h, key, d.filters, B.norm_g, B.groups > 1 ? &perm : nullptr, &S.norm))) return rc;
-      }
-      if (lay[r].se >= 0) {      // SqueezeExcite entry (parts/jasper.py:233-234, :250-251)
-        snprintf(key, sizeof key, "encoder.%zu.mconv.%d", i, lay[r].se);
-        if ((rc = load_se(h, key, d.filters, B.se_r, &S.se))) return rc;
-      }
+      // GroupNorm entry, before the GroupShuffle: its channels are stored shuffled
+      if (B.norm_g && (rc = load_norm(h, bn, d.filters, B.norm_g, B.groups, &S.norm))) return rc;
+      // SqueezeExcite entry (parts/jasper.py:233-234, :250-251)
+      if (lay[r].se >= 0 && (rc = load_se(h, mconv_key(i, lay[r].se), d.filters, B.se_r, &S.se))) return rc;
       c = d.filters;
     }
     B.has_res = d.residual != 0;
-    if (B.has_res && B.se_r) {
-      // one SE per residual pane: the panes' 1x1 convs cannot be summed before their SEs, so each pane is its own GEMM
-      const std::vector<std::string> pre = se_prefixes(h, i);
-      B.res_se.resize(pre.size());
-      for (size_t q = 0; q < pre.size(); ++q)
-        if ((rc = load_se(h, pre[q], d.filters, B.se_r, &B.res_se[q]))) return rc;
-    }
-    if (B.has_res && B.norm_g) {
-      // one GroupNorm per residual pane (not grouped, not shuffled)
-      const int panes = B.dense_panes >= 2 ? B.dense_panes : 1;
-      B.res_norm.resize(panes);
-      for (int q = 0; q < panes; ++q) {
-        snprintf(key, sizeof key, "encoder.%zu.res.%d.1", i, q);
-        if ((rc = load_norm(h, key, d.filters, B.norm_g, nullptr, &B.res_norm[q]))) return rc;
-      }
-    }
-    // (max mode: the panes are combined by max, which one GEMM over all of them cannot do)
-    if (B.has_res && (B.se_r || B.norm_g || h->res_max) && B.dense_panes >= 2) {
-      B.res_panes.resize(B.dense_panes);
-      for (int q = 0; q < B.dense_panes; ++q) {
-        const Block& P = h->blocks[i - B.dense_panes + 1 + q];
-        snprintf(key, sizeof key, "encoder.%zu.res.%d.0.conv.weight", i, q);
-        if ((rc = pack_pointwise(h, key, d.filters, P.pane_c, &B.res_panes[q]))) return rc;
-        snprintf(key, sizeof key, "encoder.%zu.res.%d.1", i, q);
-        if ((rc = conv_affine(h, B.norm_g, key, d.filters, B.res_panes[q].m_pad, &B.res_panes[q]))) return rc;
-        B.res_pane_off.push_back(P.pane_off);
-      }
-    } else if (B.has_res && B.dense_panes >= 2) {
+    // with SE or GroupNorm a dense residual's panes cannot be summed before those, so each pane is its own GEMM (max mode: the
+    // panes are combined by max, which one GEMM over all of them cannot do)
+    const bool per_pane = (B.se_r || B.norm_g || h->res_max) && B.dense_panes >= 2;
+    if (B.has_res && B.dense_panes >= 2 && !per_pane) {
       // dense residual: one GEMM over the run's first dense_panes panes (parts/jasper.py:428-439 for each pane)
       std::vector<SumSrc> src;
-      for (int q = 0; q < B.dense_panes; ++q) {
-        char wk[160], bk[160];
-        snprintf(wk, sizeof wk, "encoder.%zu.res.%d.0.conv.weight", i, q);
-        snprintf(bk, sizeof bk, "encoder.%zu.res.%d.1", i, q);
-        src.push_back(SumSrc{wk, bk, h->blocks[i - B.dense_panes + 1 + q].pane_c});
-      }
+      for (int q = 0; q < B.dense_panes; ++q)
+        src.push_back(SumSrc{res_key(i, q, 0) + ".conv.weight", res_key(i, q, 1), h->blocks[i - B.dense_panes + 1 + q].pane_c});
       for (const SumSrc& s : src)
         if (s.k % 64) return fail(VASR_ERR_UNSUPPORTED, "%s: in_channels %d is not a multiple of 64", s.w_key.c_str(), s.k);
-      if ((rc = pack_sum_1x1(h, src, d.filters, 0, &B.res))) return rc;
+      B.res.resize(1);
+      B.res[0].pane_off = 0;
+      if ((rc = pack_sum_1x1(h, src, d.filters, 0, &B.res[0].w))) return rc;
     } else if (B.has_res) {
-      snprintf(key, sizeof key, "encoder.%zu.res.0.0.conv.weight", i);
-      if ((rc = pack_pointwise(h, key, d.filters, cin, &B.res))) return rc;
-      snprintf(key, sizeof key, "encoder.%zu.res.0.1", i);
-      if ((rc = conv_affine(h, B.norm_g, key, d.filters, B.res.m_pad, &B.res))) return rc;
+      B.res.resize(residual_panes(B));
+      for (int q = 0; q < (int)B.res.size(); ++q) {
+        ResGemm& G = B.res[q];
+        int k2 = cin;
+        if (per_pane) {
+          const Block& P = h->blocks[i - B.dense_panes + 1 + q];
+          k2 = P.pane_c;
+          G.pane_off = P.pane_off;
+        } else if (B.res_pane0) {
+          G.pane_off = 0;
+        }
+        // conv, its BN or GroupNorm (not grouped, not shuffled), its SE
+        if ((rc = pack_pointwise(h, res_key(i, q, 0) + ".conv.weight", d.filters, k2, &G.w)) ||
+            (rc = conv_affine(h, B.norm_g, res_key(i, q, 1), d.filters, G.w.m_pad, &G.w)) ||
+            (B.norm_g && (rc = load_norm(h, res_key(i, q, 1), d.filters, B.norm_g, 1, &G.norm))) ||
+            (B.se_r && (rc = load_se(h, res_key(i, q, 2), d.filters, B.se_r, &G.se))))
+          return rc;
+      }
       // fold the residual branch into the last sub-block's GEMM when both reductions tile evenly
       const SubBlock& last = B.subs.back();
       const int k1 = last.pw.cin, k2 = cin;
       const int chunk = d.filters % 512 == 0 ? 128 : (d.filters % 256 == 0 ? 64 : 32);
       // (grouped blocks: the main branch's grouped reduction and the residual's dense one share no K)
-      if (d.stride == 1 && k1 % chunk == 0 && k2 % chunk == 0 && h->sw.fused_residual && !last.pw.conv_cin && !B.res_pane0 &&
-          !B.se_r && B.groups == 1 && !B.norm_g && !h->res_max) {   // (the fold sums: add mode only)
-        char w1[160], bn1[160], w2[160], bn2[160];
-        snprintf(w1, sizeof w1, "encoder.%zu.mconv.%d.conv.weight", i, lay.back().conv + (last.separable ? 1 : 0));
-        snprintf(bn1, sizeof bn1, "encoder.%zu.mconv.%d", i, lay.back().bn);
-        snprintf(w2, sizeof w2, "encoder.%zu.res.0.0.conv.weight", i);
-        snprintf(bn2, sizeof bn2, "encoder.%zu.res.0.1", i);
-        if ((rc = pack_sum_1x1(h, {SumSrc{w1, bn1, k1}, SumSrc{w2, bn2, k2}}, d.filters, k1, &B.fused))) return rc;
+      if (d.stride == 1 && k1 % chunk == 0 && k2 % chunk == 0 && h->sw.fused_residual && !last.pw.conv_cin &&
+          !B.res_pane0 && !B.se_r && B.groups == 1 && !B.norm_g && !h->res_max) {   // (the fold sums: add mode only)
+        const SumSrc s1{mconv_key(i, lay.back().conv + (last.separable ? 1 : 0)) + ".conv.weight", mconv_key(i, lay.back().bn), k1};
+        const SumSrc s2{res_key(i, 0, 0) + ".conv.weight", res_key(i, 0, 1), k2};
+        if ((rc = pack_sum_1x1(h, {s1, s2}, d.filters, k1, &B.fused))) return rc;
         B.fused_res = true;
         B.fused_k1 = k1;
       }
@@ -878,8 +813,7 @@ int build_decoder(vasr_handle* h) {
   if ((rc = need(h, "decoder_layers.0.bias", h->num_classes, &b))) return rc;
   std::vector<float> sc(h->dec.m_pad, 1.f), sh(h->dec.m_pad, 0.f);
   for (int i = 0; i < h->num_classes; ++i) sh[i] = b->data[i];
-  if ((rc = upload(h, sc, &h->dec.d_scale))) return rc;
-  return upload(h, sh, &h->dec.d_shift);
+  return upload_affine(h, sc, sh, &h->dec);
 }
 
 // ---------------- workspace plan ----------------
@@ -988,16 +922,9 @@ struct ProfScope {
 };
 enum { kProfFrontend = 0, kProfDepthwise = 1, kProfPointwise = 2, kProfHead = 3, kProfFused = 4 };
 
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(VASR_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
-  return 0;
-}
-
 // GEMM dispatch: exact-fp32 MFMA kernel, or the 3 x bf16 split kernel when selected and the layer has that pack.
 // Returns 1 when the launch published a.amax_y (only the split kernel does), 0 when not, < 0 on error.
-static int run_pointwise(vasr_handle* h, PwArgs& a, const ConvLayer& W, hipStream_t st) {
+int run_pointwise(vasr_handle* h, PwArgs& a, const ConvLayer& W, hipStream_t st) {
   if (h->gemm_mode >= 1 && W.d_w3) {
     int arith = h->gemm_mode == 2 ? 1 : 0;
     a.wt = reinterpret_cast<const float*>(W.d_w3);
@@ -1014,6 +941,49 @@ static int run_pointwise(vasr_handle* h, PwArgs& a, const ConvLayer& W, hipStrea
   a.wt = W.d_w;
   launch_pointwise(a, st);
   return 0;
+}
+
+// pw_args (vasr_host.h) of layer W's fp32 pack (run_pointwise picks the pack that runs) over a padded internal tensor
+PwArgs pw_args(const vasr_handle* h, const ConvLayer& W, const float* x, float* y, int64_t ld, int64_t frames, int batch) {
+  PwArgs a = vasr::pw_args(W.d_w, W.d_scale, W.d_shift, W.m_pad, W.cin, x, y, ld, frames, batch);
+  a.busy_cus = h->busy_cus;
+  return a;
+}
+
+// Whether a 256-channel separable sub-block of a batch [B][256][ld] takes the fused depthwise -> pointwise kernel
+// (encoder_fused.hip), and on which tile: 128 or 64 frames per workgroup, 0 = depthwise and GEMM as two kernels.  It does when
+// there are enough 128-frame tiles to fill the chip (one workgroup per tile, all channels); VASR_FUSED=0 is the A/B switch.
+int fused_tile_cols(const vasr_handle* h, int batch, int64_t ld) {
+  if (!h->sw.fused) return 0;
+  // One workgroup per CU (159 KB of LDS), one 128-frame tile each: it pays when the tiles fill whole rounds of the chip
+  // (measured, fused vs two kernels: 64 x 10 s = 256 tiles -3.4 % per step, 512 x 30 s = 6144 tiles -4 %; but 32 x 10 s = 128
+  // tiles +2.6 %, 64 x 10.3 s = 320 tiles = 1.25 rounds +3 %, 16 x 10 s = 64 tiles +4.6 %).  Smaller batches take the kernel's
+  // 64-frame form (round 4) while THOSE tiles fit one round and occupy at least 3/8 of the chip -- 12 to 32 utterances of
+  // 10 s; measured against two kernels, ms per step: 15x5 B = 12 / 16 / 20 / 24 / 32: -3.8 / -4.8 / -8.3 / -7.7 / -6.7 %, 12x1
+  // (BASELINE configs[1]) B = 16 / 20 / 24 / 32: -3.1 / -5.1 / -5.0 / -4.3 %; B = 8: +-0; B = 1-4: +5 ... +9 % (one tile is 14 us
+  // of latency against 4 + 7 us for the two kernels spread over the chip); 36-44 utterances (1.1-1.4 rounds): +0.8 ... +1.6 %.
+  const int fused_min_tiles = h->sw.fused_min_tiles, fused_tile = h->sw.fused_tile;
+  const int n_cu = h->n_cu;
+  // (units a concurrent kernel of the caller's holds -- the overlapped beam search -- take no workgroups: 256 tiles on the
+  // 192 CUs a 64-utterance search leaves free are 1.33 rounds)
+  const int f_cus = h->busy_cus > 0 && h->busy_cus < n_cu - 32 ? n_cu - h->busy_cus : n_cu;
+  const int64_t f_tiles = (int64_t)batch * (ld / kTimeTile);
+  // WHETHER a sub-block is fused is a function of the batch's shape ALONE (the whole chip's unit count): the fused and the
+  // two-kernel form round differently, and the busy-unit hint follows a concurrent kernel's progress -- with the hint in this
+  // decision the log-probs of one and the same batch depended on whether the previous search had finished (round 6,
+  // tests/devtools/stress_beam_overlap.py: 196 of 11 594 overlapped batches differed from their serial run).  The hint only
+  // picks the TILE WIDTH of a sub-block that is fused anyway: 64- and 128-frame tiles give the same bits.
+  const int f_rule = fused_tile_choice(f_tiles, n_cu);
+  int f_auto = f_rule ? f_rule : 128;
+  if (f_rule && f_cus < n_cu) {
+    // lock-stepped rounds on the free units: a 64-frame tile costs ~0.6 of a 128-frame one (17 vs 29.7 us a round); 256 tiles on
+    // the 192 units a 64-utterance search leaves: 2 rounds of 128 frames = 2.0 against 3 rounds of 64 = 1.8
+    const int64_t r128 = (f_tiles + f_cus - 1) / f_cus, r64 = (2 * f_tiles + f_cus - 1) / f_cus;
+    f_auto = 0.6 * (double)r64 < (double)r128 ? 64 : 128;
+  }
+  const bool f_fill = fused_min_tiles > 0 ? f_tiles >= fused_min_tiles : (fused_tile ? f_rule == fused_tile : f_rule != 0);
+  if (!f_fill) return 0;
+  return fused_tile == 64 || fused_tile == 128 ? fused_tile : f_auto;
 }
 
 // Encoder over an input [B][feat_in][x_ld]; writes [B][c_last][out_ld] (T1 valid frames).
@@ -1118,137 +1088,65 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
     }
     // residual panes' masks: the block input lengths; a last block's residual keeps its padding columns (the encoder output's)
     const int32_t* res_zero = last_block ? nullptr : lens(B.first_step);
-    if (B.has_res && (B.se_r || B.norm_g || h->res_max) && B.dense_panes >= 2) {
-      // dense residual with SE or GroupNorm, or combined by max: sum_p (max_p) SE_p(N_p(W_p mask(x_p))) (parts/jasper.py:428-441)
-      // -- pane 0's GEMM writes R and is normalized / rescaled in place, every later pane's goes through D and is combined
-      // onto R by its last pass; max without SE: every later pane's GEMM takes max(R, its result) into R itself (each element
-      // of R is read and then stored by the one thread that owns it, encoder_pw*.hip)
-      const int acc_mode = h->res_max ? 2 : 1;
-      for (int q = 0; q < B.dense_panes; ++q) {
-        const ConvLayer& W = B.res_panes[q];
-        const bool gemm_max = h->res_max && !B.se_r && q > 0;
-        float* Rq = (q == 0 || gemm_max) ? R : D;
-        const float* px = panes + (int64_t)B.res_pane_off[q] * cur_ld;
-        PwArgs a{};
-        a.busy_cus = h->busy_cus;
-        a.wt = W.d_w; a.x = px; a.bsx = pane_bs; a.lens = lens(B.first_step); a.scale = W.d_scale; a.shift = W.d_shift;
-        a.res = nullptr; a.y = Rq; a.M = W.m_pad; a.K = W.cin; a.batch = batch;
-        a.ldx = cur_ld; a.ldy = cur_ld; a.ldr = 0; a.frames = (int)cur_T; a.store_cols = (int)cur_ld;
-        a.m_store = W.m_pad; a.relu = 0;
-        if (gemm_max) { a.res = R; a.ldr = cur_ld; a.res_max = 1; }
-        if (want_amax) {
+    // The residual branch, sum_p (max_p) SE_p(N_p(BN_p(W_p mask(x_p)))) over the block's residual GEMMs (parts/jasper.py:428-441),
+    // every source masked with the block-input lengths -- unless it is folded into the last sub-block's GEMM.  Entry 0's GEMM
+    // writes R and is normalized / rescaled in place, every later one's goes through D and is combined onto R by its last pass;
+    // max without SE: every later GEMM takes max(R, its result) into R itself (each element of R is read and then stored by
+    // the one thread that owns it, encoder_pw*.hip)
+    for (size_t q = 0; q < B.res.size() && !B.fused_res; ++q) {
+      const ResGemm& G = B.res[q];
+      const ConvLayer& W = G.w;
+      const bool gemm_max = h->res_max && !G.se.d_w1 && q > 0;
+      float* Rq = (q == 0 || gemm_max) ? R : D;
+      // the block input -- or panes of the dense run: its own panes, or, right after the run, the run's input (pane 0)
+      const float* px = G.pane_off >= 0 ? panes + (int64_t)G.pane_off * cur_ld : cur;
+      PwArgs a = pw_args(h, W, px, Rq, cur_ld, cur_T, batch);
+      a.lens = lens(B.first_step);
+      if (gemm_max) { a.res = R; a.ldr = cur_ld; a.res_max = 1; }
+      if (G.pane_off < 0) {
+        a.amax_x = blk_amax;
+      } else {
+        a.bsx = pane_bs;
+        if (want_amax) {   // fp16 split: one scale from the maxima of all the channels the GEMM reads
           a.amax_x = free_tab(AmaxTab{});
           launch_amax(px, cur_ld, W.cin, (int)cur_T, lens(B.first_step), batch, &a.amax_x, st, pane_bs);
         }
-        {
-          ProfScope ps(h, kProfPointwise, st, 2.0 * W.cin * W.cout * (double)cur_T * batch, 4.0 * W.m_pad * (double)cur_ld * batch);
-          if (run_pointwise(h, a, W, st) < 0) return VASR_ERR_HIP;
-        }
-        if (B.norm_g && run_norm(B.res_norm[q], Rq, B.se_r ? Rq : R, (!B.se_r && q > 0) ? R : nullptr, cur_ld, cur_ld, cur_T,
-                                 (int)cur_ld, lens(B.first_step), res_zero, 0, nullptr, nullptr))
-          return VASR_ERR_HIP;
-        if (B.se_r && run_se(B.res_se[q], Rq, R, cur_ld, cur_T, (int)cur_ld, lens(B.first_step), res_zero, 0,
-                             q > 0 ? acc_mode : 0, nullptr, nullptr))
-          return VASR_ERR_HIP;
-      }
-    } else if (B.has_res && B.dense_panes >= 2) {
-      // dense residual: sum_p BN_p(W_p mask(x_p)) as one GEMM over the first res.cin channels of the pane buffer, every pane
-      // masked with the block-input lengths (parts/jasper.py:428-436); fp16 split: one scale from the maxima of all panes
-      PwArgs a{};
-      a.busy_cus = h->busy_cus;
-      a.wt = B.res.d_w; a.x = panes; a.bsx = pane_bs; a.lens = lens(B.first_step); a.scale = B.res.d_scale;
-      a.shift = B.res.d_shift; a.res = nullptr; a.y = R; a.M = B.res.m_pad; a.K = B.res.cin; a.batch = batch;
-      a.ldx = cur_ld; a.ldy = cur_ld; a.ldr = 0; a.frames = (int)cur_T; a.store_cols = (int)cur_ld;
-      a.m_store = B.res.m_pad; a.relu = 0;
-      if (want_amax) {
-        a.amax_x = free_tab(AmaxTab{});
-        launch_amax(panes, cur_ld, B.res.cin, (int)cur_T, lens(B.first_step), batch, &a.amax_x, st, pane_bs);
-      }
-      ProfScope ps(h, kProfPointwise, st, 2.0 * B.res.cin * B.res.cout * (double)cur_T * batch, 4.0 * B.res.m_pad * (double)cur_ld * batch);
-      if (run_pointwise(h, a, B.res, st) < 0) return VASR_ERR_HIP;
-    } else if (B.has_res && !B.fused_res) {
-      // res branch: MaskedConv1d(1x1)(block input -- or, right after a dense run, the run's input: pane 0 --, lens_orig) -> BN
-      // (parts/jasper.py:428-436)
-      PwArgs a{};
-      a.busy_cus = h->busy_cus;
-      a.wt = B.res.d_w; a.x = B.res_pane0 ? panes : cur; a.lens = lens(B.first_step); a.scale = B.res.d_scale; a.shift = B.res.d_shift;
-      a.res = nullptr; a.y = R; a.M = B.res.m_pad; a.K = B.res.cin; a.batch = batch;
-      a.ldx = cur_ld; a.ldy = cur_ld; a.ldr = 0; a.frames = (int)cur_T; a.store_cols = (int)cur_ld;
-      a.m_store = B.res.m_pad; a.relu = 0;
-      a.amax_x = blk_amax;
-      if (B.res_pane0) {
-        a.bsx = pane_bs;
-        a.amax_x = AmaxTab{};
-        if (want_amax) {
-          a.amax_x = free_tab(AmaxTab{});
-          launch_amax(panes, cur_ld, B.res.cin, (int)cur_T, lens(B.first_step), batch, &a.amax_x, st, pane_bs);
-        }
       }
       {
-        ProfScope ps(h, kProfPointwise, st, 2.0 * B.res.cin * B.res.cout * (double)cur_T * batch,
-                     4.0 * B.res.m_pad * (double)cur_ld * batch);   // bytes of class 2 = what the GEMM STORES (its epilogue's share of the time)
-        if (run_pointwise(h, a, B.res, st) < 0) return VASR_ERR_HIP;
+        ProfScope ps(h, kProfPointwise, st, 2.0 * W.cin * W.cout * (double)cur_T * batch,
+                     4.0 * W.m_pad * (double)cur_ld * batch);   // bytes of class 2 = what the GEMM STORES (its epilogue's share of the time)
+        if (run_pointwise(h, a, W, st) < 0) return VASR_ERR_HIP;
       }
-      // GroupNorm, then (se and residual) the residual branch's SqueezeExcite, in place on R (parts/jasper.py:275-280)
-      if (B.norm_g && run_norm(B.res_norm[0], R, R, nullptr, cur_ld, cur_ld, cur_T, (int)cur_ld, lens(B.first_step), res_zero, 0,
-                               nullptr, nullptr))
+      // GroupNorm, then the residual branch's SqueezeExcite (parts/jasper.py:275-280)
+      if (G.norm.d_gamma && run_norm(G.norm, Rq, G.se.d_w1 ? Rq : R, (!G.se.d_w1 && q > 0) ? R : nullptr, cur_ld, cur_ld, cur_T,
+                                     (int)cur_ld, lens(B.first_step), res_zero, 0, nullptr, nullptr))
         return VASR_ERR_HIP;
-      if (B.se_r && run_se(B.res_se[0], R, R, cur_ld, cur_T, (int)cur_ld, lens(B.first_step),
-                           last_block ? nullptr : lens(B.first_step), 0, 0, nullptr, nullptr))
+      if (G.se.d_w1 && run_se(G.se, Rq, R, cur_ld, cur_T, (int)cur_ld, lens(B.first_step), res_zero, 0,
+                              q > 0 ? (h->res_max ? 2 : 1) : 0, nullptr, nullptr))
         return VASR_ERR_HIP;
     }
     int flip = 0;
     for (size_t r = 0; r < B.subs.size(); ++r) {
       SubBlock& S = B.subs[r];
       const bool last_sub = r + 1 == B.subs.size();
+      const bool enc_out = last_block && last_sub;   // this sub-layer writes the encoder output
       const float* gx = cur;
       int64_t gx_ld = cur_ld, g_T = cur_T;
       const int32_t* g_lens = nullptr;
       AmaxTab gx_amax = cur_amax;
-      // ---- fused depthwise -> pointwise kernel (encoder_fused.hip): 256-channel sub-blocks in the fp16-split arithmetic, when
-      //      there are enough 128-frame tiles to fill the chip (one workgroup per tile, all channels); VASR_FUSED=0 is the
-      //      A/B switch ----
-      const bool fused_on = h->sw.fused;
-      // One workgroup per CU (159 KB of LDS), one 128-frame tile each: it pays when the tiles fill whole rounds of the chip
-      // (measured, fused vs two kernels: 64 x 10 s = 256 tiles -3.4 % per step, 512 x 30 s = 6144 tiles -4 %; but 32 x 10 s = 128
-      // tiles +2.6 %, 64 x 10.3 s = 320 tiles = 1.25 rounds +3 %, 16 x 10 s = 64 tiles +4.6 %).  Smaller batches take the kernel's
-      // 64-frame form (round 4) while THOSE tiles fit one round and occupy at least 3/8 of the chip -- 12 to 32 utterances of
-      // 10 s; measured against two kernels, ms per step: 15x5 B = 12 / 16 / 20 / 24 / 32: -3.8 / -4.8 / -8.3 / -7.7 / -6.7 %, 12x1
-      // (BASELINE configs[1]) B = 16 / 20 / 24 / 32: -3.1 / -5.1 / -5.0 / -4.3 %; B = 8: +-0; B = 1-4: +5 ... +9 % (one tile is 14 us
-      // of latency against 4 + 7 us for the two kernels spread over the chip); 36-44 utterances (1.1-1.4 rounds): +0.8 ... +1.6 %.
-      const int fused_min_tiles = h->sw.fused_min_tiles, fused_tile = h->sw.fused_tile;
-      const int n_cu = h->n_cu;
-      // (units a concurrent kernel of the caller's holds -- the overlapped beam search -- take no workgroups: 256 tiles on the
-      // 192 CUs a 64-utterance search leaves free are 1.33 rounds)
-      const int f_cus = h->busy_cus > 0 && h->busy_cus < n_cu - 32 ? n_cu - h->busy_cus : n_cu;
-      const int64_t f_tiles = (int64_t)batch * (cur_ld / kTimeTile);
-      // WHETHER a sub-block is fused is a function of the batch's shape ALONE (the whole chip's unit count): the fused and the
-      // two-kernel form round differently, and the busy-unit hint follows a concurrent kernel's progress -- with the hint in this
-      // decision the log-probs of one and the same batch depended on whether the previous search had finished (round 6,
-      // tests/devtools/stress_beam_overlap.py: 196 of 11 594 overlapped batches differed from their serial run).  The hint only
-      // picks the TILE WIDTH of a sub-block that is fused anyway: 64- and 128-frame tiles give the same bits.
-      const int f_rule = fused_tile_choice(f_tiles, n_cu);
-      int f_auto = f_rule ? f_rule : 128;
-      if (f_rule && f_cus < n_cu) {
-        // lock-stepped rounds on the free units: a 64-frame tile costs ~0.6 of a 128-frame one (17 vs 29.7 us a round); 256 tiles on
-        // the 192 units a 64-utterance search leaves: 2 rounds of 128 frames = 2.0 against 3 rounds of 64 = 1.8
-        const int64_t r128 = (f_tiles + f_cus - 1) / f_cus, r64 = (2 * f_tiles + f_cus - 1) / f_cus;
-        f_auto = 0.6 * (double)r64 < (double)r128 ? 64 : 128;
-      }
-      const int f_cols = fused_tile == 64 || fused_tile == 128 ? fused_tile : f_auto;
-      const bool f_fill = fused_min_tiles > 0 ? f_tiles >= fused_min_tiles : (fused_tile ? f_rule == fused_tile : f_rule != 0);
+      // ---- fused depthwise -> pointwise kernel (encoder_fused.hip): 256-channel sub-blocks in the fp16-split arithmetic ----
+      int f_cols = 0;
       const bool fuse_res = last_sub && B.fused_res;
       const ConvLayer& WF = fuse_res ? B.fused : S.pw;
       // (not in row-independent mode: whether a sub-block is fused depends on the batch's tile count, and the two forms
       // round differently -- that mode promises bit-identical rows whatever the batch)
       // (a sub-layer whose output feeds an SE: the fused kernel does not produce its row sums)
-      if (fused_on && !h->row_independent && S.separable && S.dw.d_ftaps && h->gemm_mode == 3 && want_amax && cur_amax.p && WF.d_w16 &&
+      if (!h->row_independent && S.separable && S.dw.d_ftaps && h->gemm_mode == 3 && want_amax && cur_amax.p && WF.d_w16 &&
           !S.se.d_w1 && B.groups == 1 && !S.norm.d_gamma &&   // (no grouped form of the fused kernel, no raw store)
           !(last_sub && B.has_res && !B.fused_res) &&
           // a folded residual must come from a 256-channel block input (K = 256 + 256): the kernel's second K range is 4 chunks
           (fuse_res ? (blk_amax.p && blk_ld == cur_ld && WF.cin == 2 * S.dw.cin && B.fused_k1 == S.dw.cin) : WF.cin == S.dw.cin) &&
-          cur_ld % kTimeTile == 0 && f_fill &&
-          !(last_block && last_sub)) {
+          cur_ld % kTimeTile == 0 && !enc_out && (f_cols = fused_tile_cols(h, batch, cur_ld)) != 0) {
         float* dst = free3[flip];
         flip ^= 1;
         FusedLaunch f{};
@@ -1310,19 +1208,16 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
       flip ^= 1;
       // (a K-tap conv's output has its own pitch: stride 2 halves the frames)
       int64_t dst_ld = S.pw.conv_cin ? pad_frames(g_T) : gx_ld;
-      if (last_block && last_sub) { dst = out; dst_ld = out_ld; }
-      const bool fuse = last_sub && B.fused_res;
+      if (enc_out) { dst = out; dst_ld = out_ld; }
       // a grouped layer in the fp32 mode: its block-diagonal form (encoder_pw.hip has no grouped kernel)
-      const ConvLayer& W = fuse ? B.fused : (S.pw.groups > 1 && h->gemm_mode == 0 ? S.pw_bd : S.pw);
-      PwArgs a{};
+      const ConvLayer& W = fuse_res ? B.fused : (S.pw.groups > 1 && h->gemm_mode == 0 ? S.pw_bd : S.pw);
+      PwArgs a = pw_args(h, W, gx, dst, gx_ld, g_T, batch);
       a.groups = W.groups;
-      a.busy_cus = h->busy_cus;
-      a.wt = W.d_w; a.x = gx; a.lens = g_lens; a.scale = W.d_scale; a.shift = W.d_shift;
+      a.lens = g_lens;
       // (a normalized block: the GEMM stores its raw output, the GroupNorm pass adds the residual)
       const bool nrm = S.norm.d_gamma != nullptr;
       a.res = (last_sub && B.has_res && !B.fused_res && !nrm) ? R : nullptr;
-      a.y = dst; a.M = W.m_pad; a.K = W.cin; a.batch = batch;
-      a.ldx = gx_ld; a.ldy = dst_ld; a.ldr = blk_ld; a.frames = (int)g_T; a.m_store = W.m_pad;
+      a.ldy = dst_ld; a.ldr = blk_ld;
       // se and not residual: the last sub-layer's SE comes before the block's output activation (parts/jasper.py:250-251, mout)
       const int act = (last_sub && S.se.d_w1) ? 0 : 1;
       a.relu = nrm ? 0 : act;
@@ -1335,16 +1230,16 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
       }
       // the depthwise output is zero past its lens_out, a masked input past its mask: tiles out there skip their K loop
       a.zero_from = S.separable ? lens(S.dw.step + 1) : g_lens;
-      if (fuse) { a.x2 = blk_in; a.lens2 = lens(B.first_step); a.K1 = B.fused_k1; a.ldx2 = blk_ld; }
-      if ((a.res || fuse || (nrm && last_sub && B.has_res)) && (blk_ld != gx_ld || (W.conv_cin && g_T != cur_T)))
+      if (fuse_res) { a.x2 = blk_in; a.lens2 = lens(B.first_step); a.K1 = B.fused_k1; a.ldx2 = blk_ld; }
+      if ((a.res || fuse_res || (nrm && last_sub && B.has_res)) && (blk_ld != gx_ld || (W.conv_cin && g_T != cur_T)))
         return fail(VASR_ERR_UNSUPPORTED, "block %zu: residual across a strided block", i);
       a.amax_x = gx_amax;
-      a.amax_x2 = fuse ? blk_amax : AmaxTab{};
+      a.amax_x2 = fuse_res ? blk_amax : AmaxTab{};
       // this GEMM's output is masked at lens(S.pw.step + 1) by whatever reads it next
       // (the encoder output's maxima are only wanted by the fused path's CTC head, which reads every column < T')
-      if (want_amax && (!(last_block && last_sub) || enc_amax)) {
+      if (want_amax && (!enc_out || enc_amax)) {
         a.amax_y = free_tab(gx_amax);
-        a.lens_y = (last_block && last_sub) ? own_tab : lens(S.pw.step + 1);
+        a.lens_y = enc_out ? own_tab : lens(S.pw.step + 1);
       }
       int published;
       {
@@ -1355,7 +1250,6 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
       // GroupNorm of the conv's output over its own lengths, then the activation (the last sub-layer's: after the residual
       // sum, or after its SE); the normalized tensor's maxima replace the ones the GEMM published
       if (nrm) {
-        const bool enc_out = last_block && last_sub;
         if (run_norm(S.norm, dst, dst, (last_sub && B.has_res) ? R : nullptr, dst_ld, blk_ld, g_T, a.store_cols,
                      lens(S.pw.step + 1), enc_out ? nullptr : lens(S.pw.step + 1), act, published ? &a.amax_y : nullptr,
                      a.lens_y))
@@ -1364,7 +1258,6 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
       // se and not residual: SE after the sub-layer, pooled over the conv's output lengths; the rescaled tensor's maxima
       // replace the ones the GEMM published
       if (S.se.d_w1) {
-        const bool enc_out = last_block && last_sub;
         if (run_se(S.se, dst, dst, dst_ld, g_T, a.store_cols, lens(S.pw.step + 1), enc_out ? nullptr : lens(S.pw.step + 1),
                    last_sub ? 1 : 0, 0, published ? &a.amax_y : nullptr, a.lens_y))
           return VASR_ERR_HIP;
@@ -1379,13 +1272,9 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
 
 int run_decoder(vasr_handle* h, const float* encp, int64_t ld, int64_t T1, int batch, float* logits, float* logp,
                 int64_t* pred, hipStream_t st, AmaxTab enc_amax = AmaxTab{}, const int32_t* own_frames = nullptr) {
-  PwArgs a{};
-  a.busy_cus = h->busy_cus;
-  // own_frames (row-independent mode): columns past the row's own frame count are read as zero
-  a.wt = h->dec.d_w; a.x = encp; a.lens = own_frames; a.scale = h->dec.d_scale; a.shift = h->dec.d_shift;
-  a.res = nullptr; a.y = logits; a.M = h->dec.m_pad; a.K = h->dec.cin; a.batch = batch;
-  a.ldx = ld; a.ldy = ld; a.ldr = 0; a.frames = (int)T1; a.store_cols = (int)ld; a.m_store = h->num_classes;
-  a.relu = 0;
+  PwArgs a = pw_args(h, h->dec, encp, logits, ld, T1, batch);
+  a.lens = own_frames;   // (row-independent mode): columns past the row's own frame count are read as zero
+  a.m_store = h->num_classes;
   ProfScope ps(h, kProfHead, st);
   // split GEMM unless fp32 mode is selected: the fp16 form when the encoder published its output's maxima (fused path),
   // else 3 x bf16 (port tensors of the per-module entry point carry none)
@@ -1403,22 +1292,18 @@ const char* vasr_last_error(void) { return g_err.c_str(); }
 const char* vasr_version(void) { return "vasr-hip 0.4 (gfx950)"; }
 int vasr_abi_version(void) { return VASR_ABI_VERSION; }
 int64_t vasr_padded_frames(int64_t frames) { return pad_frames(frames); }
-#ifdef VASR_DEVTOOLS
-int vasr_fused_tile_choice(int64_t tiles128, int compute_units) { return vasr::fused_tile_choice(tiles128, compute_units); }
-#endif
 
 int vasr_create(const vasr_model_desc* d, vasr_handle** out) {
   if (!d || !out) return fail(VASR_ERR_INVALID, "null argument");
-  auto* h = new vasr_handle();
+  std::unique_ptr<vasr_handle> owner(new vasr_handle());   // freed on every refusal below
+  vasr_handle* h = owner.get();
   if (d->frontend) {
     const vasr_frontend_desc& fe = *d->frontend;
     if (fe.n_fft != 512 || fe.n_mels != 64) {
-      delete h;
       return fail(VASR_ERR_UNSUPPORTED, "front end supports n_fft=512, n_mels=64 (got %d, %d)", fe.n_fft, fe.n_mels);
     }
     if (fe.win_length <= 0 || fe.win_length > fe.n_fft || fe.hop_length <= 0 || fe.hop_length > 512 ||
         !fe.h_filterbank) {
-      delete h;
       // FilterbankFeatures.__init__ raises ValueError for non-positive window sizes (features.py:137-149)
       return fail(VASR_ERR_INVALID, "invalid window/hop/filterbank in front-end description");
     }
@@ -1433,13 +1318,12 @@ int vasr_create(const vasr_model_desc* d, vasr_handle** out) {
     h->fe.h_filterbank = nullptr;
   }
   if (d->n_blocks > 0) {
-    if (!d->blocks || d->feat_in <= 0) { delete h; return fail(VASR_ERR_INVALID, "encoder needs blocks and feat_in"); }
+    if (!d->blocks || d->feat_in <= 0) return fail(VASR_ERR_INVALID, "encoder needs blocks and feat_in");
     h->has_encoder = true;
     h->feat_in = d->feat_in;
     for (int i = 0; i < d->n_blocks; ++i) {
       const vasr_block_desc& b = d->blocks[i];
       if (b.filters <= 0 || b.repeat <= 0 || b.kernel <= 0 || b.stride <= 0 || b.dilation <= 0) {
-        delete h;
         return fail(VASR_ERR_INVALID, "block %d has a non-positive field", i);
       }
       Block B;
@@ -1457,7 +1341,6 @@ int vasr_create(const vasr_model_desc* d, vasr_handle** out) {
       const vasr_block_desc& b = B.d;
       if (!b.residual_dense && b.residual && xs_c.size() > 1) {
         if (xs_c[0] != cin || b.stride > 1) {
-          delete h;
           return fail(VASR_ERR_INVALID, "block %d: a residual block after a dense run takes its residual from the run's input "
                       "(%d channels, block input %d%s) -- the reference fails here", i, xs_c[0], cin, b.stride > 1 ? ", strided" : "");
         }
@@ -1468,12 +1351,10 @@ int vasr_create(const vasr_model_desc* d, vasr_handle** out) {
       if (b.residual_dense) {
         ++dense_seen;
         if (b.residual && dense_seen > (int)xs_c.size()) {
-          delete h;
           return fail(VASR_ERR_INVALID, "block %d: residual_dense block number %d sees %zu residual pane(s): dense blocks must form one "
                       "contiguous run of residual blocks (the reference fails in JasperBlock.forward)", i, dense_seen, xs_c.size());
         }
         if (b.residual && b.stride > 1) {
-          delete h;
           return fail(VASR_ERR_INVALID, "block %d: a strided block cannot take a dense residual (its panes have other lengths)", i);
         }
         B.pane = (int)xs_c.size() - 1;
@@ -1499,14 +1380,13 @@ int vasr_create(const vasr_model_desc* d, vasr_handle** out) {
   }
   if (d->num_classes > 0) {
     if (d->dec_feat_in <= 0 || d->num_classes > 128) {
-      delete h;
       return fail(VASR_ERR_UNSUPPORTED, "decoder needs dec_feat_in > 0 and at most 128 classes incl. blank");
     }
     h->has_decoder = true;
     h->dec_feat_in = d->dec_feat_in;
     h->num_classes = d->num_classes;
   }
-  *out = h;
+  *out = owner.release();
   return 0;
 }
 
@@ -1539,19 +1419,23 @@ int vasr_load_weight(vasr_handle* h, const char* key, const float* data, const i
   return 0;
 }
 
-int vasr_set_block_se(vasr_handle* h, int block, int reduction_ratio) {
+// the per-block setters' common refusals
+static int settable_block(vasr_handle* h, int block) {
   if (!h) return fail(VASR_ERR_INVALID, "null handle");
   if (h->finalized) return fail(VASR_ERR_STATE, "handle already finalized");
   if (block < 0 || block >= (int)h->blocks.size()) return fail(VASR_ERR_INVALID, "block %d of %zu", block, h->blocks.size());
+  return 0;
+}
+
+int vasr_set_block_se(vasr_handle* h, int block, int reduction_ratio) {
+  if (int rc = settable_block(h, block)) return rc;
   if (reduction_ratio < 0) return fail(VASR_ERR_INVALID, "se_reduction_ratio %d is negative", reduction_ratio);
   h->blocks[block].se_r = reduction_ratio;
   return 0;
 }
 
 int vasr_set_block_groups(vasr_handle* h, int block, int groups, int heads) {
-  if (!h) return fail(VASR_ERR_INVALID, "null handle");
-  if (h->finalized) return fail(VASR_ERR_STATE, "handle already finalized");
-  if (block < 0 || block >= (int)h->blocks.size()) return fail(VASR_ERR_INVALID, "block %d of %zu", block, h->blocks.size());
+  if (int rc = settable_block(h, block)) return rc;
   if (groups < 1) return fail(VASR_ERR_INVALID, "groups %d is not positive", groups);
   if (heads == 0 || heads < -1) return fail(VASR_ERR_INVALID, "heads %d: -1 (none) or a positive count", heads);
   h->blocks[block].groups = groups;
@@ -1560,9 +1444,7 @@ int vasr_set_block_groups(vasr_handle* h, int block, int groups, int heads) {
 }
 
 int vasr_set_block_norm(vasr_handle* h, int block, int norm_groups) {
-  if (!h) return fail(VASR_ERR_INVALID, "null handle");
-  if (h->finalized) return fail(VASR_ERR_STATE, "handle already finalized");
-  if (block < 0 || block >= (int)h->blocks.size()) return fail(VASR_ERR_INVALID, "block %d of %zu", block, h->blocks.size());
+  if (int rc = settable_block(h, block)) return rc;
   if (norm_groups < 0) return fail(VASR_ERR_INVALID, "norm_groups %d is negative", norm_groups);
   h->blocks[block].norm_g = norm_groups;
   return 0;
@@ -1878,6 +1760,19 @@ int vasr_beam_workgroups(int batch) {
   return (batch + upw - 1) / upw;
 }
 
+// what both beam-search entry points refuse (pointers: all the caller's buffers are there; the one-best search: nbest 1)
+static int check_beam_args(bool pointers, int batch, int64_t frames, int num_classes, int space_id, int beam_width, int nbest,
+                           size_t ws_bytes) {
+  if (!pointers || batch <= 0 || frames <= 0) return fail(VASR_ERR_INVALID, "bad argument");
+  if (num_classes < 2 || num_classes > 128 || beam_width < 1 || beam_width > kBeamMax)
+    return fail(VASR_ERR_UNSUPPORTED, "beam search supports 2..128 classes and beam_width 1..%d", kBeamMax);
+  if (nbest < 1 || nbest > beam_width) return fail(VASR_ERR_INVALID, "nbest must be 1..beam_width (%d)", beam_width);
+  if (space_id < -1 || space_id >= num_classes - 1) return fail(VASR_ERR_INVALID, "space_id out of range");
+  const size_t need_bytes = vasr_beam_workspace_bytes(batch, frames);
+  if (ws_bytes < need_bytes) return fail(VASR_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, need_bytes);
+  return 0;
+}
+
 int vasr_beam_search_f32(const float* d_logp, int batch, int64_t frames, int num_classes, int space_id,
                          int beam_width, float token_min_logp, float beam_prune_logp, const vasr_lm* lm,
                          int32_t* d_ids, int32_t* d_id_len, float* d_score, void* d_ws, size_t ws_bytes,
@@ -1890,13 +1785,9 @@ int vasr_beam_search_rows_f32(const float* d_logp, const int32_t* d_row_frames, 
                               int num_classes, int space_id, int beam_width, float token_min_logp,
                               float beam_prune_logp, const vasr_lm* lm, int32_t* d_ids, int32_t* d_id_len,
                               float* d_score, void* d_ws, size_t ws_bytes, vasr_stream stream) {
-  if (!d_logp || !d_ids || !d_id_len || !d_score || !d_ws || batch <= 0 || frames <= 0)
-    return fail(VASR_ERR_INVALID, "bad argument");
-  if (num_classes < 2 || num_classes > 128 || beam_width < 1 || beam_width > kBeamMax)
-    return fail(VASR_ERR_UNSUPPORTED, "beam search supports 2..128 classes and beam_width 1..%d", kBeamMax);
-  if (space_id < -1 || space_id >= num_classes - 1) return fail(VASR_ERR_INVALID, "space_id out of range");
-  const size_t need_bytes = vasr_beam_workspace_bytes(batch, frames);
-  if (ws_bytes < need_bytes) return fail(VASR_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, need_bytes);
+  if (int rc = check_beam_args(d_logp && d_ids && d_id_len && d_score && d_ws, batch, frames, num_classes, space_id, beam_width, 1,
+                               ws_bytes))
+    return rc;
   // <= 64 utterances: an utterance on four wavefronts of a compute unit (beam_group.hip: the serving latency, and the shorter
   // stay in the way of an overlapped acoustic pass); beyond that
   // one wavefront per utterance, four utterances per compute unit (beam_wave.hip).  Same bits either way; VASR_BEAM_GROUP
@@ -1914,14 +1805,9 @@ int vasr_beam_search_nbest_f32(const float* d_logp, const int32_t* d_row_frames,
                                float beam_prune_logp, const vasr_lm* lm, int32_t* d_ids, int32_t* d_id_len,
                                int32_t* d_count, double* d_logit_score, double* d_score, void* d_ws, size_t ws_bytes,
                                vasr_stream stream) {
-  if (!d_logp || !d_ids || !d_id_len || !d_count || !d_logit_score || !d_score || !d_ws || batch <= 0 || frames <= 0)
-    return fail(VASR_ERR_INVALID, "bad argument");
-  if (num_classes < 2 || num_classes > 128 || beam_width < 1 || beam_width > kBeamMax)
-    return fail(VASR_ERR_UNSUPPORTED, "beam search supports 2..128 classes and beam_width 1..%d", kBeamMax);
-  if (nbest < 1 || nbest > beam_width) return fail(VASR_ERR_INVALID, "nbest must be 1..beam_width (%d)", beam_width);
-  if (space_id < -1 || space_id >= num_classes - 1) return fail(VASR_ERR_INVALID, "space_id out of range");
-  const size_t need_bytes = vasr_beam_workspace_bytes(batch, frames);
-  if (ws_bytes < need_bytes) return fail(VASR_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, need_bytes);
+  if (int rc = check_beam_args(d_logp && d_ids && d_id_len && d_count && d_logit_score && d_score && d_ws, batch, frames, num_classes,
+                               space_id, beam_width, nbest, ws_bytes))
+    return rc;
   // the same kernel forms as vasr_beam_search_rows_f32, with the n-best final pass
   const BeamNbest nb{nbest, d_count, d_logit_score, d_score};
   const int e = launch_beam_search_group(
@@ -1994,30 +1880,6 @@ int vasr_profile_end(vasr_handle* h, double ms[5], int64_t launches[5], double f
   return 0;
 }
 
-#ifdef VASR_DEVTOOLS
-static __global__ void dev_noop_kernel() {}
-
-int vasr_profile_bracket_overhead(vasr_stream stream, int n, double* out_us) {
-  if (n < 1 || n > 4096 || !out_us) return fail(VASR_ERR_INVALID, "bad argument");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  std::vector<hipEvent_t> ev(2 * (size_t)n);
-  for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-  for (int i = 0; i < n; ++i) {   // same shape as ProfScope: record, launch, record -- back to back on one stream
-    HIP_TRY(hipEventRecord(ev[2 * i], st));
-    hipLaunchKernelGGL(dev_noop_kernel, dim3(1), dim3(64), 0, st);
-    HIP_TRY(hipEventRecord(ev[2 * i + 1], st));
-  }
-  HIP_TRY(hipEventSynchronize(ev.back()));
-  std::vector<float> t(n);
-  for (int i = 0; i < n; ++i) HIP_TRY(hipEventElapsedTime(&t[i], ev[2 * i], ev[2 * i + 1]));
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  std::sort(t.begin(), t.end());
-  *out_us = 1e3 * (double)t[n / 2];
-  return 0;
-}
-
-#endif  // VASR_DEVTOOLS
-
 int vasr_algorithmic_work(const vasr_handle* h, int batch, int64_t samples, double out[5]) {
   if (!h || !h->finalized || !out) return fail(VASR_ERR_INVALID, "bad argument");
   for (int i = 0; i < 5; ++i) out[i] = 0.0;
@@ -2040,181 +1902,11 @@ int vasr_algorithmic_work(const vasr_handle* h, int batch, int64_t samples, doub
       }
       out[0] += 2.0 * S.pw.cin * S.pw.cout * (double)t * batch;
     }
-    if (B.has_res) out[0] += 2.0 * B.res.cin * B.res.cout * (double)t_in * batch;
+    // (a folded residual's GEMM counts as its own; the per-pane GEMMs of a dense residual have never been counted)
+    if (B.res.size() == 1) out[0] += 2.0 * B.res[0].w.cin * B.res[0].w.cout * (double)t_in * batch;
   }
   if (h->has_decoder) out[3] = 2.0 * h->dec_feat_in * h->num_classes * (double)t * batch;
   return 0;
 }
-
-#ifdef VASR_DEVTOOLS   // ---- include/vasr_devtools.h: isolated layers and weight packers, libvasr_hip_dev.so only ----
-int vasr_bench_depthwise(const float* d_x, const float* d_w, const int32_t* d_lens, int batch, int channels,
-                         int64_t frames, int kernel, float* d_y, vasr_stream stream) {
-  if (!d_x || !d_w || !d_lens || !d_y) return fail(VASR_ERR_INVALID, "bad argument");
-  const int64_t ld = pad_frames(frames);
-  (void)launch_depthwise(d_x, ld, (int)frames, d_w, d_lens, d_lens, batch, channels, kernel, 1, 1, kernel / 2, d_y, ld,
-                         static_cast<hipStream_t>(stream));
-  return check_launch("bench_depthwise");
-}
-
-int vasr_depthwise_mfma_table_size(int kernel, int dilation) { return depthwise_mfma_table_size(kernel, dilation); }
-
-int vasr_pack_depthwise_taps(const float* h_w, int channels, int kernel, int dilation, uint32_t* h_table, float* h_inv) {
-  const int tsz = depthwise_mfma_table_size(kernel, dilation);
-  if (!h_w || !h_table || !h_inv || channels <= 0 || !tsz) return fail(VASR_ERR_INVALID, "bad argument / shape not covered");
-  for (int c = 0; c < channels; ++c)
-    h_inv[c] = pack_depthwise_taps_f16x2(h_w + (size_t)c * kernel, kernel, dilation, tsz, h_table + (size_t)c * tsz);
-  return 0;
-}
-
-int vasr_bench_depthwise_mfma(const float* d_x, const uint32_t* d_taps, const float* d_tap_inv, const int32_t* d_lens,
-                              int batch, int channels, int64_t frames, int kernel, int dilation, float* d_y,
-                              uint32_t* d_amax, int amax_stride, vasr_stream stream) {
-  if (!d_x || !d_taps || !d_tap_inv || !d_lens || !d_y || !d_amax) return fail(VASR_ERR_INVALID, "bad argument");
-  const int64_t ld = pad_frames(frames);
-  if (amax_stride < 256 || amax_stride < depthwise_amax_slots(channels, ld)) return fail(VASR_ERR_INVALID, "maxima table too small");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  AmaxTab ax{d_amax, amax_stride, 0}, ay{d_amax + (size_t)batch * amax_stride, amax_stride, 0};
-  launch_amax(d_x, ld, channels, (int)frames, d_lens, batch, &ax, st);
-  const int e = launch_depthwise_mfma(d_x, ld, d_taps, d_tap_inv, d_lens, d_lens, ax, batch, channels, kernel, dilation,
-                                      d_y, ld, &ay, st);
-  if (e > 0) return fail(VASR_ERR_HIP, "depthwise (MFMA): %s", hipGetErrorString((hipError_t)e));
-  if (e < 0) return fail(VASR_ERR_UNSUPPORTED, "no Toeplitz instantiation for kernel %d dilation %d", kernel, dilation);
-  if (ay.n < amax_stride)
-    HIP_TRY(hipMemset2DAsync(d_amax + (size_t)batch * amax_stride + ay.n, (size_t)amax_stride * 4, 0,
-                             (size_t)(amax_stride - ay.n) * 4, batch, st));
-  if (ax.n < amax_stride)
-    HIP_TRY(hipMemset2DAsync(d_amax + ax.n, (size_t)amax_stride * 4, 0, (size_t)(amax_stride - ax.n) * 4, batch, st));
-  return check_launch("bench_depthwise_mfma");
-}
-
-int vasr_pack_pointwise(const float* h_w, int cout, int cin, int m_pad, float* h_out) {
-  if (!h_w || !h_out || cout <= 0 || cin % 8 || m_pad % 32 || m_pad < cout) return fail(VASR_ERR_INVALID, "bad argument");
-  pack_pointwise_weights(h_w, cout, cin, m_pad, h_out);
-  return 0;
-}
-
-int vasr_conv_gemm_weights(const float* h_w, int cout, int cin, int kernel, float* h_out) {
-  if (!h_w || !h_out || cout <= 0 || cin <= 0 || kernel <= 0) return fail(VASR_ERR_INVALID, "bad argument");
-  pack_conv_gemm_weights(h_w, cout, cin, kernel, h_out);
-  return 0;
-}
-
-int vasr_bench_pointwise(const float* d_x, const float* d_wt, const float* d_scale, const float* d_shift, int batch,
-                         int cin, int cout, int64_t frames, float* d_y, vasr_stream stream) {
-  // in_channels % 64 like vasr_load_weight: the K % 32 tile (128 x 256) assumes a 256-frame pitch pad_frames() no longer gives
-  if (!d_x || !d_wt || !d_scale || !d_shift || !d_y || cout % 128 || cin % 64)
-    return fail(VASR_ERR_INVALID, "bad argument");
-  const int64_t ld = pad_frames(frames);
-  PwArgs a{};
-  a.wt = d_wt; a.x = d_x; a.lens = nullptr; a.scale = d_scale; a.shift = d_shift; a.res = nullptr; a.y = d_y;
-  a.M = cout; a.K = cin; a.batch = batch; a.ldx = ld; a.ldy = ld; a.ldr = 0; a.frames = (int)frames;
-  a.store_cols = (int)ld; a.m_store = cout; a.relu = 1;
-  launch_pointwise(a, static_cast<hipStream_t>(stream));
-  return check_launch("bench_pointwise");
-}
-
-int vasr_bench_mfma_sustained(int gemm_mode, int workgroups, int steps, float* d_sink, double* flops, vasr_stream stream) {
-  if (workgroups < 1 || steps < 1 || !d_sink || !flops) return fail(VASR_ERR_INVALID, "bad argument");
-  if (gemm_mode != 1 && gemm_mode != 3) return fail(VASR_ERR_INVALID, "gemm mode %d has no 16-bit MFMA stream (1 = bf16x3, 3 = f16x2)", gemm_mode);
-  *flops = launch_mfma_sustained(gemm_mode, workgroups, steps, d_sink, static_cast<hipStream_t>(stream));
-  return check_launch("mfma_sustained");
-}
-
-int vasr_pack_pointwise_bf16x3(const float* h_w, int cout, int cin, int m_pad, uint16_t* h_out) {
-  if (!h_w || !h_out || cout <= 0 || cin % 16 || m_pad % 32 || m_pad < cout) return fail(VASR_ERR_INVALID, "bad argument");
-  pack_pointwise_weights_bf16x3(h_w, cout, cin, m_pad, h_out);
-  return 0;
-}
-
-int vasr_pack_pointwise_f16x2(const float* h_w, int cout, int cin, int m_pad, uint16_t* h_out, float* inv_scale) {
-  if (!h_w || !h_out || !inv_scale || cout <= 0 || cin % 16 || m_pad % 32 || m_pad < cout)
-    return fail(VASR_ERR_INVALID, "bad argument");
-  *inv_scale = pack_pointwise_weights_f16x2(h_w, cout, cin, m_pad, h_out);
-  return 0;
-}
-
-int vasr_bench_pointwise_f16x2(const float* d_x, const uint16_t* d_w16, float w_inv_scale, const float* d_scale,
-                               const float* d_shift, int batch, int cin, int cout, int64_t frames, float* d_y,
-                               uint32_t* d_amax, int amax_stride, vasr_stream stream) {
-  if (!d_x || !d_w16 || !d_scale || !d_shift || !d_y || !d_amax || !pointwise_split_supported(cout, cin, 0))
-    return fail(VASR_ERR_INVALID, "bad argument");
-  const int64_t ld = pad_frames(frames);
-  if (amax_stride < 256 || amax_stride < pointwise_amax_slots(cout, ld)) return fail(VASR_ERR_INVALID, "maxima table too small");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  AmaxTab ax{d_amax, amax_stride, 0};
-  launch_amax(d_x, ld, cin, (int)frames, nullptr, batch, &ax, st);
-  PwArgs a{};
-  a.wt = reinterpret_cast<const float*>(d_w16); a.x = d_x; a.scale = d_scale; a.shift = d_shift; a.y = d_y;
-  a.M = cout; a.K = cin; a.batch = batch; a.ldx = ld; a.ldy = ld; a.frames = (int)frames;
-  a.store_cols = (int)ld; a.m_store = cout; a.relu = 1;
-  a.amax_x = ax; a.w_inv_scale = w_inv_scale;
-  a.amax_y = AmaxTab{d_amax + (size_t)batch * amax_stride, amax_stride, 0};   // second table: maxima of y
-  int n_y = 0;
-  const int e = launch_pointwise_split(a, 2, st, &n_y);
-  if (e) return fail(VASR_ERR_HIP, "pointwise GEMM: %s", hipGetErrorString((hipError_t)e));
-  // slots past the ones the launch used read as zero for the caller
-  if (n_y < amax_stride)
-    HIP_TRY(hipMemset2DAsync(d_amax + (size_t)batch * amax_stride + n_y, (size_t)amax_stride * 4, 0,
-                             (size_t)(amax_stride - n_y) * 4, batch, st));
-  if (ax.n < amax_stride)
-    HIP_TRY(hipMemset2DAsync(d_amax + ax.n, (size_t)amax_stride * 4, 0, (size_t)(amax_stride - ax.n) * 4, batch, st));
-  return check_launch("bench_pointwise_f16x2");
-}
-
-int vasr_bench_pointwise_bf16x3(const float* d_x, const uint16_t* d_w3, const float* d_scale, const float* d_shift,
-                                int batch, int cin, int cout, int64_t frames, float* d_y, vasr_stream stream) {
-  if (!d_x || !d_w3 || !d_scale || !d_shift || !d_y || !pointwise_split_supported(cout, cin, 0))
-    return fail(VASR_ERR_INVALID, "bad argument");
-  const int64_t ld = pad_frames(frames);
-  PwArgs a{};
-  a.wt = reinterpret_cast<const float*>(d_w3); a.x = d_x; a.scale = d_scale; a.shift = d_shift; a.y = d_y;
-  a.M = cout; a.K = cin; a.batch = batch; a.ldx = ld; a.ldy = ld; a.frames = (int)frames;
-  a.store_cols = (int)ld; a.m_store = cout; a.relu = 1;
-  const int e = launch_pointwise_split(a, 0, static_cast<hipStream_t>(stream));
-  if (e) return fail(VASR_ERR_HIP, "pointwise GEMM: %s", hipGetErrorString((hipError_t)e));
-  return check_launch("bench_pointwise_bf16x3");
-}
-
-int vasr_bench_groupnorm(const float* d_x, const int32_t* d_lens, int batch, int channels, int64_t frames, int norm_groups,
-                         int shuffle, const float* h_gamma, const float* h_beta, int relu, float* d_y, vasr_stream stream) {
-  if (!d_x || !d_lens || !d_y || !h_gamma || !h_beta || batch < 1 || frames < 1 || shuffle < 1 || channels % shuffle ||
-      !norm_supported(channels, norm_groups))
-    return fail(VASR_ERR_INVALID, "bad argument");
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int64_t ld = pad_frames(frames);
-  std::vector<float> gs(channels), bs(channels);
-  std::vector<int32_t> group_of(channels), members(channels);
-  const std::vector<int> perm = shuffle_perm(channels, shuffle);
-  for (int p = 0; p < channels; ++p) {
-    const int o = perm[p];
-    gs[o] = h_gamma[p];
-    bs[o] = h_beta[p];
-    group_of[o] = p / (channels / norm_groups);
-    members[p] = o;
-  }
-  char* buf = nullptr;
-  const size_t nc = (size_t)channels, ws = (size_t)2 * batch * (channels + norm_groups);
-  HIP_TRY(hipMalloc(&buf, (4 * nc + ws) * 4));
-  float* f = reinterpret_cast<float*>(buf);
-  int32_t* i32 = reinterpret_cast<int32_t*>(buf);
-  NormLaunch a{};
-  a.x = d_x; a.y = d_y; a.add = nullptr; a.ld = ld; a.ld_add = ld; a.bs = 0;
-  a.channels = channels; a.groups = norm_groups; a.batch = batch; a.frames = (int)frames; a.store_cols = (int)ld;
-  a.lens = d_lens; a.gamma = f; a.beta = f + nc; a.group_of = i32 + 2 * nc; a.members = i32 + 3 * nc;
-  a.row_mean = f + 4 * nc; a.row_m2 = a.row_mean + (size_t)batch * channels;
-  a.g_mean = a.row_m2 + (size_t)batch * channels; a.g_rstd = a.g_mean + (size_t)batch * norm_groups;
-  a.zero_lens = d_lens; a.relu = relu;
-  hipError_t e = hipMemcpyAsync(buf, gs.data(), nc * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(buf + nc * 4, bs.data(), nc * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(buf + 2 * nc * 4, group_of.data(), nc * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(buf + 3 * nc * 4, members.data(), nc * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = (hipError_t)launch_norm(a, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(buf);
-  if (e != hipSuccess) return fail(VASR_ERR_HIP, "bench_groupnorm: %s", hipGetErrorString(e));
-  return 0;
-}
-
-#endif  // VASR_DEVTOOLS
 
 }  // extern "C"

@@ -1,0 +1,227 @@
+// What libvasr_hip_dev.so adds to the product library (include/vasr_devtools.h): the kernel-selection switches read from the
+// environment, isolated-layer launches and the weight packers.  Compiled into the devtools build only (Makefile SRCS_DEV).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <initializer_list>
+#include <vector>
+
+#include "vasr.h"
+#include "vasr_devtools.h"
+#include "vasr_host.h"
+#include "vasr_internal.h"
+
+using namespace vasr;
+
+// The devtools build's kernel-selection switches (vasr_internal.h DevSwitches): the environment is read HERE, once per
+// process, and nowhere else; a value outside a switch's documented set aborts instead of silently meaning "default".
+const vasr::DevSwitches& vasr::dev_switches() {
+  static const DevSwitches sw = [] {
+    DevSwitches s;
+    auto num = [](const char* name, int dflt, std::initializer_list<int> allowed) {
+      const char* e = getenv(name);
+      if (!e) return dflt;
+      const int v = atoi(e);
+      for (int a : allowed) if (a == v) return v;
+      fprintf(stderr, "vasr (devtools build): %s=%s is not a documented value -- refusing to guess\n", name, e);
+      abort();
+      return dflt;   // (not reached)
+    };
+    s.pw3_tile = num("VASR_PW3_TILE", 0, {0, 1, 2, 3, 4, 5});
+    s.pw_lat = num("VASR_PW_LAT", 1, {0, 1});
+    s.dw_pair = num("VASR_DW_PAIR", 1, {0, 1}) != 0;
+    s.dw_mfma = num("VASR_DW_MFMA", 1, {0, 1}) != 0;
+    s.dw_upw = num("VASR_DW_UPW", 0, {0, 1, 2, 3, 4, 5, 6, 7, 8});
+    s.fused = num("VASR_FUSED", 1, {0, 1}) != 0;
+    s.fused_min_tiles = getenv("VASR_FUSED_MIN_TILES") ? atoi(getenv("VASR_FUSED_MIN_TILES")) : 0;
+    s.fused_tile = num("VASR_FUSED_TILE", 0, {0, 64, 128});
+    s.fused_residual = num("VASR_NO_FUSED_RESIDUAL", 0, {0, 1}) == 0;
+    s.beam_group = num("VASR_BEAM_GROUP", -1, {-1, 0, 1, 4});
+    s.no_grouped = num("VASR_NO_GROUPED", 0, {0, 1}) != 0;
+    return s;
+  }();
+  return sw;
+}
+
+extern "C" {
+
+int vasr_fused_tile_choice(int64_t tiles128, int compute_units) { return vasr::fused_tile_choice(tiles128, compute_units); }
+
+static __global__ void dev_noop_kernel() {}
+
+int vasr_profile_bracket_overhead(vasr_stream stream, int n, double* out_us) {
+  if (n < 1 || n > 4096 || !out_us) return fail(VASR_ERR_INVALID, "bad argument");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  std::vector<hipEvent_t> ev(2 * (size_t)n);
+  for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+  for (int i = 0; i < n; ++i) {   // same shape as ProfScope: record, launch, record -- back to back on one stream
+    HIP_TRY(hipEventRecord(ev[2 * i], st));
+    hipLaunchKernelGGL(dev_noop_kernel, dim3(1), dim3(64), 0, st);
+    HIP_TRY(hipEventRecord(ev[2 * i + 1], st));
+  }
+  HIP_TRY(hipEventSynchronize(ev.back()));
+  std::vector<float> t(n);
+  for (int i = 0; i < n; ++i) HIP_TRY(hipEventElapsedTime(&t[i], ev[2 * i], ev[2 * i + 1]));
+  for (auto& e : ev) (void)hipEventDestroy(e);
+  std::sort(t.begin(), t.end());
+  *out_us = 1e3 * (double)t[n / 2];
+  return 0;
+}
+
+int vasr_bench_depthwise(const float* d_x, const float* d_w, const int32_t* d_lens, int batch, int channels,
+                         int64_t frames, int kernel, float* d_y, vasr_stream stream) {
+  if (!d_x || !d_w || !d_lens || !d_y) return fail(VASR_ERR_INVALID, "bad argument");
+  const int64_t ld = pad_frames(frames);
+  (void)launch_depthwise(d_x, ld, (int)frames, d_w, d_lens, d_lens, batch, channels, kernel, 1, 1, kernel / 2, d_y, ld,
+                         static_cast<hipStream_t>(stream));
+  return check_launch("bench_depthwise");
+}
+
+int vasr_depthwise_mfma_table_size(int kernel, int dilation) { return depthwise_mfma_table_size(kernel, dilation); }
+
+int vasr_pack_depthwise_taps(const float* h_w, int channels, int kernel, int dilation, uint32_t* h_table, float* h_inv) {
+  const int tsz = depthwise_mfma_table_size(kernel, dilation);
+  if (!h_w || !h_table || !h_inv || channels <= 0 || !tsz) return fail(VASR_ERR_INVALID, "bad argument / shape not covered");
+  for (int c = 0; c < channels; ++c)
+    h_inv[c] = pack_depthwise_taps_f16x2(h_w + (size_t)c * kernel, kernel, dilation, tsz, h_table + (size_t)c * tsz);
+  return 0;
+}
+
+int vasr_bench_depthwise_mfma(const float* d_x, const uint32_t* d_taps, const float* d_tap_inv, const int32_t* d_lens,
+                              int batch, int channels, int64_t frames, int kernel, int dilation, float* d_y,
+                              uint32_t* d_amax, int amax_stride, vasr_stream stream) {
+  if (!d_x || !d_taps || !d_tap_inv || !d_lens || !d_y || !d_amax) return fail(VASR_ERR_INVALID, "bad argument");
+  const int64_t ld = pad_frames(frames);
+  if (amax_stride < 256 || amax_stride < depthwise_amax_slots(channels, ld)) return fail(VASR_ERR_INVALID, "maxima table too small");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  AmaxTab ax{d_amax, amax_stride, 0}, ay{d_amax + (size_t)batch * amax_stride, amax_stride, 0};
+  launch_amax(d_x, ld, channels, (int)frames, d_lens, batch, &ax, st);
+  const int e = launch_depthwise_mfma(d_x, ld, d_taps, d_tap_inv, d_lens, d_lens, ax, batch, channels, kernel, dilation,
+                                      d_y, ld, &ay, st);
+  if (e > 0) return fail(VASR_ERR_HIP, "depthwise (MFMA): %s", hipGetErrorString((hipError_t)e));
+  if (e < 0) return fail(VASR_ERR_UNSUPPORTED, "no Toeplitz instantiation for kernel %d dilation %d", kernel, dilation);
+  if (ay.n < amax_stride)
+    HIP_TRY(hipMemset2DAsync(d_amax + (size_t)batch * amax_stride + ay.n, (size_t)amax_stride * 4, 0,
+                             (size_t)(amax_stride - ay.n) * 4, batch, st));
+  if (ax.n < amax_stride)
+    HIP_TRY(hipMemset2DAsync(d_amax + ax.n, (size_t)amax_stride * 4, 0, (size_t)(amax_stride - ax.n) * 4, batch, st));
+  return check_launch("bench_depthwise_mfma");
+}
+
+int vasr_pack_pointwise(const float* h_w, int cout, int cin, int m_pad, float* h_out) {
+  if (!h_w || !h_out || cout <= 0 || cin % 8 || m_pad % 32 || m_pad < cout) return fail(VASR_ERR_INVALID, "bad argument");
+  pack_pointwise_weights(h_w, cout, cin, m_pad, h_out);
+  return 0;
+}
+
+int vasr_conv_gemm_weights(const float* h_w, int cout, int cin, int kernel, float* h_out) {
+  if (!h_w || !h_out || cout <= 0 || cin <= 0 || kernel <= 0) return fail(VASR_ERR_INVALID, "bad argument");
+  pack_conv_gemm_weights(h_w, cout, cin, kernel, h_out);
+  return 0;
+}
+
+int vasr_bench_pointwise(const float* d_x, const float* d_wt, const float* d_scale, const float* d_shift, int batch,
+                         int cin, int cout, int64_t frames, float* d_y, vasr_stream stream) {
+  // in_channels % 64 like vasr_load_weight: the K % 32 tile (128 x 256) assumes a 256-frame pitch pad_frames() no longer gives
+  if (!d_x || !d_wt || !d_scale || !d_shift || !d_y || cout % 128 || cin % 64)
+    return fail(VASR_ERR_INVALID, "bad argument");
+  const int64_t ld = pad_frames(frames);
+  PwArgs a = pw_args(d_wt, d_scale, d_shift, cout, cin, d_x, d_y, ld, frames, batch);
+  a.relu = 1;
+  launch_pointwise(a, static_cast<hipStream_t>(stream));
+  return check_launch("bench_pointwise");
+}
+
+int vasr_bench_mfma_sustained(int gemm_mode, int workgroups, int steps, float* d_sink, double* flops, vasr_stream stream) {
+  if (workgroups < 1 || steps < 1 || !d_sink || !flops) return fail(VASR_ERR_INVALID, "bad argument");
+  if (gemm_mode != 1 && gemm_mode != 3) return fail(VASR_ERR_INVALID, "gemm mode %d has no 16-bit MFMA stream (1 = bf16x3, 3 = f16x2)", gemm_mode);
+  *flops = launch_mfma_sustained(gemm_mode, workgroups, steps, d_sink, static_cast<hipStream_t>(stream));
+  return check_launch("mfma_sustained");
+}
+
+int vasr_pack_pointwise_bf16x3(const float* h_w, int cout, int cin, int m_pad, uint16_t* h_out) {
+  if (!h_w || !h_out || cout <= 0 || cin % 16 || m_pad % 32 || m_pad < cout) return fail(VASR_ERR_INVALID, "bad argument");
+  pack_pointwise_weights_bf16x3(h_w, cout, cin, m_pad, h_out);
+  return 0;
+}
+
+int vasr_pack_pointwise_f16x2(const float* h_w, int cout, int cin, int m_pad, uint16_t* h_out, float* inv_scale) {
+  if (!h_w || !h_out || !inv_scale || cout <= 0 || cin % 16 || m_pad % 32 || m_pad < cout)
+    return fail(VASR_ERR_INVALID, "bad argument");
+  *inv_scale = pack_pointwise_weights_f16x2(h_w, cout, cin, m_pad, h_out);
+  return 0;
+}
+
+int vasr_bench_pointwise_f16x2(const float* d_x, const uint16_t* d_w16, float w_inv_scale, const float* d_scale,
+                               const float* d_shift, int batch, int cin, int cout, int64_t frames, float* d_y,
+                               uint32_t* d_amax, int amax_stride, vasr_stream stream) {
+  if (!d_x || !d_w16 || !d_scale || !d_shift || !d_y || !d_amax || !pointwise_split_supported(cout, cin, 0))
+    return fail(VASR_ERR_INVALID, "bad argument");
+  const int64_t ld = pad_frames(frames);
+  if (amax_stride < 256 || amax_stride < pointwise_amax_slots(cout, ld)) return fail(VASR_ERR_INVALID, "maxima table too small");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  AmaxTab ax{d_amax, amax_stride, 0};
+  launch_amax(d_x, ld, cin, (int)frames, nullptr, batch, &ax, st);
+  PwArgs a = pw_args(d_w16, d_scale, d_shift, cout, cin, d_x, d_y, ld, frames, batch);
+  a.relu = 1;
+  a.amax_x = ax; a.w_inv_scale = w_inv_scale;
+  a.amax_y = AmaxTab{d_amax + (size_t)batch * amax_stride, amax_stride, 0};   // second table: maxima of y
+  int n_y = 0;
+  const int e = launch_pointwise_split(a, 2, st, &n_y);
+  if (e) return fail(VASR_ERR_HIP, "pointwise GEMM: %s", hipGetErrorString((hipError_t)e));
+  // slots past the ones the launch used read as zero for the caller
+  if (n_y < amax_stride)
+    HIP_TRY(hipMemset2DAsync(d_amax + (size_t)batch * amax_stride + n_y, (size_t)amax_stride * 4, 0,
+                             (size_t)(amax_stride - n_y) * 4, batch, st));
+  if (ax.n < amax_stride)
+    HIP_TRY(hipMemset2DAsync(d_amax + ax.n, (size_t)amax_stride * 4, 0, (size_t)(amax_stride - ax.n) * 4, batch, st));
+  return check_launch("bench_pointwise_f16x2");
+}
+
+int vasr_bench_pointwise_bf16x3(const float* d_x, const uint16_t* d_w3, const float* d_scale, const float* d_shift,
+                                int batch, int cin, int cout, int64_t frames, float* d_y, vasr_stream stream) {
+  if (!d_x || !d_w3 || !d_scale || !d_shift || !d_y || !pointwise_split_supported(cout, cin, 0))
+    return fail(VASR_ERR_INVALID, "bad argument");
+  const int64_t ld = pad_frames(frames);
+  PwArgs a = pw_args(d_w3, d_scale, d_shift, cout, cin, d_x, d_y, ld, frames, batch);
+  a.relu = 1;
+  const int e = launch_pointwise_split(a, 0, static_cast<hipStream_t>(stream));
+  if (e) return fail(VASR_ERR_HIP, "pointwise GEMM: %s", hipGetErrorString((hipError_t)e));
+  return check_launch("bench_pointwise_bf16x3");
+}
+
+int vasr_bench_groupnorm(const float* d_x, const int32_t* d_lens, int batch, int channels, int64_t frames, int norm_groups,
+                         int shuffle, const float* h_gamma, const float* h_beta, int relu, float* d_y, vasr_stream stream) {
+  if (!d_x || !d_lens || !d_y || !h_gamma || !h_beta || batch < 1 || frames < 1 || shuffle < 1 || channels % shuffle ||
+      !norm_supported(channels, norm_groups))
+    return fail(VASR_ERR_INVALID, "bad argument");
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t ld = pad_frames(frames);
+  const NormTables t = norm_tables(h_gamma, h_beta, channels, norm_groups, shuffle);
+  char* buf = nullptr;
+  const size_t nc = (size_t)channels, ws = (size_t)2 * batch * (channels + norm_groups);
+  HIP_TRY(hipMalloc(&buf, (4 * nc + ws) * 4));
+  float* f = reinterpret_cast<float*>(buf);
+  int32_t* i32 = reinterpret_cast<int32_t*>(buf);
+  NormLaunch a{};
+  a.x = d_x; a.y = d_y; a.add = nullptr; a.ld = ld; a.ld_add = ld; a.bs = 0;
+  a.channels = channels; a.groups = norm_groups; a.batch = batch; a.frames = (int)frames; a.store_cols = (int)ld;
+  a.lens = d_lens; a.gamma = f; a.beta = f + nc; a.group_of = i32 + 2 * nc; a.members = i32 + 3 * nc;
+  a.row_mean = f + 4 * nc; a.row_m2 = a.row_mean + (size_t)batch * channels;
+  a.g_mean = a.row_m2 + (size_t)batch * channels; a.g_rstd = a.g_mean + (size_t)batch * norm_groups;
+  a.zero_lens = d_lens; a.relu = relu;
+  hipError_t e = hipMemcpyAsync(buf, t.gamma.data(), nc * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(buf + nc * 4, t.beta.data(), nc * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(buf + 2 * nc * 4, t.group_of.data(), nc * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(buf + 3 * nc * 4, t.members.data(), nc * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = (hipError_t)launch_norm(a, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(buf);
+  if (e != hipSuccess) return fail(VASR_ERR_HIP, "bench_groupnorm: %s", hipGetErrorString(e));
+  return 0;
+}
+
+
+}  // extern "C"

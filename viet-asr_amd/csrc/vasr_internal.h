@@ -11,7 +11,7 @@ namespace vasr {
 // Kernel-SELECTION switches: every product path that the default rules do not reach at a given shape (the packed-FMA
 // depthwise, the two-kernel form of a fused sub-block, a pinned GEMM tile, the one-wavefront beam search ...) can be forced,
 // so that the tests can hold it to the same goldens.  They exist in the DEVTOOLS build only (libvasr_hip_dev.so), are read
-// from the environment ONCE per process (dev_switches(), vasr_api.cpp) and copied into every handle at vasr_create(); in the
+// from the environment ONCE per process (dev_switches(), vasr_devtools.cpp) and copied into every handle at vasr_create(); in the
 // product library the struct is a compile-time constant of defaults and nothing looks at the environment.  (Rounds 1-5 also
 // kept timing ablations and one-off experiments behind ~40 more switches and macros inside the kernels; their results are in
 // DESIGN_HISTORY.md, their code is in the history -- `git show a54b0b9:viet-asr_amd/csrc`.)  VASR_GEMM and VASR_SLICES --
@@ -258,7 +258,7 @@ bool fused_dwpw_supported(int channels, int cout, int kernel, int stride, int di
 // Which form a 256-channel sub-block takes for `tiles128` tiles of 128 frames (batch x padded frames / 128) on `cus` free
 // compute units: 128 or 64 = the fused kernel on tiles of that many frames, 0 = depthwise and GEMM as two kernels.
 // One workgroup per CU and tile, so a launch is whole rounds of lock-stepped workgroups (measurements: vasr_api.cpp
-// run_encoder): 128-frame tiles from 3/4 of a round up when the last round is >= 80 % full; otherwise
+// fused_tile_cols): 128-frame tiles from 3/4 of a round up when the last round is >= 80 % full; otherwise
 // 64-frame tiles while THOSE fit one round and occupy >= 3/8 of the chip; otherwise two kernels.
 static inline int fused_tile_choice(int64_t tiles128, int cus) {
   if (tiles128 <= 0 || cus <= 0) return 0;
