@@ -24,7 +24,7 @@ namespace vasr {
 namespace {
 
 constexpr int kTile = 512;  // outputs per wavefront (2 groups x 64 lanes x 4)
-using v4f = __attribute__((ext_vector_type(4))) float;  // native vector: one ds_read_b128 / global dwordx4
+// (v4f, vasr_device.h, is a native vector: one ds_read_b128 / global dwordx4 where a struct float4 can fall apart)
 
 template <int K, int DIL = 1>
 struct DwGeom {
@@ -34,8 +34,6 @@ struct DwGeom {
   static constexpr int NQ = (OFF + K + 3 + 3) / 4;       // float4 reads per lane per group
   static constexpr int WIN = 256 + 252 + 4 * NQ;         // floats of LDS per wavefront
 };
-
-using v2f = __attribute__((ext_vector_type(2))) float;
 
 // Each wavefront owns a private LDS window, so no workgroup barrier is needed: the LDS pipeline
 // executes one wavefront's ds_write / ds_read in issue order; this only pins the compiler.

@@ -47,10 +47,6 @@ namespace vasr {
 namespace {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
-using v4f = __attribute__((ext_vector_type(4))) float;
-using v2f = __attribute__((ext_vector_type(2))) float;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
 using u32x4 = __attribute__((vector_size(16))) unsigned int;
 
 constexpr int kTile = 512;          // output frames per task: 2 groups of 16 windows x 16 outputs

@@ -44,12 +44,6 @@ namespace vasr {
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using v4f = __attribute__((ext_vector_type(4))) float;
-using v2f = __attribute__((ext_vector_type(2))) float;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
-
 constexpr int FC = 256;     // channels in = out
 constexpr int FCH = 64;     // channels per chunk (4 k-steps of 16)
 constexpr int FNT = 512;    // threads: 4 consumer + 4 producer wavefronts
@@ -128,12 +122,6 @@ struct FusedArgs {
 // for the rows they have just requested for the NEXT chunk
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-__device__ __forceinline__ void wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // B image: element (plane, k-step ks, k-half kh, column n) is one 16-byte slot (8 consecutive channels of one frame).
 // The column index is swizzled inside its aligned group of 16 -- low4 ^= (n >> 4) | (kh << KHS) -- so that the producers'
 // 4-byte writes (8 lanes of one pair sit 16 (8) columns apart: the same bank(s) unswizzled) and the consumers' 16-byte
@@ -144,7 +132,7 @@ __device__ __forceinline__ int bimg_slot(int n, int kh) { return (n & ~15) | ((n
 template <int BN>
 __device__ __forceinline__ constexpr int bimg_off(int buf, int plane, int ks) { return (((buf * 2 + plane) * 4 + ks) * 2) * BN * 16; }
 
-// EPI: epilogue_kind (vasr_internal.h): 0 = ReLU as a maximum with a uniform floor, 1 = Hardtanh as a clamp, 2 = SELU
+// EPI: epilogue_kind (vasr_internal.h), the float4 form of vasr_device.h's Epilogue<EPI> without a residual tensor
 template <int K, bool DUAL, int BN, int EPI = 0>
 __global__ __launch_bounds__(FNT, 1) void dwpw_fused_kernel(FusedArgs a, int tiles_t, int n_blocks) {
   using G = FGeom<K, BN>;
@@ -155,11 +143,8 @@ __global__ __launch_bounds__(FNT, 1) void dwpw_fused_kernel(FusedArgs a, int til
   unsigned char* wins = smem + TL::kBimgBytes;
   unsigned char* tapl = smem + TL::kBimgBytes + TL::kWinBytes;
 
-  int bid = blockIdx.x;
-  {   // XCD-aware order: consecutive tiles of an utterance on one XCD (its L2 then serves the neighbouring windows' halo)
-    const int q = n_blocks / 8, r = n_blocks % 8, xcd = bid % 8, slot = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
+  // consecutive tiles of an utterance on one XCD: its L2 then serves the neighbouring windows' halo
+  const int bid = xcd_remap(blockIdx.x, n_blocks);
   const int b = bid / tiles_t;
   const int tile = bid % tiles_t;
   const int t0 = tile * BN;
@@ -281,11 +266,8 @@ __global__ __launch_bounds__(FNT, 1) void dwpw_fused_kernel(FusedArgs a, int til
       }
     }
     // ---- epilogue: BN affine + ReLU, rows transposed through the (now idle) producer windows into float4 stores ----
-    const int ylen = a.amax_y.p ? (a.lens_y ? a.lens_y[b] : a.frames) : 0;
-    unsigned ymax = 0;
-    const float relu_floor = (a.relu & 1) ? 0.f : -__builtin_inff();
-    float act_lo = 0.f, act_hi = 0.f;
-    if constexpr (EPI == 1) clamp_bounds(a.relu, a.act, act_lo, act_hi);
+    AmaxTracker amax{a.amax_y.p ? (a.lens_y ? a.lens_y[b] : a.frames) : 0};
+    const Epilogue<EPI> epi(a.relu, a.act, 0);   // (only add-mode residuals reach this kernel, folded into the weights)
     float* stage = reinterpret_cast<float*>(wins + wave * kWWave);   // 2 x 8 rows x BN columns = 8 KB of 13 KB (4 of 9)
     // every pass's BN scale / shift BEFORE the first store: stores count in vmcnt like loads, so a load issued between
     // two passes makes its consumer wait (vmcnt(0)) for every store before it -- eight store round trips in series
@@ -323,27 +305,13 @@ __global__ __launch_bounds__(FNT, 1) void dwpw_fused_kernel(FusedArgs a, int til
         for (int k = 0; k < NT; ++k) {
           const int f = lane + 64 * k, row = f / (BN / 4), c4 = f % (BN / 4);
           const int m = mq + row, t = t0 + 4 * c4;
-          v4f v;
-          if constexpr (EPI == 1) {
-            v = __builtin_elementwise_min(__builtin_elementwise_max(pv[k], v4f{act_lo, act_lo, act_lo, act_lo}),
-                                          v4f{act_hi, act_hi, act_hi, act_hi});
-          } else if constexpr (EPI == 2) {
-            v = pv[k];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = selu(v[e]);
-          } else {
-            v = __builtin_elementwise_max(pv[k], v4f{relu_floor, relu_floor, relu_floor, relu_floor});
-          }
+          const v4f v = epi.apply4(pv[k]);
           *reinterpret_cast<v4f*>(a.y + ((int64_t)b * FC + m) * a.ldy + t) = v;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const unsigned u = abs_bits(v[e]);
-            ymax = (t + e < ylen && u > ymax) ? u : ymax;
-          }
+          amax.track4(v, t);
         }
       }
     }
-    if (a.amax_y.p) amax_publish(a.amax_y.p, a.amax_y.stride, b, tile * 4 + wave, ymax, lane);
+    if (a.amax_y.p) amax_publish(a.amax_y.p, a.amax_y.stride, b, tile * 4 + wave, amax.ymax, lane);
     return;
   }
 

@@ -36,9 +36,6 @@ namespace vasr {
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using v4f = __attribute__((ext_vector_type(4))) float;
-
 constexpr int kChunkFloats = 8192;  // 32 KB of activations per LDS buffer
 
 // WM x WN wave grid, each wave TM (1 or 2) m-tiles of 32 rows by 2 n-tiles of 32 columns
@@ -56,18 +53,13 @@ struct PwGeom {
 // DUAL: the reduction runs over two activation tensors back to back -- rows [0, K1) from a.x, rows [K1, K)
 // from a.x2 (masked with a.lens2).  Used to fold a JasperBlock's residual 1x1 conv into its last sub-block's GEMM
 // (weights [s1*W1 | s2*W2] concatenated along K, shift h1 + h2), which removes the residual tensor round trip.
-// EPI: epilogue_kind (vasr_internal.h), as encoder_pw_split.hip's
+// EPI: epilogue_kind (vasr_internal.h), the shared Epilogue<EPI> of vasr_device.h
 template <int WM, int TM, bool MASK, bool RES, bool DUAL, bool CONV = false, int EPI = 0>
 __global__ __launch_bounds__(512, 4) void pw_gemm_kernel(PwArgs a, int blocks_m, int tiles_t, int n_blocks) {
   using G = PwGeom<WM, TM>;
   __shared__ v4f Bs4[2][kChunkFloats / 4];
 
-  // ---- XCD-aware remap: consecutive logical ids -> same XCD ----
-  int bid = blockIdx.x;
-  {
-    const int q = n_blocks / 8, r = n_blocks % 8, xcd = bid % 8, slot = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
+  const int bid = xcd_remap(blockIdx.x, n_blocks);
   const int mb = bid % blocks_m;
   const int nt = bid / blocks_m;
   const int b = nt / tiles_t;
@@ -184,8 +176,7 @@ __global__ __launch_bounds__(512, 4) void pw_gemm_kernel(PwArgs a, int blocks_m,
   // C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
   if (a.relu & 2) return;  // debug: skip the epilogue (tools/bench_layers.py ablation)
   const bool full = (t0 + G::BN <= a.store_cols) && (m0 + G::BM <= a.m_store);
-  float act_lo = 0.f, act_hi = 0.f;
-  if constexpr (EPI == 1) clamp_bounds(a.relu, a.act, act_lo, act_hi);
+  const Epilogue<EPI> epi(a.relu, a.act, a.res_max);
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -199,17 +190,8 @@ __global__ __launch_bounds__(512, 4) void pw_gemm_kernel(PwArgs a, int blocks_m,
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           const int t = t0 + wn + j * 32 + l31;
-          float v = fmaf(acc[i][j][4 * q + rr], sc[rr], sh[rr]);
-          if constexpr (EPI != 0) {
-            if (RES) {   // (res may be y: this thread reads the element before it stores it)
-              const float r = a.res[((int64_t)b * a.M + m) * a.ldr + t];
-              v = a.res_max ? fmaxf(v, r) : v + r;
-            }
-            v = EPI == 1 ? fminf(fmaxf(v, act_lo), act_hi) : selu(v);
-          } else {
-            if (RES) v += a.res[((int64_t)b * a.M + m) * a.ldr + t];
-            if (a.relu & 1) v = fmaxf(v, 0.f);
-          }
+          // (res may be y: this thread reads the element before it stores it)
+          const float v = epi.template apply<RES>(fmaf(acc[i][j][4 * q + rr], sc[rr], sh[rr]), a.res + ((int64_t)b * a.M + m) * a.ldr + t);
           if (full || (t < a.store_cols && m < a.m_store)) a.y[((int64_t)b * a.m_store + m) * a.ldy + t] = v;
         }
       }

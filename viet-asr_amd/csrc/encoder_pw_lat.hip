@@ -24,23 +24,11 @@ namespace vasr {
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using v4f = __attribute__((ext_vector_type(4))) float;
-using v2f = __attribute__((ext_vector_type(2))) float;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
-
 constexpr int LBN = 32;          // columns per workgroup
 constexpr int LNW = 4;           // multiplying wavefronts = 32-row m-tiles: 128 rows per workgroup
 constexpr int LNT = 128 * LNW;   // + as many staging wavefronts
 constexpr int LAD = 8;           // weight fragments requested this many k-steps ahead
 constexpr int LBD = 2;           // B fragments read from LDS this many k-steps ahead
-
-__device__ __forceinline__ void wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // KS = K / 16 k-steps (16, 32, 64).  Wavefronts 0-3 MULTIPLY (one 32-row m-tile each), wavefronts 4-7 STAGE: a staging thread
 // owns PI = K / 256 items (8 consecutive k rows x four adjacent columns), requests them all at once and converts them in
@@ -48,7 +36,7 @@ __device__ __forceinline__ void wave_fence() {
 // multipliers, which run its 16 k-steps while the next items are still arriving.  The roles keep the two request streams
 // on different wavefronts: s_waitcnt counts in order, and a multiplier that waited for its next weight fragments would
 // otherwise wait for every row requested before them.
-// EPI: epilogue_kind (vasr_internal.h), as pw_gemm_split_kernel's
+// EPI: epilogue_kind (vasr_internal.h), the Epilogue<EPI> of vasr_device.h that pw_gemm_split_kernel calls too
 template <int KS, bool DUAL, bool RES, int EPI = 0>
 __global__ __launch_bounds__(LNT, 1) void pw_gemm_latency_kernel(PwArgs a, int blocks_m, int tiles_t, int n_blocks) {
   constexpr int PI = KS / 16;          // items per staging thread = phases
@@ -56,11 +44,7 @@ __global__ __launch_bounds__(LNT, 1) void pw_gemm_latency_kernel(PwArgs a, int b
   extern __shared__ __attribute__((aligned(16))) uint4 Bl[];   // [plane][KS][2][LBN]
   auto bs = [&](int plane, int s, int kb, int n) -> uint4& { return Bl[((plane * KS + s) * 2 + kb) * LBN + n]; };
 
-  int bid = blockIdx.x;
-  {
-    const int q = n_blocks / 8, r = n_blocks % 8, xcd = bid % 8, slot = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
+  const int bid = xcd_remap(blockIdx.x, n_blocks);
   const int mb = bid % blocks_m;
   const int nt = bid / blocks_m;
   const int b = nt / tiles_t;
@@ -203,17 +187,10 @@ __global__ __launch_bounds__(LNT, 1) void pw_gemm_latency_kernel(PwArgs a, int b
     __syncthreads();   // the epilogue reuses the LDS image
   }
 
-  // ---- epilogue: BN affine (+ residual) + activation, as pw_gemm_split_kernel with TM = TN = 1 ----
+  // ---- epilogue: BN affine, then the shared Epilogue<EPI> and AmaxTracker (vasr_device.h); pw_gemm_split_kernel's passes at TM = TN = 1 ----
   if (a.relu & 2) return;
-  const int ylen = a.amax_y.p ? (a.lens_y ? a.lens_y[b] : a.frames) : 0;
-  unsigned ymax = 0;
-  auto track = [&](float v, int t) {
-    const unsigned u = __float_as_uint(v) & 0x7fffffffu;
-    ymax = (t < ylen && u > ymax) ? u : ymax;
-  };
-  const float relu_floor = (a.relu & 1) ? 0.f : -__builtin_inff();
-  float act_lo = 0.f, act_hi = 0.f;
-  if constexpr (EPI == 1) clamp_bounds(a.relu, a.act, act_lo, act_hi);
+  AmaxTracker amax{a.amax_y.p ? (a.lens_y ? a.lens_y[b] : a.frames) : 0};
+  const Epilogue<EPI> epi(a.relu, a.act, a.res_max);
   if (vec) {
     float* stage = reinterpret_cast<float*>(Bl) + wave * (2 * 8 * LBN);
     const int row = erow, c4 = ec4;
@@ -228,24 +205,10 @@ __global__ __launch_bounds__(LNT, 1) void pw_gemm_latency_kernel(PwArgs a, int b
         buf[(4 * kh + rr) * LBN + l31] = fmaf(v, scv[q][rr], shv[q][rr]);
       }
       wave_fence();
-      v4f v = *reinterpret_cast<const v4f*>(buf + row * LBN + 4 * c4);
-      if constexpr (EPI != 0) {
-        if (RES) v = a.res_max ? __builtin_elementwise_max(v, rv[q]) : v + rv[q];
-        if constexpr (EPI == 1) {
-          v = __builtin_elementwise_min(__builtin_elementwise_max(v, v4f{act_lo, act_lo, act_lo, act_lo}),
-                                        v4f{act_hi, act_hi, act_hi, act_hi});
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = selu(v[e]);
-        }
-      } else {
-        if (RES) v += rv[q];
-        v = __builtin_elementwise_max(v, v4f{relu_floor, relu_floor, relu_floor, relu_floor});
-      }
+      const v4f v = epi.template apply4<RES>(*reinterpret_cast<const v4f*>(buf + row * LBN + 4 * c4), rv[q]);
       const int m = mq + row, t = t0 + 4 * c4;
       *reinterpret_cast<v4f*>(a.y + ((int64_t)b * a.m_store + m) * a.ldy + t) = v;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) track(v[e], t + e);
+      amax.track4(v, t);
     }
   } else {
 #pragma unroll
@@ -255,26 +218,15 @@ __global__ __launch_bounds__(LNT, 1) void pw_gemm_latency_kernel(PwArgs a, int b
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
         const int m = mq + rr, t = t0 + l31;
-        float v = acc[4 * q + rr] * out_scale;
-        v = fmaf(v, sc[rr], sh[rr]);
-        if constexpr (EPI != 0) {
-          if (RES) {
-            const float r = a.res[((int64_t)b * a.M + m) * a.ldr + t];
-            v = a.res_max ? fmaxf(v, r) : v + r;
-          }
-          v = EPI == 1 ? fminf(fmaxf(v, act_lo), act_hi) : selu(v);
-        } else {
-          if (RES) v += a.res[((int64_t)b * a.M + m) * a.ldr + t];
-          if (a.relu & 1) v = fmaxf(v, 0.f);
-        }
+        const float v = epi.template apply<RES>(fmaf(acc[4 * q + rr] * out_scale, sc[rr], sh[rr]), a.res + ((int64_t)b * a.M + m) * a.ldr + t);
         if (full || (t < a.store_cols && m < a.m_store)) {
           a.y[((int64_t)b * a.m_store + m) * a.ldy + t] = v;
-          if (a.amax_y.p) track(v, t);
+          if (a.amax_y.p) amax.track(v, t);
         }
       }
     }
   }
-  if (a.amax_y.p) amax_publish(a.amax_y.p, a.amax_y.stride, b, (mb * tiles_t + nt % tiles_t) * LNW + wave, ymax, lane);
+  if (a.amax_y.p) amax_publish(a.amax_y.p, a.amax_y.stride, b, (mb * tiles_t + nt % tiles_t) * LNW + wave, amax.ymax, lane);
 }
 
 template <int KS, bool DUAL, bool RES>

@@ -54,13 +54,8 @@ namespace vasr {
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using v4f = __attribute__((ext_vector_type(4))) float;
-using v2f = __attribute__((ext_vector_type(2))) float;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
 
 enum { kBf16x3 = 0, kBf16x2 = 1, kF16x2 = 2 };
 
@@ -115,13 +110,6 @@ __device__ __forceinline__ f32x16 mma(uint4 a, uint4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
-// orders a wavefront's own LDS writes and reads for the compiler (the LDS pipeline itself keeps them in issue order)
-__device__ __forceinline__ void wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // NW wavefronts stacked along M, each TM m-tiles (32 rows) x all TN n-tiles (32 columns each):
 // workgroup tile (32*TM*NW) x (32*TN).
 template <int NW, int TM, int TN, int ARITH>
@@ -139,8 +127,7 @@ struct Geom {
   static_assert(PATCHES % NT == 0 && PPT >= 1, "staging patches must divide evenly over the threads");
 };
 
-// EPI (epilogue_kind, vasr_internal.h): 0 = the ReLU / add epilogue (relu flag: ReLU or nothing) the default models run;
-// 1 = a clamp to uniform bounds, 2 = SELU, both with the residual added or (a.res_max) combined by max.
+// EPI: epilogue_kind (vasr_internal.h), the shared Epilogue<EPI> of vasr_device.h; 0 is what the default models run
 template <int NW, int TM, int TN, bool MASK, bool RES, bool DUAL, int ARITH, bool CONV = false, bool GRP = false, int EPI = 0>
 __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int blocks_m, int tiles_t, int n_blocks) {
   using G = Geom<NW, TM, TN, ARITH>;
@@ -150,11 +137,7 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
     return Bs[(((buf * PL + plane) * STEPS + s) * 2 + kb) * BN + n];
   };
 
-  int bid = blockIdx.x;
-  {
-    const int q = n_blocks / 8, r = n_blocks % 8, xcd = bid % 8, slot = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
+  const int bid = xcd_remap(blockIdx.x, n_blocks);
   const int mb = bid % blocks_m;
   const int nt = bid / blocks_m;
   const int b = nt / tiles_t;
@@ -448,15 +431,8 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
 
   // ---- epilogue (as encoder_pw.hip): BN affine (+ residual) + activation, 128-byte row segments per half-wave ----
   // max |y| over the utterance's VALID output frames, for the split of the next kF16x2 consumer of y
-  const int ylen = a.amax_y.p ? (a.lens_y ? a.lens_y[b] : a.frames) : 0;
-  unsigned ymax = 0;
-  auto track = [&](float v, int t) {
-    const unsigned u = __float_as_uint(v) & 0x7fffffffu;
-    ymax = (t < ylen && u > ymax) ? u : ymax;
-  };
-  const float relu_floor = (a.relu & 1) ? 0.f : -__builtin_inff();   // max(v, floor): ReLU or nothing, without a branch
-  float act_lo = 0.f, act_hi = 0.f;
-  if constexpr (EPI == 1) clamp_bounds(a.relu, a.act, act_lo, act_hi);
+  AmaxTracker amax{a.amax_y.p ? (a.lens_y ? a.lens_y[b] : a.frames) : 0};
+  const Epilogue<EPI> epi(a.relu, a.act, a.res_max);
   // GRP: pre-shuffle row m = grp * mg + j is stored at row j * G + grp (GroupShuffle); otherwise at m
   auto orow = [&](int m) { return GRP ? (m - grp * mg) * ng + grp : m; };
   const bool full = (t0 + BN <= a.store_cols) && (m0 + BM <= a.m_store);
@@ -512,24 +488,10 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
         for (int k = 0; k < F4; ++k) {
           const int f = lane + 64 * k, row = f / (BN / 4), c4 = f % (BN / 4);
           const int m = mq + row, t = t0 + 4 * c4;
-          v4f v = pv[k];
-          if constexpr (EPI != 0) {
-            if (RES) v = a.res_max ? __builtin_elementwise_max(v, rv[k]) : v + rv[k];   // (a uniform select)
-            if constexpr (EPI == 1) {
-              v = __builtin_elementwise_min(__builtin_elementwise_max(v, v4f{act_lo, act_lo, act_lo, act_lo}),
-                                            v4f{act_hi, act_hi, act_hi, act_hi});
-            } else {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = selu(v[e]);
-            }
-          } else {
-            if (RES) v += rv[k];
-            v = __builtin_elementwise_max(v, v4f{relu_floor, relu_floor, relu_floor, relu_floor});
-          }
+          const v4f v = epi.template apply4<RES>(pv[k], rv[k]);
           v4f* dstp = reinterpret_cast<v4f*>(a.y + ((int64_t)b * a.m_store + orow(m)) * a.ldy + t);
           *dstp = v;   // (non-temporal stores for outputs beyond the Infinity Cache: measured, no gain)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) track(v[e], t + e);
+          amax.track4(v, t);
         }
       }
     }
@@ -549,27 +511,17 @@ __global__ __launch_bounds__(64 * NW, 2) void pw_gemm_split_kernel(PwArgs a, int
             const int t = t0 + j * 32 + l31;
             float v = acc[i][j][4 * q + rr];
             if constexpr (ARITH == kF16x2) v *= out_scale;
-            v = fmaf(v, sc[rr], sh[rr]);
-            if constexpr (EPI != 0) {
-              if (RES) {
-                const float r = a.res[((int64_t)b * a.M + orow(m)) * a.ldr + t];
-                v = a.res_max ? fmaxf(v, r) : v + r;
-              }
-              v = EPI == 1 ? fminf(fmaxf(v, act_lo), act_hi) : selu(v);
-            } else {
-              if (RES) v += a.res[((int64_t)b * a.M + orow(m)) * a.ldr + t];
-              if (a.relu & 1) v = fmaxf(v, 0.f);
-            }
+            v = epi.template apply<RES>(fmaf(v, sc[rr], sh[rr]), a.res + ((int64_t)b * a.M + orow(m)) * a.ldr + t);
             if (full || (t < a.store_cols && m < a.m_store)) {
               a.y[((int64_t)b * a.m_store + orow(m)) * a.ldy + t] = v;
-              if (a.amax_y.p) track(v, t);
+              if (a.amax_y.p) amax.track(v, t);
             }
           }
         }
       }
     }
   }
-  if (a.amax_y.p) amax_publish(a.amax_y.p, a.amax_y.stride, b, (mb * tiles_t + nt % tiles_t) * NW + wave, ymax, lane);
+  if (a.amax_y.p) amax_publish(a.amax_y.p, a.amax_y.stride, b, (mb * tiles_t + nt % tiles_t) * NW + wave, amax.ymax, lane);
 }
 
 template <int NW, int TM, int TN, bool MASK, bool RES, bool DUAL, int ARITH, bool CONV = false, bool GRP = false>

@@ -13,6 +13,7 @@
 
 #include "vasr_internal.h"
 #include "len_chain.h"
+#include "vasr_device.h"
 
 namespace vasr {
 
@@ -30,12 +31,7 @@ __device__ __forceinline__ cf cmul_negi(cf a) { return {a.im, -a.re}; }
 
 // The FFT scratch, power spectrum and tile columns of a frame belong to ONE wavefront, and the LDS pipeline executes a
 // wavefront's accesses in issue order: a compiler-level fence is all the frame loop needs (it used six workgroup
-// barriers per frame, i.e. the wavefronts of a workgroup kept waiting for each other 48 times per block).
-__device__ __forceinline__ void wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+// barriers per frame, i.e. the wavefronts of a workgroup kept waiting for each other 48 times per block): wave_fence().
 
 // grid (ceil(T / kFramesPerBlock), B), block kThreads.  kFramesPerBlock = 32 (four frames per wavefront, one after the other:
 // the throughput form, 62.5 % of the staged samples shared) or 8 (one frame per wavefront: a small batch's few workgroups

@@ -4,6 +4,27 @@
 
 namespace vasr {
 
+// native vectors: a v4f is one ds_read_b128 / global dwordx4, f32x16 the accumulator of a 32x32 MFMA, f16x8 its 16-bit operand
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+using v4f = __attribute__((ext_vector_type(4))) float;
+using v2f = __attribute__((ext_vector_type(2))) float;
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
+
+// orders a wavefront's own LDS writes and reads for the compiler (the LDS pipeline itself keeps them in issue order)
+__device__ __forceinline__ void wave_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// XCD-aware remap of a 1-D grid: workgroup i runs on XCD i % 8 (each with a private L2), so consecutive LOGICAL ids --
+// neighbours in (m-block, time-tile) order, which share activations or a window's halo -- are dealt to one XCD
+__device__ __forceinline__ int xcd_remap(int bid, int n_blocks) {
+  const int q = n_blocks / 8, r = n_blocks % 8, xcd = bid % 8, slot = bid / 8;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+}
+
 // Wave-wide unsigned maximum, uniform result: butterfly inside each 16-lane row on DPP (VALU only -- a ds_bpermute
 // chain is six dependent LDS round trips at the tail of every wavefront), then the four row maxima through SGPRs.
 __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
@@ -27,11 +48,6 @@ constexpr float kSeluAlpha = 1.6732632423543772848170429916717f;
 __device__ __forceinline__ float selu(float v) {
   return v > 0.f ? kSeluLambda * v : (kSeluLambda * kSeluAlpha) * expm1f(v);
 }
-// the clamp of epilogue kind 1 (epilogue_kind, vasr_internal.h): Hardtanh [-1, 1], ReLU [0, inf), nothing (relu flag clear)
-__device__ __forceinline__ void clamp_bounds(int relu, int act, float& lo, float& hi) {
-  lo = (relu & 1) ? (act == 1 ? -1.f : 0.f) : -__builtin_inff();
-  hi = ((relu & 1) && act == 1) ? 1.f : __builtin_inff();
-}
 // act: 0 ReLU, 1 Hardtanh, 2 SELU (uniform across the launch)
 __device__ __forceinline__ float activate(float v, int act) {
   if (act == 2) return selu(v);
@@ -39,7 +55,63 @@ __device__ __forceinline__ float activate(float v, int act) {
   return v > 0.f ? v : 0.f;
 }
 
+// ---- the GEMM epilogues' residual + activation (encoder_pw*.hip, encoder_fused.hip), after the BN affine ----
+// EPI = epilogue_kind (vasr_internal.h): 0 = residual added, ReLU or nothing (relu flag); 1 = a clamp to uniform bounds --
+// Hardtanh [-1, 1], ReLU [0, inf), nothing (relu flag clear); 2 = SELU; under 1 and 2 the residual is added or (res_max)
+// combined by max, a uniform select.  Built once per kernel; RES = the launch has a residual tensor.  The throughput and
+// latency GEMMs give the same bits because both call this.
+template <int EPI>
+struct Epilogue {
+  bool relu, res_max;
+  float lo, hi;   // kind 1: the clamp; kind 0: lo = the ReLU floor of the float4 form (0, or -inf for nothing)
+  __device__ __forceinline__ Epilogue(int relu_flag, int act, int res_max_flag) : relu(relu_flag & 1), res_max(res_max_flag) {
+    lo = relu ? (EPI == 1 && act == 1 ? -1.f : 0.f) : -__builtin_inff();
+    hi = (relu && act == 1) ? 1.f : __builtin_inff();
+  }
+  // one element (edge tiles, the fp32 GEMM); r is dereferenced only under RES
+  template <bool RES>
+  __device__ __forceinline__ float apply(float v, const float* __restrict__ r) const {
+    if constexpr (EPI != 0) {
+      if constexpr (RES) v = res_max ? fmaxf(v, *r) : v + *r;
+      return EPI == 1 ? fminf(fmaxf(v, lo), hi) : selu(v);
+    } else {
+      if constexpr (RES) v += *r;
+      return relu ? fmaxf(v, 0.f) : v;   // (relu flag clear: a NaN stays a NaN)
+    }
+  }
+  // a float4 row piece (interior tiles): straight-line, ReLU as a maximum with the uniform floor.  NOT the scalar form's
+  // arithmetic when the relu flag is clear: max(NaN, -inf) is -inf.  The two are kept apart, each as it always was.
+  template <bool RES = false>
+  __device__ __forceinline__ v4f apply4(v4f v, const v4f& r = v4f{}) const {
+    if constexpr (EPI != 0) {
+      if constexpr (RES) v = res_max ? __builtin_elementwise_max(v, r) : v + r;
+      if constexpr (EPI == 1) return __builtin_elementwise_min(__builtin_elementwise_max(v, v4f{lo, lo, lo, lo}), v4f{hi, hi, hi, hi});
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = selu(v[e]);
+      return v;
+    } else {
+      if constexpr (RES) v += r;
+      return __builtin_elementwise_max(v, v4f{lo, lo, lo, lo});
+    }
+  }
+};
+
 __device__ __forceinline__ unsigned abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
+
+// largest |y| over an utterance's VALID output frames (t < ylen; ylen = 0 without a table), as fp32 bits: a lane's share
+// of what amax_publish() stores for the split of the next kF16x2 consumer of y
+struct AmaxTracker {
+  int ylen;
+  unsigned ymax = 0;
+  __device__ __forceinline__ void track(float v, int t) {
+    const unsigned u = abs_bits(v);
+    ymax = (t < ylen && u > ymax) ? u : ymax;
+  }
+  __device__ __forceinline__ void track4(v4f v, int t) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) track(v[e], t + e);
+  }
+};
 
 // ---- per-utterance maxima (AmaxTab, vasr_internal.h) ----
 // Producer side: every wavefront of the producing launch owns ONE slot per utterance it touches and stores its maximum
