@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- whole-job throughput of the viet-asr hot path on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}] [--gemm ...] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}] [--gemm ...] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set-up, W warm-up steps, K timed steps, the files of
+--dump-outputs, and ONE JSON line on rank 0 with the driver contract keys (metric, value, unit, n_gpus, steps, warmup,
+ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config, utts_per_sec; under a launcher also the ranks and
+their own milliseconds).  Everything else this file measures takes runs of its own after the timed steps and is asked for
+with --full, which adds the blocks listed below to the SAME line; the timed steps and the contract keys are the same either
+way.
 
 One *step* = one pass of the hot path over one batch of synthetic audio per GPU (input already resident in HBM),
 then the gather of the collapsed id sequences to every rank (the reference's _infer gathers each returned tensor with
@@ -22,7 +29,7 @@ Workloads (BASELINE.json `configs`, 0-based):
                                     "strong", and the line carries the ranks' min / max milliseconds.  --ragged draws clip
                                     lengths in [15 s, 30 s] and deals them to the ranks with dist.balanced_shards.
 
-The default invocation (config 3, N = 1) also runs 5 steps each of configs 2, 4 and 5 after the headline and adds them
+Under --full the default invocation (config 3, N = 1) also runs 5 steps each of configs 2, 4 and 5 after the headline and adds them
 as "configs": {"2": {...}, "3r": {...}, "4": {...}, "5": {...}} to the SAME JSON line ("3r" = the headline shape with ragged
 lengths U[L/2, L]), a "latency" block (batch 1 / 8 of 15x5, and the reference's own serving shape: batch 1, 12x1_vi, beam
 50 / 100 + LM, split into acoustic pass and search) and a "sol" block (speed-of-light floors of the headline step).
@@ -34,7 +41,7 @@ port of 127.0.0.1); launched by torchrun / the driver it uses the ranks it is gi
 `--dump-outputs DIR` writes what the last timed step returned on rank 0 as float32 DIR/<name>.npy (ids, -1 past id_len;
 id_len; enc_len; score under --config 4).  Inputs and weights are seeded, so two builds can be compared file by file.
 
-Prints ONE JSON line on rank 0 with the driver contract keys plus
+--full adds to the line (--no-cpu-baseline, --no-other-gemm and --no-side-configs leave single blocks out again)
   roofline      -- dominant kernel family (1x1-conv GEMMs, incl. the fused depthwise + pointwise launches): executed MFMA
                    flops of the launches that ran / their summed kernel durations (per-launch dispatch timestamps,
                    hipExtLaunchKernelGGL) vs the dense MFMA peak of the operand type
@@ -562,9 +569,12 @@ def main():
     ap.add_argument("--beam-width", type=int, default=128)
     ap.add_argument("--no-lm", action="store_true", help="--config 4 without the n-gram model")
     ap.add_argument("--no-overlap", action="store_true", help="--config 4: search on the acoustic stream (serialised)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-gemm", action="store_true", help="skip the comparison pass in the other GEMM arithmetic")
-    ap.add_argument("--no-side-configs", action="store_true", help="skip the configs 2 / 4 / 5 and latency blocks of the default line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and add to the line: per-kernel-class rates against the roofline, the "
+                         "other GEMM arithmetic, the box normalisers, configs 2 / 4 / 5, latency and speed-of-light blocks, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-other-gemm", action="store_true", help="--full without the comparison pass in the other GEMM arithmetic")
+    ap.add_argument("--no-side-configs", action="store_true", help="--full without the configs 2 / 4 / 5, latency and sol blocks of the default line")
     ap.add_argument("--spawn", action="store_true", help="go through the self-launcher even for --gpus 1 (RCCL world of 1)")
     ap.add_argument("--gemm", choices=sorted(GEMM_MODES), default=None,
                     help="arithmetic of the 1x1-conv GEMMs (default: the library's default mode)")
@@ -725,7 +735,46 @@ def main():
     else:
         audio_all, clips_all = audio_sec_per_step, clips_per_step
 
-    # ---- second pass, same K steps, with per-kernel-class HIP events on the launch stream ----
+    def finish(line):
+        if rank == 0:
+            if dist is not None:
+                import ctypes
+                ctypes.CDLL(None).fflush(None)      # RCCL's version banner sits in C stdio's buffer: keep the JSON line last
+            print(json.dumps(line, ensure_ascii=False), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    out = None
+    if rank == 0:
+        what = {"greedy": "greedy CTC", "beam": f"beam search (width {a.beam_width}" + (", 3-gram LM" if lm_info else ", no LM") + ")"}[decoder]
+        if job:
+            wl = (f"BASELINE configs[4]: the {JOB_CLIPS}-clip job, {model} {what}, {seconds:g}s {rate // 1000}kHz clips"
+                  f"{' (lengths in [15, 30] s)' if a.ragged else ''} -> 16 kHz on the device, sharded over {world} ranks "
+                  f"({clips_per_step} clips on rank 0 in {len(passes)} pass(es) of <= {batch}), wav in HBM -> collapsed ids")
+        else:
+            wl = (f"BASELINE configs[{a.config - 1}]: {model} {what}, batch={batch}x{seconds:g}s "
+                  f"{rate // 1000}kHz mono per GPU{' (ragged lengths)' if a.ragged else ''}"
+                  f"{' -> 16 kHz on the device' if rate != 16000 else ''}, wav in HBM -> "
+                  f"{'collapsed ids' if decoder == 'greedy' else 'best-hypothesis ids'}")
+        out = {
+            "metric": "real_time_factor", "value": round(audio_all * a.steps / elapsed, 1),
+            "unit": "audio-sec/wall-sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": round(elapsed / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong" if job else "weak",
+            "vs_baseline": None, "dtype": GEMM_MODES[gemm][2], "data": "synthetic",
+            "config": {"workload": wl, "batch_per_gpu": batch, "clip_seconds": seconds, "clips_per_step_all_ranks": clips_all,
+                       "parallelism": f"utterance-shard x{world}"},
+            "utts_per_sec": round(clips_all * a.steps / elapsed, 1),
+        }
+        if sharding:
+            out["sharding"] = sharding
+        if rccl is not None:
+            out.update(rccl)
+    if not a.full:
+        return finish(out)
+
+    # ---- --full: everything from here on takes runs of its own, after the line's headline keys are settled ----
+    # second pass, same K steps, with per-kernel-class HIP events on the launch stream
     wav16, ln16 = acoustic_input(passes[0])
     torch.cuda.synchronize()
     eng.handle.profile_begin()
@@ -826,24 +875,7 @@ def main():
         pmc_of = "" if headline else ("c5_" if shard5 else None)
         pw_traffic, traffic_src = pmc_traffic(kname, arith_tag, pmc_of) if pmc_of is not None else (None, None)
         dw_traffic, _ = pmc_traffic("dw_", "", pmc_of) if pmc_of is not None else (None, None)
-        what = {"greedy": "greedy CTC", "beam": f"beam search (width {a.beam_width}" + (", 3-gram LM" if lm_info else ", no LM") + ")"}[decoder]
-        if job:
-            wl = (f"BASELINE configs[4]: the {JOB_CLIPS}-clip job, {model} {what}, {seconds:g}s {rate // 1000}kHz clips"
-                  f"{' (lengths in [15, 30] s)' if a.ragged else ''} -> 16 kHz on the device, sharded over {world} ranks "
-                  f"({clips_per_step} clips on rank 0 in {len(passes)} pass(es) of <= {batch}), wav in HBM -> collapsed ids")
-        else:
-            wl = (f"BASELINE configs[{a.config - 1}]: {model} {what}, batch={batch}x{seconds:g}s "
-                  f"{rate // 1000}kHz mono per GPU{' (ragged lengths)' if a.ragged else ''}"
-                  f"{' -> 16 kHz on the device' if rate != 16000 else ''}, wav in HBM -> "
-                  f"{'collapsed ids' if decoder == 'greedy' else 'best-hypothesis ids'}")
-        out = {
-            "metric": "real_time_factor", "value": round(audio_all * a.steps / elapsed, 1),
-            "unit": "audio-sec/wall-sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(elapsed / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong" if job else "weak",
-            "vs_baseline": None, "dtype": dtype_str, "data": "synthetic",
-            "config": {"workload": wl, "batch_per_gpu": batch, "clip_seconds": seconds, "clips_per_step_all_ranks": clips_all,
-                       "parallelism": f"utterance-shard x{world}"},
-            "utts_per_sec": round(clips_all * a.steps / elapsed, 1),
+        out.update({
             "roofline": {"kernel": f"{kname} (1x1 conv as {'split-operand ' if terms > 1 else ''}MFMA GEMM + BN/residual/ReLU epilogue; "
                                    "the fused depthwise + pointwise launches are listed under `fused`, both together under gemm_family)",
                          "bound": "mfma", "achieved": round(cr["exec_tflops"], 2), "peak": cr["peak"],
@@ -884,14 +916,10 @@ def main():
             "other_ms_per_step": {"frontend": round(prof["frontend"]["ms"] / a.steps, 3),
                                   "head": round(prof["head"]["ms"] / a.steps, 3)},
             "sample_transcript": hyp[0][:32],
-        }
+        })
         if job and len(passes) > 1:
             out["roofline"]["note"] = out["depthwise"]["note"] = "kernel classes measured on the first pass of rank 0's share"
-        if sharding:
-            out["sharding"] = sharding
         out.update(extra)
-        if rccl is not None:
-            out.update(rccl)
         if other is not None:
             out["other_gemm_arithmetic"] = other
         norm = box_normalisers(dev, gemm)
@@ -944,13 +972,7 @@ def main():
             out["sol"] = sol_block(cfg, work, batch, samples, elapsed / a.steps * 1e3, launches_b1, norm)
         if world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(model, seed, decoder, lm_path, batch=batch, clip_seconds=seconds)
-        if dist is not None:
-            import ctypes
-            ctypes.CDLL(None).fflush(None)      # RCCL's version banner sits in C stdio's buffer: keep the JSON line last
-        print(json.dumps(out, ensure_ascii=False), flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish(out)
 
 
 if __name__ == "__main__":

@@ -290,7 +290,7 @@ def test_bench_self_launch_matches_plain_run_and_refuses_missing_devices(gpu):
     gather in the loop): its value must equal the plain single-process run within 2 % (best of two each -- the two forms
     run the same kernels; the gather is asynchronous).  With more GPUs requested than the box has: a clear message and
     exit code 3, nothing run."""
-    common = ["--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-other-gemm", "--no-side-configs"]
+    common = ["--steps", "30", "--warmup", "5"]
     plain, spawned = [], []
     for _ in range(2):
         rc, j, log = _bench(common)
@@ -307,10 +307,26 @@ def test_bench_self_launch_matches_plain_run_and_refuses_missing_devices(gpu):
     assert out.returncode == 3 and f"needs {have + 1} visible HIP devices" in out.stderr, (out.returncode, out.stderr[-500:])
 
 
+def test_bench_plain_run_prints_the_contract_keys_and_measures_nothing_after_its_steps(gpu):
+    """Without --full the line is the headline figure and what describes its steps: none of the blocks that take runs of
+    their own after the timed region (test_bench_default_line_... and test_bench_config_modes_... check them under --full)."""
+    rc, j, log = _bench(["--steps", "3", "--warmup", "1"])
+    assert rc == 0 and j is not None, log
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "utts_per_sec"):
+        assert k in j, k
+    assert j["metric"] == "real_time_factor" and j["unit"] == "audio-sec/wall-sec" and j["higher_is_better"] is True
+    assert (j["steps"], j["warmup"], j["n_gpus"]) == (3, 1, 1) and "configs[2]" in j["config"]["workload"]
+    assert j["value"] > 2000 and abs(j["value"] * j["ms_per_step"] / (640.0 * 1e3) - 1.0) < 1e-3     # 64 x 10 s per step
+    for k in ("roofline", "depthwise", "fused", "other_ms_per_step", "other_gemm_arithmetic", "box", "configs", "latency", "sol",
+              "cpu_baseline"):
+        assert k not in j, k
+
+
 def test_bench_default_line_carries_every_baseline_config_and_the_latency_block(gpu):
-    """the driver only ever sees the default line, so it must carry configs 2, 4 and 5 (5 steps each) and the
-    batch-1 / batch-8 latency of the whole path next to the headline, with their roofline fractions."""
-    rc, j, log = _bench(["--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-other-gemm"])
+    """one line must carry configs 2, 4 and 5 (5 steps each) and the batch-1 / batch-8 latency of the whole path
+    next to the headline, with their roofline fractions: the default workload's line under --full."""
+    rc, j, log = _bench(["--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-other-gemm"])
     assert rc == 0 and j is not None, log
     assert "configs[2]" in j["config"]["workload"] and j["value"] > 2000
     for cid, tag in (("2", "quartznet12x1_vi"), ("4", "beam"), ("5", "512x30s")):
@@ -327,11 +343,12 @@ def test_bench_default_line_carries_every_baseline_config_and_the_latency_block(
 
 def test_bench_job_mode_of_config5_in_a_world_of_one(gpu):
     """`--gpus N --config 5` walks the whole 4096-clip job (strong scaling, per-rank min / max); the code path is run here
-    with the job shrunk to 256 clips on the one GPU there is (RCCL world of one via --spawn), equal-length and ragged."""
+    with the job shrunk to 256 clips on the one GPU there is (RCCL world of one via --spawn), equal-length and ragged; under
+    --full, so that the per-class pass over a rank's first pass runs in the job form too."""
     import json
     env = dict(os.environ, VASR_BENCH_FORCE_JOB="1", VASR_BENCH_JOB_CLIPS="256")
     for extra in ([], ["--ragged"]):
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "5", "--spawn", "--batch", "128", "--steps",
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "5", "--spawn", "--batch", "128", "--steps",
                               "2", "--warmup", "1", "--no-cpu-baseline", "--no-other-gemm"] + extra, env=env, capture_output=True,
                              text=True, timeout=900)
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -345,8 +362,8 @@ def test_bench_job_mode_of_config5_in_a_world_of_one(gpu):
 
 @pytest.mark.parametrize("config", [2, 4, 5])
 def test_bench_config_modes_print_the_contract(gpu, config):
-    """bench.py --config {2,4,5}: same JSON contract as the default line, workload named after BASELINE.json's entry."""
-    rc, j, log = _bench(["--config", str(config), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-other-gemm"])
+    """bench.py --full --config {2,4,5}: same JSON contract as the default line, workload named after BASELINE.json's entry."""
+    rc, j, log = _bench(["--full", "--config", str(config), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-other-gemm"])
     assert rc == 0 and j is not None, log
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline"):

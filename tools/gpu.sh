@@ -25,7 +25,7 @@ task_full() {
 O=$R/gpurun_out/${1:-full}; mkdir -p $O; rm -f $R/gpurun_out/parity_errors.jsonl; cd $R
 (time timeout 2400 python -m pytest tests -m gpu -q --timeout 900 -p no:cacheprovider) > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log
-timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cp $R/gpurun_out/parity_errors.jsonl $O/ 2>/dev/null
 tail -8 $O/pytest.log; tail -3 $O/smoke.log; head -c 600 $O/bench_default.json
 }
@@ -35,7 +35,7 @@ task_quick() {
 O=$R/gpurun_out/${1:-quick}; mkdir -p $O; cd $R
 timeout 1200 python -m pytest ${TESTS:-tests/test_beam.py tests/test_gpu_parity.py} -m gpu -q -x -p no:cacheprovider > $O/pytest.log 2>&1; tail -4 $O/pytest.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu | tail -3
-timeout 600 python bench.py ${BENCH_ARGS:---no-cpu-baseline --no-other-gemm --no-side-configs} 2> $O/bench.err | tee $O/bench.json | python -c "
+timeout 600 python bench.py ${BENCH_ARGS:---full --no-cpu-baseline --no-other-gemm --no-side-configs} 2> $O/bench.err | tee $O/bench.json | python -c "
 import sys, json
 j = json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1])
 print('step %.3f ms = %.0fx | gemm %.3f ms frac %.3f (of measured %s) | dw %.3f ms frac %.3f | fused %.3f ms | other %s | box %s' % (j['ms_per_step'], j['value'], j['roofline']['ms_per_step'], j['roofline']['frac'], j['roofline'].get('frac_of_measured'), j['depthwise']['ms_per_step'], j['depthwise']['frac'], j['fused']['ms_per_step'], j['other_ms_per_step'], j.get('box')))"
@@ -47,7 +47,7 @@ print('step %.3f ms = %.0fx | gemm %.3f ms frac %.3f (of measured %s) | dw %.3f 
 task_prof() {
 local O=$R/gpurun_out/${1:-prof}; mkdir -p $O   # (local: task_final calls this twice and keeps its own $O)
 local ARGS PARGS f
-ARGS=${BENCH_ARGS:---steps 10 --warmup 2 --no-cpu-baseline --no-other-gemm --no-side-configs}
+ARGS=${BENCH_ARGS:---full --steps 10 --warmup 2 --no-cpu-baseline --no-other-gemm --no-side-configs}
 PARGS=${PMC_BENCH_ARGS:-$ARGS}
 cd /tmp && export TMPDIR=/tmp
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py $ARGS > $O/bench_under_rocprof.json 2> $O/stats.err
@@ -68,10 +68,10 @@ timeout 1800 python -m pytest tests -m gpu -q --timeout 900 -p no:cacheprovider 
 cp $R/gpurun_out/parity_errors.jsonl $O/parity_errors.jsonl 2>/dev/null
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 task_prof $TAG/headline > $O/prof_headline.log 2>&1
-BENCH_ARGS="--config 5 --steps 3 --warmup 1 --no-cpu-baseline --no-other-gemm" task_prof $TAG/c5 > $O/prof_c5.log 2>&1
+BENCH_ARGS="--full --config 5 --steps 3 --warmup 1 --no-cpu-baseline --no-other-gemm" task_prof $TAG/c5 > $O/prof_c5.log 2>&1
 cd $R
-timeout 600 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
-for c in 2 4 5; do timeout 300 python bench.py --config $c --steps $([ $c = 5 ] && echo 5 || echo 20) --warmup 3 --no-other-gemm --no-cpu-baseline > $O/bench_c$c.json 2> $O/bench_c$c.err; done
+timeout 600 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
+for c in 2 4 5; do timeout 300 python bench.py --full --config $c --steps $([ $c = 5 ] && echo 5 || echo 20) --warmup 3 --no-other-gemm --no-cpu-baseline > $O/bench_c$c.json 2> $O/bench_c$c.err; done
 python tools/b1_serving.py > $O/b1_vi12x1.json 2> /dev/null
 python tools/b1_serving.py --model quartznet15x5 --seconds 10 --no-beam > $O/b1_15x5.json 2> /dev/null
 cd /tmp && export TMPDIR=/tmp
