@@ -181,6 +181,22 @@ VASR_API int vasr_set_block_norm(vasr_handle* h, int block, int norm_groups);
  * models run exactly the kernels they ran before.  (ABI 8: a function, no layout change.) */
 VASR_API int vasr_set_activation(vasr_handle* h, int activation, int residual_mode);
 
+/* JasperDecoderForClassification (jasper.py:257-319) as the handle's head, in place of a CTC head: the handle is created with
+ * dec_feat_in = 0 and num_classes = 0.  pooling 0 = 'avg' (nn.AdaptiveAvgPool1d(1)), 1 = 'max' (nn.AdaptiveMaxPool1d(1)); the
+ * weights arrive through vasr_load_weight under the reference's keys, decoder_layers.0.weight [num_classes][feat_in] (2-D: an
+ * nn.Linear) and decoder_layers.0.bias [num_classes].  Between vasr_create and vasr_finalize.  Refused here: a CTC head on the
+ * same handle, a pooling code out of range, feat_in or num_classes <= 0 (VASR_ERR_INVALID), feat_in > 1024
+ * (VASR_ERR_UNSUPPORTED).  vasr_finalize refuses, before it touches a device, a feat_in that is not the encoder's output width
+ * and a weight of any other shape (VASR_ERR_INVALID) and a missing weight (VASR_ERR_STATE).
+ * The pool is taken over the WIDTH OF THE TENSOR AS HANDED IN -- all T' frames of every row, as the reference's forward does,
+ * which takes no lengths; after CropOrPadSpectrogramAugmentation every row is audio_length frames long anyway.  This differs
+ * from vasr_set_block_se, whose time mean is over each row's own frames.  Never over the columns between T' and the
+ * 128-frame pitch of an internal buffer (vasr_padded_frames).  The maximum is taken with fmaxf: a NaN frame is skipped
+ * (nn.AdaptiveMaxPool1d propagates it); the two agree wherever no NaN is present.  Every sum has one fixed order that depends
+ * on (feat_in, T') alone and there are no atomics: a row's output bits are the same whatever else is in the batch.
+ * (ABI 8: a function, no layout change.) */
+VASR_API int vasr_set_classifier(vasr_handle* h, int feat_in, int num_classes, int pooling);
+
 /* Checks that every tensor arrived, folds eval-mode BatchNorm1d(eps=1e-3)
  * (parts/jasper.py:392) into per-channel (scale, shift), packs the 1x1-conv weights
  * K-major for the MFMA kernels and uploads everything.  Needed before any compute call. */
@@ -251,6 +267,39 @@ VASR_API int vasr_transcribe_greedy_pcm16(vasr_handle* h, const int16_t* d_pcm, 
                                  int64_t samples, int64_t* d_pred, int32_t* d_ids, int32_t* d_id_len,
                                  float* d_logp, float* d_enc_len, void* d_workspace, size_t workspace_bytes,
                                  vasr_stream stream);
+
+/* ---- the classification path (speech commands, keywords) ----------------------------------- */
+/* CropOrPadSpectrogramAugmentation.forward (audio_preprocessing.py:666-738) on contiguous port tensors.
+ *   d_in [B][feat][frames] f32 -> d_out [B][feat][audio_length] f32, d_out_len [B] i64 = audio_length (may be NULL)
+ * frames > audio_length: row b is d_in[b, :, off : off + audio_length] with off = d_offsets[b] (device i64 [B], required;
+ * the reference draws torch.randint(0, frames - audio_length + 1, [B])), clamped into [0, frames - audio_length] so that no
+ * read leaves the row.  Otherwise (frames == audio_length included, with zero pads) the row sits between
+ * left = (audio_length - frames) / 2 zero frames and audio_length - frames - left on the right: the odd frame goes right.
+ * A copy: every value is bit-equal to the one it was cut from.  d_offsets may be NULL when frames <= audio_length. */
+VASR_API int vasr_crop_or_pad_f32(const float* d_in, int batch, int feat, int64_t frames, int64_t audio_length,
+                                  const int64_t* d_offsets, float* d_out, int64_t* d_out_len, vasr_stream stream);
+
+/* JasperDecoderForClassification.forward (jasper.py:310-319): pool over time, Linear, optional softmax (vasr_set_classifier).
+ *   d_enc [B][feat_in][T'] f32 contiguous -> d_out [B][num_classes] f32: logits, or (softmax != 0) F.softmax(logits, -1)
+ * Workspace: B * feat_in * 4 bytes (the pooled vectors). */
+VASR_API int vasr_classifier_f32(vasr_handle* h, const float* d_enc, int batch, int64_t enc_frames, int softmax, float* d_out,
+                                 void* d_workspace, size_t workspace_bytes, vasr_stream stream);
+
+/* The whole classification path in one call, as vasr_transcribe_greedy_f32 is for CTC: wav -> mel -> crop / pad to
+ * audio_length -> encoder -> pool + Linear (+ softmax), all intermediates in the workspace; the crop / pad writes straight
+ * into the encoder's padded-pitch input buffer.  The handle needs a front end, an encoder and vasr_set_classifier.
+ *   d_wav [B][samples] f32 (rows zero padded), d_len [B] i64; d_offsets [B] i64 device, may be NULL when
+ *   1 + samples / hop <= audio_length (no crop can occur); d_out [B][num_classes] f32;
+ *   d_mel (may be NULL) [B][n_mels][audio_length] f32: the encoder's input, CropOrPadSpectrogramAugmentation's output port.
+ * The reference's batched semantics by default: the crop acts on the batch tensor's width, every row of which is
+ * 1 + samples / hop frames.  With vasr_set_row_independent row b is as wide as a call on it alone makes it, 1 + d_len[b] / hop
+ * frames, reflected at its own end, and is cut (d_offsets[b], clamped into the row) or centred on that width: its output
+ * is what a batch-1 call on the row alone returns, bit for bit.
+ * Workspace: vasr_classify_workspace_bytes(h, batch, samples, audio_length). */
+VASR_API size_t vasr_classify_workspace_bytes(const vasr_handle* h, int batch, int64_t samples, int64_t audio_length);
+VASR_API int vasr_classify_f32(vasr_handle* h, const float* d_wav, const int64_t* d_len, int batch, int64_t samples,
+                               int64_t audio_length, const int64_t* d_offsets, int softmax, float* d_out, float* d_mel,
+                               void* d_workspace, size_t workspace_bytes, vasr_stream stream);
 
 /* GEMM arithmetic of the 1x1 convolutions of the encoder:
  *   0            v_mfma_f32_32x32x2_f32: bit-for-bit an fp32 fmaf chain;

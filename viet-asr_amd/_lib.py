@@ -70,6 +70,11 @@ SIGNATURES = {
     "vasr_set_block_norm": (C.c_int, [_P, C.c_int, C.c_int]),
     "vasr_set_activation": (C.c_int, [_P, C.c_int, C.c_int]),
     "vasr_set_block_groups": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    "vasr_set_classifier": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    "vasr_crop_or_pad_f32": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    "vasr_classifier_f32": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, C.c_size_t, _P]),
+    "vasr_classify_workspace_bytes": (C.c_size_t, [_P, C.c_int, C.c_int64, C.c_int64]),
+    "vasr_classify_f32": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int64, _P, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "vasr_beam_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
     "vasr_beam_search_f32": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P,
                                        _P, _P, _P, _P, C.c_size_t, _P]),
@@ -170,14 +175,16 @@ def _fptr(a):
 
 
 class Handle:
-    """Owns one vasr_handle: any subset of {front end, encoder, CTC head}."""
+    """Owns one vasr_handle: any subset of {front end, encoder, CTC head or classification head}."""
 
     def __init__(self, frontend=None, feat_in=0, blocks=None, dec_feat_in=0, num_classes=0, se=None, groups=None, norm=None,
-                 activation=0, residual_mode=0):
+                 activation=0, residual_mode=0, classifier=None):
         """se: per block, the squeeze-and-excitation reduction ratio (0 = none; engine.se_from_config).  groups: per block,
         (groups, heads) (engine.groups_from_config; (1, -1) = none).  norm: per block, the GroupNorm group count (0 =
         BatchNorm; engine.norm_from_config).  activation (0 relu, 1 hardtanh, 2 selu), residual_mode (0 add, 1 max): the
-        encoder's, engine.activation_from_config; codes out of range raise ValueError."""
+        encoder's, engine.activation_from_config; codes out of range raise ValueError.  classifier: (feat_in, num_classes,
+        pooling 0 avg / 1 max) of a JasperDecoderForClassification head (vasr_set_classifier), instead of dec_feat_in /
+        num_classes of a CTC head."""
         L = lib()
         self._keep = []
         md = ModelDesc()
@@ -223,6 +230,9 @@ class Handle:
         if activation or residual_mode:
             check(L.vasr_set_activation(h, int(activation), int(residual_mode)))
         self.num_classes = int(num_classes)
+        if classifier is not None:
+            check(L.vasr_set_classifier(h, *[int(v) for v in classifier]))
+            self.num_classes = int(classifier[1])
 
     def load_state_dict(self, sd):
         """sd: {reference state_dict key: array-like}; integer tensors (num_batches_tracked) are skipped."""

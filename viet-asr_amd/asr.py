@@ -14,14 +14,14 @@ import torch.nn as nn
 
 from . import _lib, stages
 from .core import (AcousticEncodedRepresentation, AudioSignal, DataLayerNM, DeviceType, LengthsType,
-                   LogprobsType, MelSpectrogramType, NeuralType, NonTrainableNM, PredictionsType,
+                   LogitsType, LogprobsType, MelSpectrogramType, NeuralType, NonTrainableNM, PredictionsType,
                    SpectrogramType, TrainableNM)
 from .engine import (activation_from_config, blocks_from_config, check_dense_layout, norm_from_config, groups_from_config,
                      se_from_config)
 from .frontend_tables import frontend_description
 
-__all__ = ["AudioToMelSpectrogramPreprocessor", "JasperEncoder", "JasperDecoderForCTC", "GreedyCTCDecoder",
-           "BeamSearchDecoderWithLM", "AudioDataLayer"]
+__all__ = ["AudioToMelSpectrogramPreprocessor", "CropOrPadSpectrogramAugmentation", "JasperEncoder", "JasperDecoderForCTC",
+           "JasperDecoderForClassification", "GreedyCTCDecoder", "BeamSearchDecoderWithLM", "AudioDataLayer"]
 
 
 def _no_gpu():
@@ -99,6 +99,49 @@ class AudioToMelSpectrogramPreprocessor(NonTrainableNM):
         if self.pad_to > 0 and mel.shape[-1] % self.pad_to:
             mel = torch.nn.functional.pad(mel, (0, self.pad_to - mel.shape[-1] % self.pad_to), value=self._desc.get("pad_value", 0.0))
         return mel, seq
+
+
+def crop_or_pad_split(audio_length, image_len):
+    """(pad_left, pad_right) of CropOrPadSpectrogramAugmentation's pad branch (audio_preprocessing.py:700-707): the odd frame
+    goes on the right."""
+    d = int(audio_length) - int(image_len)
+    if d < 0:
+        raise ValueError(f"{image_len} frames are cropped to {audio_length}, not padded")
+    return d // 2, d - d // 2
+
+
+class CropOrPadSpectrogramAugmentation(NonTrainableNM):
+    """nemo/collections/asr/audio_preprocessing.py:666-738: pad or crop the spectrogram to ``audio_length`` frames.
+
+    A wider batch tensor is cut per row at an offset drawn with the reference's own call on the default CPU generator,
+    ``torch.randint(low=0, high=image_len - audio_length + 1, size=[num_images])`` -- after ``torch.manual_seed(s)`` this module
+    crops where the reference crops; any other tensor is centred between zero frames (``crop_or_pad_split``)."""
+
+    @property
+    def input_ports(self):
+        return {"input_signal": NeuralType(("B", "D", "T"), SpectrogramType()),
+                "length": NeuralType(tuple("B"), LengthsType())}
+
+    @property
+    def output_ports(self):
+        return {"processed_signal": NeuralType(("B", "D", "T"), SpectrogramType()),
+                "processed_length": NeuralType(tuple("B"), LengthsType())}
+
+    def __init__(self, audio_length, **kwargs):
+        super().__init__()
+        self.audio_length = audio_length
+
+    def draw_offsets(self, num_images, image_len):
+        """The reference's draw (:691); None when the tensor is not wider than audio_length (no draw happens there)."""
+        if image_len <= self.audio_length:
+            return None
+        return torch.randint(low=0, high=image_len - self.audio_length + 1, size=[num_images])
+
+    @torch.no_grad()
+    def forward(self, input_signal, length):
+        offsets = self.draw_offsets(input_signal.shape[0], input_signal.shape[-1])
+        image, out_len = stages.crop_or_pad(input_signal, self.audio_length, offsets)
+        return image, out_len.to(device=length.device, dtype=(length * 0 + self.audio_length).dtype)
 
 
 class _MaskedConvParams(nn.Module):
@@ -281,6 +324,43 @@ class JasperDecoderForCTC(_HipWeights, TrainableNM):
 
     def forward(self, encoder_output):
         return stages.decoder(self._get_handle(), encoder_output)
+
+
+class JasperDecoderForClassification(_HipWeights, TrainableNM):
+    """nemo/collections/asr/jasper.py:257-319: pooling over time, a Linear layer, optionally a softmax."""
+
+    @property
+    def input_ports(self):
+        return {"encoder_output": NeuralType(("B", "D", "T"), AcousticEncodedRepresentation())}
+
+    @property
+    def output_ports(self):
+        return {"logits": NeuralType(("B", "D"), LogitsType())}
+
+    def __init__(self, *, feat_in, num_classes, init_mode="xavier_uniform", return_logits=True, pooling_type='avg', **kwargs):
+        super().__init__()
+        self._feat_in = feat_in
+        self._return_logits = return_logits
+        self._num_classes = num_classes
+        if pooling_type not in ("avg", "max"):
+            raise ValueError('Pooling type chosen is not valid. Must be either `avg` or `max`')
+        self._pooling = 0 if pooling_type == "avg" else 1
+        self.decoder_layers = nn.Sequential(nn.Linear(self._feat_in, self._num_classes, bias=True))
+        self.apply(lambda m: _init_weights(m, mode=init_mode))
+        self._handle = None
+
+    def _get_handle(self):
+        if self._handle is None:
+            if not torch.cuda.is_available():
+                raise _no_gpu()
+            h = _lib.Handle(classifier=(self._feat_in, self._num_classes, self._pooling))
+            h.load_state_dict(self.state_dict())
+            h.finalize()
+            self._handle = h
+        return self._handle
+
+    def forward(self, encoder_output):
+        return stages.classifier(self._get_handle(), encoder_output, softmax=not self._return_logits)
 
 
 class GreedyCTCDecoder(TrainableNM):

@@ -118,6 +118,10 @@ class PredictionsType(ElementType):
     pass
 
 
+class LogitsType(ElementType):
+    pass
+
+
 class NeuralType:
     """axes ('B','D','T') + element type (neural_types/neural_type.py:34-187)."""
 

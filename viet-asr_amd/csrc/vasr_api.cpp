@@ -184,6 +184,11 @@ struct vasr_handle {
   // vasr_set_activation: the encoder's activation (kAct*) and residual_mode max (false: add)
   int act = kActRelu;
   bool res_max = false;
+  // vasr_set_classifier: JasperDecoderForClassification in place of a CTC head (classify.hip)
+  bool has_classifier = false;
+  int cls_feat_in = 0, cls_classes = 0, cls_pool = 0;
+  float* d_cls_w = nullptr;   // [cls_classes][cls_feat_in]
+  float* d_cls_b = nullptr;   // [cls_classes]
   std::vector<LenStep> steps;
   std::map<std::string, HostTensor> weights;
   std::vector<void*> dev_allocs;
@@ -814,6 +819,24 @@ int build_decoder(vasr_handle* h) {
   std::vector<float> sc(h->dec.m_pad, 1.f), sh(h->dec.m_pad, 0.f);
   for (int i = 0; i < h->num_classes; ++i) sh[i] = b->data[i];
   return upload_affine(h, sc, sh, &h->dec);
+}
+
+// vasr_finalize's check of the classification head (before anything touches the device): it reads what the encoder writes, and
+// both of its weights are there -- the Linear's [num_classes][feat_in] and [num_classes]
+int check_classifier(const vasr_handle* h) {
+  if (h->has_encoder && h->blocks.back().d.filters != h->cls_feat_in)
+    return fail(VASR_ERR_INVALID, "classifier feat_in %d, the encoder's last block has %d filters", h->cls_feat_in,
+                h->blocks.back().d.filters);
+  const HostTensor* t;
+  int rc;
+  if ((rc = need_shape(h, "decoder_layers.0.weight", {h->cls_classes, h->cls_feat_in}, &t))) return rc;
+  return need_shape(h, "decoder_layers.0.bias", {h->cls_classes}, &t);
+}
+
+int build_classifier(vasr_handle* h) {
+  int rc;
+  if ((rc = upload(h, find(h, "decoder_layers.0.weight")->data, &h->d_cls_w))) return rc;
+  return upload(h, find(h, "decoder_layers.0.bias")->data, &h->d_cls_b);
 }
 
 // ---------------- workspace plan ----------------
@@ -1461,6 +1484,22 @@ int vasr_set_activation(vasr_handle* h, int activation, int residual_mode) {
   return 0;
 }
 
+int vasr_set_classifier(vasr_handle* h, int feat_in, int num_classes, int pooling) {
+  if (!h) return fail(VASR_ERR_INVALID, "null handle");
+  if (h->finalized) return fail(VASR_ERR_STATE, "handle already finalized");
+  if (h->has_decoder) return fail(VASR_ERR_INVALID, "the handle has a CTC head (dec_feat_in %d): one head per handle", h->dec_feat_in);
+  if (pooling < 0 || pooling > 1) return fail(VASR_ERR_INVALID, "pooling %d (0 avg, 1 max)", pooling);
+  if (feat_in <= 0 || num_classes <= 0)
+    return fail(VASR_ERR_INVALID, "classifier needs feat_in > 0 and num_classes > 0 (got %d, %d)", feat_in, num_classes);
+  if (feat_in > kClassifyMaxChannels)
+    return fail(VASR_ERR_UNSUPPORTED, "classifier over %d channels (at most %d)", feat_in, kClassifyMaxChannels);
+  h->has_classifier = true;
+  h->cls_feat_in = feat_in;
+  h->cls_classes = num_classes;
+  h->cls_pool = pooling;
+  return 0;
+}
+
 int vasr_finalize(vasr_handle* h) {
   if (!h) return fail(VASR_ERR_INVALID, "null handle");
   if (h->finalized) return 0;
@@ -1472,9 +1511,11 @@ int vasr_finalize(vasr_handle* h) {
   if (h->has_encoder && (rc = check_groups(h))) return rc;
   if (h->has_encoder && (rc = check_se(h))) return rc;
   if (h->has_encoder && (rc = check_norm(h))) return rc;
+  if (h->has_classifier && (rc = check_classifier(h))) return rc;
   if (h->has_frontend && (rc = build_frontend(h))) return rc;
   if (h->has_encoder && (rc = build_encoder(h))) return rc;
   if (h->has_decoder && (rc = build_decoder(h))) return rc;
+  if (h->has_classifier && (rc = build_classifier(h))) return rc;
   HIP_TRY(hipDeviceSynchronize());
   {
     int dev = 0, n = 0;
@@ -1697,6 +1738,111 @@ int vasr_transcribe_greedy_pcm16(vasr_handle* h, const int16_t* d_pcm, const int
                                  int64_t* d_pred, int32_t* d_ids, int32_t* d_id_len, float* d_logp, float* d_enc_len,
                                  void* d_ws, size_t ws_bytes, vasr_stream stream) {
   return transcribe_any(h, d_pcm, true, d_len, batch, samples, d_pred, d_ids, d_id_len, d_logp, d_enc_len, d_ws, ws_bytes, stream);
+}
+
+// ---- classification path (classify.hip) ----
+int vasr_crop_or_pad_f32(const float* d_in, int batch, int feat, int64_t frames, int64_t audio_length, const int64_t* d_offsets,
+                         float* d_out, int64_t* d_out_len, vasr_stream stream) {
+  if (!d_in || !d_out || batch <= 0 || feat <= 0 || frames <= 0 || audio_length <= 0 || frames > INT32_MAX ||
+      audio_length > INT32_MAX)
+    return fail(VASR_ERR_INVALID, "bad argument");
+  if (frames > audio_length && !d_offsets)
+    return fail(VASR_ERR_INVALID, "%lld frames are cropped to %lld: offsets needed", (long long)frames, (long long)audio_length);
+  const int e = launch_crop_or_pad(d_in, frames, batch, feat, (int)frames, nullptr, 0, (int)audio_length, d_offsets, d_out,
+                                   audio_length, (int)audio_length, d_out_len, static_cast<hipStream_t>(stream));
+  if (e) return fail(VASR_ERR_HIP, "crop_or_pad: %s", hipGetErrorString((hipError_t)e));
+  return 0;
+}
+
+// pool + linear (+ softmax) over x [B][cls_feat_in][ld]; pooled: [B][cls_feat_in] scratch
+static int run_classifier(vasr_handle* h, const float* x, int64_t ld, int64_t frames, int batch, int softmax, float* pooled,
+                          float* d_out, hipStream_t st) {
+  ProfScope ps(h, kProfHead, st);
+  const ClassifyLaunch a{x, ld, batch, h->cls_feat_in, (int)frames, h->cls_classes, h->cls_pool, softmax ? 1 : 0,
+                         h->d_cls_w, h->d_cls_b, pooled, d_out};
+  const int e = launch_classifier(a, st);
+  if (e) return fail(VASR_ERR_HIP, "classifier: %s", hipGetErrorString((hipError_t)e));
+  return 0;
+}
+
+int vasr_classifier_f32(vasr_handle* h, const float* d_enc, int batch, int64_t enc_frames_, int softmax, float* d_out,
+                        void* d_ws, size_t ws_bytes, vasr_stream stream) {
+  if (!h || !h->has_classifier || !h->finalized) return fail(VASR_ERR_STATE, "no finalized classifier in this handle");
+  if (batch <= 0 || enc_frames_ <= 0 || enc_frames_ > INT32_MAX || !d_enc || !d_out || !d_ws)
+    return fail(VASR_ERR_INVALID, "bad argument");
+  const size_t need_bytes = (size_t)batch * h->cls_feat_in * 4;
+  if (ws_bytes < need_bytes) return fail(VASR_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, need_bytes);
+  return run_classifier(h, d_enc, enc_frames_, enc_frames_, batch, softmax, static_cast<float*>(d_ws), d_out,
+                        static_cast<hipStream_t>(stream));
+}
+
+// vasr_classify_f32's workspace: the encoder's plan over audio_length frames, then the uncropped mel [B][n_mels][pad(T)], its
+// lengths [B] i64, the encoder's float lengths [B] and the pooled vectors [B][feat_in]
+namespace {
+struct ClsPlan { WsPlan enc; size_t mel_raw, seq_raw, enc_len, pooled, total; int64_t T, Tp; };
+ClsPlan plan_classify(const vasr_handle* h, int batch, int64_t samples, int64_t audio_length) {
+  ClsPlan c{};
+  c.enc = plan_ws(h, batch, audio_length);
+  c.T = vasr_mel_frames(h, samples);
+  c.Tp = pad_frames(c.T);
+  size_t o = align_up(c.enc.total, 256);
+  auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
+  c.mel_raw = take((size_t)batch * h->fe.n_mels * c.Tp * 4);
+  c.seq_raw = take((size_t)batch * 8);
+  c.enc_len = take((size_t)batch * 4);
+  c.pooled = take((size_t)batch * h->cls_feat_in * 4);
+  c.total = o;
+  return c;
+}
+}  // namespace
+
+size_t vasr_classify_workspace_bytes(const vasr_handle* h, int batch, int64_t samples, int64_t audio_length) {
+  if (!h || !h->finalized || !h->has_frontend || !h->has_encoder || !h->has_classifier || batch <= 0 || samples <= 0 ||
+      audio_length <= 0)
+    return 0;
+  return plan_classify(h, batch, samples, audio_length).total;
+}
+
+int vasr_classify_f32(vasr_handle* h, const float* d_wav, const int64_t* d_len, int batch, int64_t samples, int64_t audio_length,
+                      const int64_t* d_offsets, int softmax, float* d_out, float* d_mel, void* d_ws, size_t ws_bytes,
+                      vasr_stream stream) {
+  if (!h || !h->finalized || !h->has_frontend || !h->has_encoder || !h->has_classifier)
+    return fail(VASR_ERR_STATE, "handle needs a finalized front end, encoder and classifier");
+  if (batch <= 0 || !d_wav || !d_len || !d_out || !d_ws || audio_length <= 0 || audio_length > INT32_MAX)
+    return fail(VASR_ERR_INVALID, "bad argument");
+  if (samples <= h->fe.n_fft / 2)
+    return fail(VASR_ERR_INVALID, "reflect padding needs more than n_fft/2 = %d samples (got %lld)",
+                h->fe.n_fft / 2, (long long)samples);
+  if (h->feat_in != h->fe.n_mels) return fail(VASR_ERR_INVALID, "encoder feat_in %d, front end n_mels %d", h->feat_in, h->fe.n_mels);
+  const ClsPlan c = plan_classify(h, batch, samples, audio_length);
+  if (c.T > audio_length && !d_offsets)
+    return fail(VASR_ERR_INVALID, "%lld mel frames are cropped to %lld: offsets needed", (long long)c.T, (long long)audio_length);
+  if (ws_bytes < c.total) return fail(VASR_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, c.total);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* ws = static_cast<char*>(d_ws);
+  const WsPlan& p = c.enc;
+  float* mel_raw = reinterpret_cast<float*>(ws + c.mel_raw);
+  int64_t* seq_raw = reinterpret_cast<int64_t*>(ws + c.seq_raw);
+  int64_t* seq = reinterpret_cast<int64_t*>(ws + p.seq);
+  float* melp = reinterpret_cast<float*>(ws + p.melp);
+  float* encp = reinterpret_cast<float*>(ws + p.encp);
+  {
+    ProfScope ps(h, kProfFrontend, st);
+    launch_seq_len(d_len, batch, h->fe.hop_length, seq_raw, st);
+    launch_stft_logmel(h->ft, d_wav, false, batch, samples, h->row_independent ? d_len : nullptr, h->fe.hop_length,
+                       h->fe.preemph, h->fe.log_guard, mel_raw, c.Tp, (int)c.T, st);
+    launch_normalize(mel_raw, c.Tp, seq_raw, batch, h->fe.n_mels, (int)c.T, h->fe.normalize == 1, st);
+    if (h->fe.normalize == 2) launch_normalize_all(mel_raw, c.Tp, seq_raw, batch, h->fe.n_mels, (int)c.T, st);
+    // cut or centred straight into the encoder's padded-pitch input; every row is audio_length frames long from here on
+    const int e = launch_crop_or_pad(mel_raw, c.Tp, batch, h->fe.n_mels, (int)c.T, h->row_independent ? d_len : nullptr,
+                                     h->fe.hop_length, (int)audio_length, d_offsets, melp, p.Tp0, (int)p.Tp0, seq, st);
+    if (e) return fail(VASR_ERR_HIP, "crop_or_pad: %s", hipGetErrorString((hipError_t)e));
+    if (d_mel) launch_repad(melp, p.Tp0, batch * h->fe.n_mels, (int)audio_length, d_mel, audio_length, st);
+  }
+  int rc = run_encoder(h, melp, p.Tp0, audio_length, seq, batch, encp, p.Tp1, reinterpret_cast<float*>(ws + c.enc_len), ws, p, st);
+  if (rc) return rc;
+  if ((rc = run_classifier(h, encp, p.Tp1, p.T1, batch, softmax, reinterpret_cast<float*>(ws + c.pooled), d_out, st))) return rc;
+  return check_launch("classify");
 }
 
 int vasr_pcm16_to_f32(const int16_t* d_pcm, int64_t n, float* d_out, vasr_stream stream) {

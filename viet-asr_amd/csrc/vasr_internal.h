@@ -313,6 +313,25 @@ struct NormLaunch {
 bool norm_supported(int channels, int groups);   // groups divides channels
 int launch_norm(const NormLaunch& a, hipStream_t st);   // 0 or a hipError_t
 
+// ---- classification path (classify.hip) ----
+// CropOrPadSpectrogramAugmentation: in [B][feat][ld_in] with `frames` valid columns -> out [B][feat][ld_out]; a row wider than
+// audio_length is cut at off[b] (clamped into the row; nullptr: 0), any other row is centred between zero frames, the odd
+// one on the right.  Columns [audio_length, store_cols) are stored as 0; out_len (optional) [B] = audio_length.  wav_len
+// (optional, with hop): row b is 1 + wav_len[b] / hop columns wide (at most frames) -- the row-independent mode.
+int launch_crop_or_pad(const float* in, int64_t ld_in, int batch, int feat, int frames, const int64_t* wav_len, int hop,
+                       int audio_length, const int64_t* off, float* out, int64_t ld_out, int store_cols, int64_t* out_len,
+                       hipStream_t st);   // 0 or a hipError_t
+// JasperDecoderForClassification: x [B][channels][ld] pooled over columns < frames (mean, or pool_max: maximum) into pooled
+// [B][channels] (workspace), out [B][classes] = bias + w pooled (w [classes][channels]), softmax != 0: softmax over the classes
+constexpr int kClassifyMaxChannels = 1024;
+struct ClassifyLaunch {
+  const float* x; int64_t ld;
+  int batch, channels, frames, classes, pool_max, softmax;
+  const float* w; const float* bias;
+  float* pooled; float* out;
+};
+int launch_classifier(const ClassifyLaunch& a, hipStream_t st);   // 0 or a hipError_t
+
 // ---- CTC head / decode (decode.hip) ----
 // logits [B][ldm rows][ld] (row v, column t) -> logp [B][T][V] (optional), pred [B][T] (optional)
 void launch_logsoftmax_argmax(const float* logits, int64_t row_ld, int64_t batch_stride, int batch, int frames,

@@ -413,6 +413,110 @@ class QuartzNetCTC:
         return slot.launch(signals, row_independent)
 
 
+class QuartzNetClassifier:
+    """The fused wav -> class fast path of the speech-command / keyword models (one C-ABI call per batch,
+    vasr_classify_f32): AudioToMelSpectrogramPreprocessor -> CropOrPadSpectrogramAugmentation(audio_length) -> JasperEncoder ->
+    JasperDecoderForClassification.  Lives beside QuartzNetCTC; the per-module classes in asr.py run the same kernels."""
+
+    def __init__(self, model_definition, encoder_state, decoder_state, audio_length, labels=None, pooling_type="avg",
+                 device="cuda:0", gemm=None):
+        """decoder_state: JasperDecoderForClassification's state_dict (decoder_layers.0.weight [num_classes][feat_in], .bias);
+        labels: class names for classify() (None: it returns indices); gemm: as QuartzNetCTC's."""
+        _require_gpu()
+        if pooling_type not in ("avg", "max"):
+            raise ValueError('Pooling type chosen is not valid. Must be either `avg` or `max`')
+        self.device = torch.device(device)
+        self.audio_length = int(audio_length)
+        if self.audio_length <= 0:
+            raise ValueError(f"audio_length must be positive, got {audio_length!r}")
+        self.labels = list(labels) if labels is not None else None
+        pre = dict(model_definition["AudioToMelSpectrogramPreprocessor"])
+        enc_cfg = model_definition["JasperEncoder"]
+        jas = enc_cfg["jasper"]
+        act, res_mode = activation_from_config(enc_cfg)
+        if not enc_cfg.get("conv_mask", True):
+            raise NotImplementedError("only conv_mask=True is implemented")
+        norm = norm_from_config(enc_cfg, jas)
+        if res_mode and any(norm):
+            raise NotImplementedError("residual_mode='max' with group, instance or layer normalization is not implemented")
+        self.frontend = frontend_description(pre)
+        w = np.asarray(decoder_state["decoder_layers.0.weight"].detach().cpu().numpy()
+                       if hasattr(decoder_state["decoder_layers.0.weight"], "detach") else decoder_state["decoder_layers.0.weight"])
+        self.num_classes = int(w.shape[0])
+        if self.labels is not None and len(self.labels) != self.num_classes:
+            raise ValueError(f"{len(self.labels)} labels for {self.num_classes} classes")
+        with torch.cuda.device(self.device):
+            self.handle = _lib.Handle(frontend=self.frontend, feat_in=pre.get("features", 64), blocks=blocks_from_config(jas),
+                                      se=se_from_config(jas), groups=groups_from_config(jas), norm=norm, activation=act,
+                                      residual_mode=res_mode,
+                                      classifier=(jas[-1]["filters"], self.num_classes, 0 if pooling_type == "avg" else 1))
+            self.handle.load_state_dict(encoder_state)
+            self.handle.load_state_dict(decoder_state)
+            self.handle.finalize()
+            if gemm is not None:
+                self.handle.set_gemm_mode(gemm)
+        self._ws = None
+        self._row_independent = False
+
+    def forward(self, wav, length, offsets=None, softmax=False, row_independent=False, want_mel=False):
+        """wav [B, L] f32 cuda (rows zero padded), length [B] i64 cuda -> logits [B, num_classes] f32, or probabilities
+        (softmax=True: F.softmax(logits, -1)).  Enqueued on the current stream; nothing synchronises.
+
+        offsets [B] i64: where each row is cut when the batch is wider than audio_length frames; None draws them as the
+        reference does, torch.randint(0, T - audio_length + 1, [B]) on the default CPU generator (reproducible under
+        torch.manual_seed); an explicit array makes the crop reproducible without the generator.  row_independent: as
+        QuartzNetCTC.forward -- every row is reflected, cut (its offset clamped into its own width) or centred as a batch-1
+        call on it alone would be, and its output is that call's, bit for bit; every length must then exceed n_fft / 2.
+        want_mel: return (out, mel [B, n_mels, audio_length]), the encoder's input."""
+        if wav.device.type != "cuda" or wav.dtype != torch.float32 or not wav.is_contiguous():
+            raise ValueError("wav must be a contiguous float32 cuda tensor")
+        if length.dtype != torch.int64 or length.device != wav.device:
+            raise ValueError("length must be an int64 tensor on the same device")
+        B, L = wav.shape
+        T = self.handle.mel_frames(L)
+        if offsets is None and T > self.audio_length:
+            offsets = torch.randint(low=0, high=T - self.audio_length + 1, size=[B])
+        off = None
+        if offsets is not None:
+            off = torch.as_tensor(offsets).to(device=wav.device, dtype=torch.int64).contiguous()
+            if off.shape != (B,):
+                raise ValueError(f"offsets must have shape ({B},), got {tuple(off.shape)}")
+        need = int(_lib.lib().vasr_classify_workspace_bytes(self.handle.h, B, L, self.audio_length))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if bool(row_independent) != self._row_independent:
+            self.handle.set_row_independent(row_independent)
+            self._row_independent = bool(row_independent)
+        out = torch.empty((B, self.num_classes), dtype=torch.float32, device=wav.device)
+        mel = torch.empty((B, self.frontend["n_mels"], self.audio_length), dtype=torch.float32, device=wav.device) if want_mel else None
+        _lib.check(_lib.lib().vasr_classify_f32(
+            self.handle.h, wav.data_ptr(), length.data_ptr(), B, L, self.audio_length, off.data_ptr() if off is not None else None,
+            int(bool(softmax)), out.data_ptr(), mel.data_ptr() if mel is not None else None, self._ws.data_ptr(),
+            self._ws.numel(), _stream_ptr()))
+        return (out, mel) if want_mel else out
+
+    def classify(self, signals, offsets=None, row_independent=False):
+        """List of 1-D arrays (model sample rate; float, or integer PCM) -> the arg-max class index per signal, or its label
+        where ``labels`` was given; zero-pad-to-max collate (parts/dataset.py:14-53).  Short inputs follow QuartzNetCTC's
+        rules: no empty batch or signal, and more than n_fft / 2 samples per signal with row_independent."""
+        if len(signals) == 0:
+            raise ValueError("empty batch")
+        lens = [len(s) for s in signals]
+        if min(lens) == 0:
+            raise ValueError("empty signal in batch")
+        if row_independent and min(lens) <= self.frontend["n_fft"] // 2:
+            raise ValueError(f"row-independent batching needs more than n_fft/2 = {self.frontend['n_fft'] // 2} samples "
+                             f"per signal (got {min(lens)}): an unbatched call refuses such input too")
+        batch = np.zeros((len(signals), max(lens)), dtype=np.float32)
+        for i, s in enumerate(signals):
+            batch[i, : lens[i]] = _pcm_to_float(np.asarray(s))
+        out = self.forward(torch.from_numpy(batch).to(self.device), torch.tensor(lens, device=self.device), offsets=offsets,
+                           row_independent=row_independent)
+        idx = out.argmax(-1).cpu().tolist()
+        return [self.labels[i] for i in idx] if self.labels is not None else idx
+
+
 class PendingBatch:
     """Result handle of QuartzNetCTC.launch()."""
 

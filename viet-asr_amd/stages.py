@@ -83,6 +83,37 @@ def decoder(handle, encoder_output):
     return logp
 
 
+def crop_or_pad(input_signal, audio_length, offsets=None):
+    """CropOrPadSpectrogramAugmentation.forward -> (processed_signal [B,D,audio_length] f32, processed_length [B] i64).
+    offsets [B] i64 (any device): where each row is cut when it is wider than audio_length."""
+    _need_cuda(input_signal)
+    x = input_signal.to(torch.float32).contiguous()
+    B, D, T = x.shape
+    A = int(audio_length)
+    if T > A and offsets is None:
+        raise ValueError(f"{T} frames are cropped to {A}: offsets needed")
+    off = None if offsets is None else torch.as_tensor(offsets).to(device=x.device, dtype=torch.int64).contiguous()
+    if off is not None and off.shape != (B,):
+        raise ValueError(f"offsets must have shape ({B},), got {tuple(off.shape)}")
+    out = torch.empty((B, D, A), dtype=torch.float32, device=x.device)
+    out_len = torch.empty((B,), dtype=torch.int64, device=x.device)
+    _lib.check(_lib.lib().vasr_crop_or_pad_f32(x.data_ptr(), B, D, T, A, off.data_ptr() if off is not None else None,
+                                               out.data_ptr(), out_len.data_ptr(), _st()))
+    return out, out_len
+
+
+def classifier(handle, encoder_output, softmax=False):
+    """JasperDecoderForClassification.forward -> logits (or probabilities) [B,num_classes] f32."""
+    _need_cuda(encoder_output)
+    x = encoder_output.to(torch.float32).contiguous()
+    B, C, T1 = x.shape
+    ws = _workspace(x.device, B * C * 4)
+    out = torch.empty((B, handle.num_classes), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().vasr_classifier_f32(handle.h, x.data_ptr(), B, T1, int(bool(softmax)), out.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), _st()))
+    return out
+
+
 def greedy_argmax(log_probs):
     """GreedyCTCDecoder.forward -> predictions [B,T'] i64."""
     _need_cuda(log_probs)

@@ -147,6 +147,14 @@ def decoder_state_dict(feat_in, num_classes_with_blank, seed=0):
     return sd
 
 
+def classifier_state_dict(feat_in, num_classes, seed=0):
+    """JasperDecoderForClassification's nn.Linear (jasper.py:306): decoder_layers.0.weight [num_classes][feat_in] (2-D) and
+    decoder_layers.0.bias.  Gain 2 on the pooled activations: class margins far above fp32 round-off."""
+    w = _conv_weight("decoder_layers.0.weight", seed, num_classes, feat_in, 1, gain=2.0)
+    return {"decoder_layers.0.weight": np.ascontiguousarray(w.reshape(num_classes, feat_in)),
+            "decoder_layers.0.bias": _rs("decoder_layers.0.bias", seed).normal(0, 0.5, size=num_classes).astype(np.float32)}
+
+
 def band_limit(x, band_hz, rate=16000, taps=255, beta=8.6):
     """Rows of ``x`` low-passed at ``band_hz`` by a Kaiser-windowed sinc (about -85 dB in the stop band), float64
     accumulation in a fixed order (no FFT: the result must be the same bits wherever the fixtures are replayed).
