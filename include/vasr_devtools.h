@@ -25,6 +25,15 @@ VASR_API int vasr_fused_tile_choice(int64_t tiles128, int compute_units);
  * Buffers are caller provided [B][C][Tp] with Tp = vasr_padded_frames(T). */
 VASR_API int vasr_bench_depthwise(const float* d_x, const float* d_w, const int32_t* d_lens, int batch, int channels,
                          int64_t frames, int kernel, float* d_y, vasr_stream stream);
+/* One depthwise layer through the packed-FMA / generic kernels' own launcher (encoder_dw.hip launch_depthwise) with its full
+ * argument list: any kernel / stride / dilation (not both > 1: VASR_ERR_INVALID, as the reference's get_same_padding refuses it),
+ * pad = "same" padding of jasper.py:60-65.  x [B][C][vasr_padded_frames(frames_in)], y [B][C][vasr_padded_frames(t_out)] with
+ * t_out = (frames_in + 2 pad - dilation (kernel - 1) - 1) / stride + 1; the caller supplies both length vectors (input mask,
+ * output zeroed from d_lens_out[b] to the row pitch).  d_amax: NULL, or [batch][amax_stride] u32 receiving the per-wavefront
+ * maxima of |y| (amax_stride >= channels * ceil(padded t_out / 256) * 4, else VASR_ERR_INVALID; unused slots are zeroed). */
+VASR_API int vasr_bench_depthwise_layer(const float* d_x, const float* d_w, const int32_t* d_lens_in, const int32_t* d_lens_out,
+                               int batch, int channels, int64_t frames_in, int kernel, int stride, int dilation, float* d_y,
+                               uint32_t* d_amax, int amax_stride, vasr_stream stream);
 /* Depthwise convolution on the matrix pipe (Toeplitz form, fp16-split arithmetic; stride 1, the (kernel, dilation) pairs
  * of the shipped models): vasr_depthwise_mfma_table_size = dwords per channel of the tap table (0 = shape not covered),
  * vasr_pack_depthwise_taps fills [channels][size] tables and [channels] inverse scales on the host; the bench call runs

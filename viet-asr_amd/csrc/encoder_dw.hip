@@ -555,7 +555,8 @@ static int launch_depthwise_impl(const float* x, int64_t ldx, int frames_in, con
                                  int pad, float* y, int64_t ldy, hipStream_t st, AmaxTab* amax) {
   const bool aligned = channels % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 &&
                        (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
-  const bool pair = dev_switches().dw_pair;   // devtools build: VASR_DW_PAIR=0 sends every shape to the generic kernel
+  // devtools build: VASR_DW_PAIR=0 takes the one-row kernel (dw_conv_kernel) for the tiled widths instead of the pair kernel
+  const bool pair = dev_switches().dw_pair;
   if (pair && aligned && stride == 1) {
     if (dilation == 2 && kernel == 87 && pad == 86)
       { launch_dw_pair<87, 2>(x, ldx, w, lens_in, lens_out, batch, channels, y, ldy, st, amax); return 0; }

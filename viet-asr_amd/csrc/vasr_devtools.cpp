@@ -79,6 +79,28 @@ int vasr_bench_depthwise(const float* d_x, const float* d_w, const int32_t* d_le
   return check_launch("bench_depthwise");
 }
 
+int vasr_bench_depthwise_layer(const float* d_x, const float* d_w, const int32_t* d_lens_in, const int32_t* d_lens_out, int batch,
+                               int channels, int64_t frames_in, int kernel, int stride, int dilation, float* d_y,
+                               uint32_t* d_amax, int amax_stride, vasr_stream stream) {
+  if (!d_x || !d_w || !d_lens_in || !d_lens_out || !d_y || batch < 1 || channels < 1 || frames_in < 1 ||
+      frames_in > 0x7fffff00 || kernel < 1 || stride < 1 || dilation < 1)
+    return fail(VASR_ERR_INVALID, "bad argument");
+  if (stride > 1 && dilation > 1) return fail(VASR_ERR_INVALID, "only stride OR dilation may be greater than 1");
+  const int pad = dilation > 1 ? (dilation * kernel) / 2 - 1 : kernel / 2;   // get_same_padding (jasper.py:60-65)
+  const int64_t span = frames_in + 2 * pad - (int64_t)dilation * (kernel - 1) - 1;
+  if (span < 0) return fail(VASR_ERR_INVALID, "no output frame");
+  const int64_t ldx = pad_frames(frames_in), ldy = pad_frames(span / stride + 1);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  AmaxTab ay{d_amax, amax_stride, 0};
+  if (launch_depthwise(d_x, ldx, (int)frames_in, d_w, d_lens_in, d_lens_out, batch, channels, kernel, stride, dilation, pad,
+                       d_y, ldy, st, d_amax ? &ay : nullptr))
+    return fail(VASR_ERR_INVALID, "maxima table too small");
+  // slots past the ones the launch used read as zero for the caller
+  if (d_amax && ay.n < amax_stride)
+    HIP_TRY(hipMemset2DAsync(d_amax + ay.n, (size_t)amax_stride * 4, 0, (size_t)(amax_stride - ay.n) * 4, batch, st));
+  return check_launch("bench_depthwise_layer");
+}
+
 int vasr_depthwise_mfma_table_size(int kernel, int dilation) { return depthwise_mfma_table_size(kernel, dilation); }
 
 int vasr_pack_depthwise_taps(const float* h_w, int channels, int kernel, int dilation, uint32_t* h_table, float* h_inv) {
