@@ -247,6 +247,28 @@ VASR_API int vasr_greedy_argmax(const float* d_logp, int batch, int64_t frames, 
 VASR_API int vasr_ctc_collapse(const int64_t* d_pred, int batch, int64_t frames, int blank_id, int32_t* d_ids,
                       int32_t* d_id_len, vasr_stream stream);
 
+/* word_error_rate (nemo/collections/asr/metrics.py:30-63), both use_cer settings, per row, on device ids.
+ *   d_hyp [B][hyp_width] i32, d_hyp_len [B] i32 (d_ids / d_id_len of the calls below and of the beam search),
+ *   d_ref [B][ref_width] i32, d_ref_len [B] i32 (the data layer's transcripts / transcript_length)
+ *   -> d_counts [B][4] i32 = {word_edits, ref_words, char_edits, ref_chars}, 16-byte aligned (one vector store per row).
+ * Characters: the Levenshtein distance (unit costs, metrics.py:7-27) between the two id rows over their own lengths,
+ * whitespace ids included -- list(h) against list(r); ref_chars = the reference's length.  Words: the same distance between the
+ * rows' words -- h.split() against r.split(): a word is a maximal run of ids that are not among h_space_ids (host, n_space ids,
+ * 0..8: every label for which str.isspace() holds), so leading, trailing and repeated whitespace make no empty words, a row
+ * of whitespace has none, and with n_space = 0 a non-empty row is one word.  Two words are equal iff their id runs are equal:
+ * a 64-bit fold (vasr_beam_hash_step) only prefilters, equal folds are confirmed id by id.  Integer arithmetic throughout.
+ * A row's counts depend on that row alone -- not on the batch, the other rows or the ids behind its lengths, which are never
+ * read.  Lengths are clamped into [0, width]; a NEGATIVE length on either side (the beam search's id_len = -1 overflow
+ * report) gives {-1, -1, -1, -1} for that row, never a plausible number.  A width of 0 is legal (the distance to an empty side
+ * is the other side's length); widths above 4096 return VASR_ERR_UNSUPPORTED before anything is launched; NULL pointers,
+ * batch <= 0, a width < 0, n_space outside 0..8 and a misaligned d_counts return VASR_ERR_INVALID before a device is touched.
+ * No handle, no workspace: one workgroup per row, everything in LDS (133 KB at 4096 x 4096, where ONE row takes about
+ * 10.0 ms -- the rows of a batch run side by side; DESIGN section 7c has the measured times).  (ABI 8) */
+VASR_API int vasr_error_counts_i32(const int32_t* d_hyp, int64_t hyp_width, const int32_t* d_hyp_len,
+                                   const int32_t* d_ref, int64_t ref_width, const int32_t* d_ref_len, int batch,
+                                   const int32_t* h_space_ids, int n_space,   /* host, 0..8 ids */
+                                   int32_t* d_counts /* [B][4] */, vasr_stream stream);
+
 /* ---- the whole path in one call (the fast path bench.py times) ------------------------ */
 /* wav -> mel -> encoder -> CTC head -> log-softmax/argmax -> collapse, all intermediates in
  * the workspace (padded time stride, no port tensors materialised).

@@ -1622,6 +1622,28 @@ int vasr_ctc_collapse(const int64_t* d_pred, int batch, int64_t frames, int blan
   return check_launch("ctc_collapse");
 }
 
+int vasr_error_counts_i32(const int32_t* d_hyp, int64_t hyp_width, const int32_t* d_hyp_len, const int32_t* d_ref,
+                          int64_t ref_width, const int32_t* d_ref_len, int batch, const int32_t* h_space_ids, int n_space,
+                          int32_t* d_counts, vasr_stream stream) {
+  // every refusal comes before a device is touched
+  if (!d_hyp || !d_hyp_len || !d_ref || !d_ref_len || !d_counts) return fail(VASR_ERR_INVALID, "error_counts: NULL pointer");
+  if (batch <= 0 || hyp_width < 0 || ref_width < 0)
+    return fail(VASR_ERR_INVALID, "error_counts: batch %d, widths %lld / %lld", batch, (long long)hyp_width, (long long)ref_width);
+  if (n_space < 0 || n_space > kMetricsMaxSpace || (n_space > 0 && !h_space_ids))
+    return fail(VASR_ERR_INVALID, "error_counts: n_space %d outside 0..%d (or no ids given)", n_space, kMetricsMaxSpace);
+  if (reinterpret_cast<uintptr_t>(d_counts) & 15) return fail(VASR_ERR_INVALID, "error_counts: d_counts is not 16-byte aligned");
+  if (hyp_width > kMetricsMaxWidth || ref_width > kMetricsMaxWidth)
+    return fail(VASR_ERR_UNSUPPORTED, "error_counts: rows of %lld / %lld ids, at most %d per side", (long long)hyp_width,
+                (long long)ref_width, kMetricsMaxWidth);
+  SpaceIds sp{};
+  sp.n = n_space;
+  for (int k = 0; k < n_space; ++k) sp.id[k] = h_space_ids[k];
+  const int rc = launch_error_counts(d_hyp, (int)hyp_width, d_hyp_len, d_ref, (int)ref_width, d_ref_len, batch, sp, d_counts,
+                                     static_cast<hipStream_t>(stream));
+  if (rc) return fail(VASR_ERR_HIP, "error_counts: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
+  return check_launch("error_counts");
+}
+
 // One contiguous slice of the batch through the whole path on one stream.
 static int transcribe_part(vasr_handle* h, const void* d_wav, bool pcm16, const int64_t* d_len, int batch, int64_t samples,
                            int64_t* d_pred, int32_t* d_ids, int32_t* d_id_len, float* d_logp, float* d_enc_len,

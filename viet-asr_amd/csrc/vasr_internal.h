@@ -343,6 +343,15 @@ void launch_ctc_collapse(const int64_t* pred, int batch, int64_t frames, int bla
                          int32_t* id_len, hipStream_t st, const int64_t* wav_len = nullptr, int hop = 0,
                          const LenStep* steps = nullptr, int n_steps = 0);
 
+// ---- evaluation metrics (metrics.hip) ----
+// per row {word_edits, ref_words, char_edits, ref_chars} of hyp [B][hyp_width] / ref [B][ref_width] over their own lengths;
+// widths 0 .. kMetricsMaxWidth (the caller checks); counts [B][4], 16-byte aligned; returns 0 or a hipError_t
+constexpr int kMetricsMaxWidth = 4096;
+constexpr int kMetricsMaxSpace = 8;
+struct SpaceIds { int32_t id[kMetricsMaxSpace]; int n; };   // the label ids str.split() separates on
+int launch_error_counts(const int32_t* hyp, int hyp_width, const int32_t* hyp_len, const int32_t* ref, int ref_width,
+                        const int32_t* ref_len, int batch, const SpaceIds& sp, int32_t* counts, hipStream_t st);
+
 // ---- audio ingest (audio.hip) ----
 void launch_pcm16_to_f32(const short* in, int64_t n, float* out, hipStream_t st);
 void launch_resample(const float* x, int64_t ld_in, const int64_t* len_in, int batch, const float* table, int nwin,

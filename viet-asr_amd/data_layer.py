@@ -132,7 +132,9 @@ class _BatchIter:
 
 
 def word_error_rate(hypotheses, references, use_cer=False):
-    """nemo/collections/asr/metrics.py:30-63: summed Levenshtein distance / summed reference length."""
+    """nemo/collections/asr/metrics.py:30-63: summed Levenshtein distance / summed reference length, on host strings.
+    ``metrics.ErrorRate`` (``VietASR.evaluate_manifest``) computes the same two rates on the device from the parsed token
+    ids; on raw manifest text this one differs from it only where a reference contains characters outside the labels."""
     def lev(a, b):
         prev = list(range(len(b) + 1))
         for i, x in enumerate(a, 1):

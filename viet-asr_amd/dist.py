@@ -184,3 +184,19 @@ def transcribe_sharded(engine, signals, group=None, balance=True, batch_size=Non
     for t, i in zip(texts, idx_t.tolist()):
         out[i] = t
     return out
+
+
+def all_reduce_counts(counts, group=None):
+    """Sum an integer count vector (``metrics.ErrorRate``'s int64 [4] sums + its flag) over the process group: one
+    all-reduce of a few integers instead of a gather of texts.  The identity when no process group is initialised.  The
+    tensor is reduced where the backend wants it (RCCL: this rank's current device, gloo: the host) and returned there."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return counts
+    out = counts.clone()
+    backend = dist.get_backend(group)
+    if backend == "nccl" and out.device.type != "cuda":
+        out = out.cuda()
+    elif backend == "gloo" and out.device.type != "cpu":
+        out = out.cpu()
+    dist.all_reduce(out, op=dist.ReduceOp.SUM, group=group)
+    return out

@@ -395,13 +395,17 @@ class QuartzNetCTC:
         return lf
 
     # -- pipelined host path: pinned staging, copies on their own stream, two batches in flight
-    def launch(self, signals, row_independent=False):
+    def launch(self, signals, row_independent=False, after_forward=None):
         """Enqueue one batch and return at once; ``.texts()`` of the returned PendingBatch waits for it.
 
         Two staging slots alternate: while batch k computes, batch k+1 is collated into pinned memory and its
         host->device copy runs on a separate stream (``torch.from_numpy(x).to(device)`` from pageable memory costs
         more than the whole forward pass of a 64 x 10 s batch).  int16 PCM signals cross PCIe as int16 and are scaled
         by 2^-15 on the device (segment.py:61-74) -- half the bytes, same floats.
+
+        after_forward(out): called with ``forward``'s result dict on the compute stream, right after the forward pass is
+        enqueued and before its results are copied out -- device-side consumers of the ids (``metrics.ErrorRate.update``)
+        hook in here; it must not synchronise.
         """
         if len(signals) == 0:
             raise ValueError("empty batch")
@@ -410,7 +414,7 @@ class QuartzNetCTC:
             self._copy_stream = torch.cuda.Stream(self.device)
         slot = self._slots[self._launched % 2]
         self._launched += 1
-        return slot.launch(signals, row_independent)
+        return slot.launch(signals, row_independent, after_forward)
 
 
 class QuartzNetClassifier:
@@ -566,7 +570,7 @@ class _Slot:
         if self.pin_ids is None or self.pin_ids.numel() < B * t1:
             self.pin_ids = torch.empty(B * t1, dtype=torch.int32, pin_memory=True)
 
-    def launch(self, signals, row_independent=False):
+    def launch(self, signals, row_independent=False, after_forward=None):
         eng = self.eng
         if self.pending is not None:
             self.pending.texts()          # the slot's previous batch: fetch before its buffers are overwritten
@@ -604,6 +608,8 @@ class _Slot:
             wav = self.dev[:nbytes].view(dtype).view(B, L)
             # (int16 PCM goes into the front end as it is: scaled by 2^-15 in the STFT kernel's staging load)
             self.out = eng.forward(wav, self.dev_len[:B], want_pred=False, row_independent=row_independent)
+            if after_forward is not None:
+                after_forward(self.out)
             self.pin_ids[: B * t1].copy_(self.out["ids"].view(-1), non_blocking=True)
             self.pin_idlen[:B].copy_(self.out["id_len"], non_blocking=True)
             self.ev_out.record(comp)

@@ -109,17 +109,12 @@ class VietASR:
         sigs = [self._to_model_rate(s, sample_rate) for s in signals]
         return self._fused_engine().transcribe_beam(sigs, self.beam.decoder, self.beam.beam_width, row_independent)
 
-    def transcribe_manifest(self, manifest_filepath, batch_size=64, row_independent=True):
-        """Greedy transcripts of every entry of a NeMo JSON-lines manifest (parts/manifest.py:21-94), in manifest order,
-        plus the word error rate against the entries' ``text`` (None when no entry has one).
-
-        The reference CLI walks a directory one file at a time (infer.py:194-206).  Here the entries are sorted by
-        duration, cut into batches of ``batch_size`` and pushed through the pipelined engine two batches at a time
-        (engine.QuartzNetCTC.launch); with row_independent=True (default) every transcript is what ``transcribe`` returns
-        for that file alone.  PCM WAV only; files at another rate are resampled on the device."""
+    def _walk_manifest(self, manifest_filepath, batch_size, row_independent, after_forward=None):
+        """The entries of a NeMo JSON-lines manifest and their greedy transcripts, in manifest order: sorted by duration, cut
+        into batches of ``batch_size``, two batches in flight (engine.QuartzNetCTC.launch).  after_forward(entries, idx) -> the
+        ``launch`` hook of the batch holding entries ``idx`` (or None)."""
         import json
         from . import audio
-        from .data_layer import word_error_rate
         entries = []
         for path in str(manifest_filepath).split(","):
             with open(path, encoding="utf-8") as f:
@@ -138,15 +133,73 @@ class VietASR:
             for i in idx:
                 x, sr = audio.read_wav(entries[i]["audio_filepath"])
                 sigs.append(self._to_model_rate(x, sr))
-            pending.append((idx, self._fused_engine().launch(sigs, row_independent)))
+            hook = after_forward(entries, idx) if after_forward is not None else None
+            pending.append((idx, self._fused_engine().launch(sigs, row_independent, hook)))
             if len(pending) == 2:
                 collect(pending.pop(0))
         for job in pending:
             collect(job)
+        return entries, hyps
+
+    def transcribe_manifest(self, manifest_filepath, batch_size=64, row_independent=True):
+        """Greedy transcripts of every entry of a NeMo JSON-lines manifest (parts/manifest.py:21-94), in manifest order,
+        plus the word error rate against the entries' ``text`` (None when no entry has one).
+
+        The reference CLI walks a directory one file at a time (infer.py:194-206).  Here the entries are sorted by
+        duration, cut into batches of ``batch_size`` and pushed through the pipelined engine two batches at a time
+        (engine.QuartzNetCTC.launch); with row_independent=True (default) every transcript is what ``transcribe`` returns
+        for that file alone.  PCM WAV only; files at another rate are resampled on the device.
+
+        The rate is ``data_layer.word_error_rate`` on the RAW manifest text, computed on the host after the last batch.
+        ``evaluate_manifest`` scores the parsed tokens on the device instead (WER and CER); the two word error rates
+        differ only where a reference contains characters outside the labels."""
+        from .data_layer import word_error_rate
+        entries, hyps = self._walk_manifest(manifest_filepath, batch_size, row_independent)
         refs = [e.get("text") for e in entries]
         scored = [i for i, r in enumerate(refs) if r]
         wer = word_error_rate([hyps[i] for i in scored], [refs[i] for i in scored]) if scored else None
         return hyps, wer
+
+    def evaluate_manifest(self, manifest_filepath, batch_size=64, row_independent=True):
+        """``transcribe_manifest``'s walk with WER and CER scored on the device: -> (hyps, ``ErrorRate.compute()``), the
+        dict {"wer", "cer", "word_edits", "ref_words", "char_edits", "ref_chars"}.
+
+        As the reference's evaluation does (helpers.py:128-204), the references are the PARSED tokens -- the character
+        parser of ``AudioToTextDataLayer``: characters outside the labels are dropped -- and both rates are reported.
+        Each batch's scoring (metrics.ErrorRate.update) is enqueued on the compute stream right after its forward pass,
+        before its ids are copied out: no transcript has to reach the host to be scored, two batches stay in flight, and
+        the one synchronisation is the final ``compute``.  Entries without ``text`` are transcribed and not scored.
+        ``transcribe_manifest``'s rate is on the raw text: it differs from this "wer" only where a reference contains
+        characters outside the labels."""
+        from .metrics import ErrorRate
+        lab = {c: i for i, c in enumerate(self.labels)}
+        metric = ErrorRate(self.labels)
+        keep = []                   # pinned reference batches, alive until the copies that read them have run
+
+        def after_forward(entries, idx):
+            rows = [k for k, i in enumerate(idx) if entries[i].get("text")]
+            if not rows:
+                return None
+            toks = [[lab[c] for c in entries[idx[k]]["text"] if c in lab] for k in rows]
+            width = max(1, max(len(t) for t in toks))
+            ref = torch.zeros((len(rows), width), dtype=torch.int32).pin_memory()
+            ref_len = torch.tensor([len(t) for t in toks], dtype=torch.int32).pin_memory()
+            for k, t in enumerate(toks):
+                ref[k, : len(t)] = torch.tensor(t, dtype=torch.int32)
+            sel = None if len(rows) == len(idx) else torch.tensor(rows, dtype=torch.int64).pin_memory()
+            keep.append((ref, ref_len, sel))
+
+            def score(out):
+                dev = out["ids"].device
+                ids, id_len = out["ids"], out["id_len"]
+                if sel is not None:
+                    rows_d = sel.to(dev, non_blocking=True)
+                    ids, id_len = ids.index_select(0, rows_d), id_len.index_select(0, rows_d)
+                metric.update(ids, id_len, ref.to(dev, non_blocking=True), ref_len.to(dev, non_blocking=True))
+            return score
+
+        _, hyps = self._walk_manifest(manifest_filepath, batch_size, row_independent, after_forward)
+        return hyps, metric.compute()
 
     def launch_batch(self, signals, sample_rate=None, row_independent=False):
         """Asynchronous ``transcribe_batch``: returns a handle at once, ``.texts()`` waits (engine.QuartzNetCTC.launch)."""

@@ -133,3 +133,31 @@ def ctc_collapse(predictions, blank_id):
     n = torch.empty((B,), dtype=torch.int32, device=p.device)
     _lib.check(_lib.lib().vasr_ctc_collapse(p.data_ptr(), B, T1, int(blank_id), ids.data_ptr(), n.data_ptr(), _st()))
     return ids, n
+
+
+def error_counts(hyp_ids, hyp_len, ref_ids, ref_len, space_ids):
+    """word_error_rate (metrics.py:30-63) per row, both use_cer settings -> counts [B,4] i32 =
+    {word_edits, ref_words, char_edits, ref_chars} (vasr_error_counts_i32).  hyp_ids [B,Th] / hyp_len [B]: collapsed ids
+    (greedy or beam); ref_ids [B,Tr] / ref_len [B]: the data layer's transcripts / transcript_length -- int64 is cast on
+    the device.  space_ids: the label ids str.split() separates on (host integers, at most 8).  Enqueued on the current
+    stream; nothing synchronises.  A row with a negative length comes back as four -1."""
+    _need_cuda(hyp_ids, hyp_len, ref_ids, ref_len)
+    if hyp_ids.dim() != 2 or ref_ids.dim() != 2:
+        raise ValueError(f"hyp_ids / ref_ids must be [B, T], got {tuple(hyp_ids.shape)} / {tuple(ref_ids.shape)}")
+    B = hyp_ids.shape[0]
+    if ref_ids.shape[0] != B or tuple(hyp_len.shape) != (B,) or tuple(ref_len.shape) != (B,):
+        raise ValueError(f"batch sizes differ: ids {tuple(hyp_ids.shape)} / {tuple(ref_ids.shape)}, lengths "
+                         f"{tuple(hyp_len.shape)} / {tuple(ref_len.shape)}")
+    dev = hyp_ids.device
+    h, r = hyp_ids.to(torch.int32).contiguous(), ref_ids.to(device=dev, dtype=torch.int32).contiguous()
+    hn, rn = hyp_len.to(torch.int32).contiguous(), ref_len.to(device=dev, dtype=torch.int32).contiguous()
+    # a [B, 0] tensor has no storage to point at: the library wants a pointer it never reads
+    hp = h if h.numel() else torch.empty(1, dtype=torch.int32, device=dev)
+    rp = r if r.numel() else torch.empty(1, dtype=torch.int32, device=dev)
+    sp = [int(s) for s in space_ids]
+    arr = (_lib.C.c_int32 * max(len(sp), 1))(*sp)
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().vasr_error_counts_i32(hp.data_ptr(), h.shape[1], hn.data_ptr(), rp.data_ptr(), r.shape[1],
+                                                    rn.data_ptr(), B, arr, len(sp), counts.data_ptr(), _st()))
+    return counts
