@@ -269,6 +269,30 @@ VASR_API int vasr_error_counts_i32(const int32_t* d_hyp, int64_t hyp_width, cons
                                    const int32_t* h_space_ids, int n_space,   /* host, 0..8 ids */
                                    int32_t* d_counts /* [B][4] */, vasr_stream stream);
 
+/* Scores of classification logits, per row: metrics.classification_accuracy (nemo/collections/asr/metrics.py:66-99) for
+ * every k at once, nn.CrossEntropyLoss(reduction='none') as CrossEntropyLossNM calls it, and the top-k classes.
+ *   d_logits [B][num_classes] f32 contiguous; d_targets [B] i64 or NULL; k: 0, or 1..16 with k <= num_classes
+ *   -> d_topk_idx [B][k] i32, d_topk_val [B][k] f32, d_topk_prob [B][k] f32; d_rank [B] i32, d_loss [B] f32 (both need
+ *      d_targets).  Every output may be NULL.
+ * ONE total order on a row's classes: the larger value first; a NaN ranks above every number (as torch.topk orders it);
+ * -0 equals +0; among equal values, and among NaNs, the LOWER class index comes first.  torch.topk leaves the order of
+ * equal values unspecified ([1,3,3,2,3].topk(3) returns the indices 2,4,1 on the CPU): the tie rule is this library's own,
+ * and on a row with ties among its first k values or at its target the reference's own answer is not defined.
+ *   d_topk_idx / d_topk_val: the first k classes of that order and their logits (copies, bit-equal to the input);
+ *   d_topk_prob: expf(x - logsumexp(row)), the softmax probability of each of them;
+ *   d_rank[b]: the 0-based position of d_targets[b] in the order = the number of classes that come before it, so the row is
+ *     top-k correct iff 0 <= rank < k, for every k;
+ *   d_loss[b]: logsumexp(row) - row[target] in float32, the maximum subtracted first, expf / logf (no fast intrinsics).
+ * A target outside [0, num_classes) gives rank -1 and loss +0.0f for that row (the convention of vasr_error_counts_i32's -1
+ * rows); nothing is read outside the row.  Every reduction has one fixed order that depends on num_classes alone and there
+ * are no atomics: a row's outputs are bit-identical whatever batch it sits in.  NULL logits, batch <= 0, num_classes <= 0, k
+ * outside 0..16 or above num_classes, d_rank / d_loss without d_targets, k == 0 with neither of them, and k > 0 with all
+ * three top-k pointers NULL return VASR_ERR_INVALID; num_classes > 65536 returns VASR_ERR_UNSUPPORTED (the limit is in
+ * vasr_last_error()) -- all before a device is touched.  No handle, no workspace: one wavefront per row.  (ABI 8) */
+VASR_API int vasr_class_scores_f32(const float* d_logits, int batch, int num_classes, const int64_t* d_targets, int k,
+                                   int32_t* d_topk_idx, float* d_topk_val, float* d_topk_prob, int32_t* d_rank,
+                                   float* d_loss, vasr_stream stream);
+
 /* ---- the whole path in one call (the fast path bench.py times) ------------------------ */
 /* wav -> mel -> encoder -> CTC head -> log-softmax/argmax -> collapse, all intermediates in
  * the workspace (padded time stride, no port tensors materialised).

@@ -1644,6 +1644,26 @@ int vasr_error_counts_i32(const int32_t* d_hyp, int64_t hyp_width, const int32_t
   return check_launch("error_counts");
 }
 
+int vasr_class_scores_f32(const float* d_logits, int batch, int num_classes, const int64_t* d_targets, int k,
+                          int32_t* d_topk_idx, float* d_topk_val, float* d_topk_prob, int32_t* d_rank, float* d_loss,
+                          vasr_stream stream) {
+  // every refusal comes before a device is touched
+  if (!d_logits) return fail(VASR_ERR_INVALID, "class_scores: NULL logits");
+  if (batch <= 0 || num_classes <= 0) return fail(VASR_ERR_INVALID, "class_scores: batch %d, num_classes %d", batch, num_classes);
+  if (k < 0 || k > kClassScoresMaxK || k > num_classes)
+    return fail(VASR_ERR_INVALID, "class_scores: k %d outside 0..%d or above num_classes %d", k, kClassScoresMaxK, num_classes);
+  if ((d_rank || d_loss) && !d_targets) return fail(VASR_ERR_INVALID, "class_scores: d_rank / d_loss need d_targets");
+  const bool topk = d_topk_idx || d_topk_val || d_topk_prob;
+  if (k == 0 && !d_rank && !d_loss) return fail(VASR_ERR_INVALID, "class_scores: k == 0 and neither d_rank nor d_loss: nothing to do");
+  if (k > 0 && !topk) return fail(VASR_ERR_INVALID, "class_scores: k %d without a top-k output", k);
+  if (num_classes > kClassScoresMaxClasses)
+    return fail(VASR_ERR_UNSUPPORTED, "class_scores: %d classes, at most %d", num_classes, kClassScoresMaxClasses);
+  const int rc = launch_class_scores(d_logits, batch, num_classes, d_targets, k, d_topk_idx, d_topk_val, d_topk_prob, d_rank,
+                                     d_loss, static_cast<hipStream_t>(stream));
+  if (rc) return fail(VASR_ERR_HIP, "class_scores: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
+  return check_launch("class_scores");
+}
+
 // One contiguous slice of the batch through the whole path on one stream.
 static int transcribe_part(vasr_handle* h, const void* d_wav, bool pcm16, const int64_t* d_len, int batch, int64_t samples,
                            int64_t* d_pred, int32_t* d_ids, int32_t* d_id_len, float* d_logp, float* d_enc_len,

@@ -352,6 +352,16 @@ struct SpaceIds { int32_t id[kMetricsMaxSpace]; int n; };   // the label ids str
 int launch_error_counts(const int32_t* hyp, int hyp_width, const int32_t* hyp_len, const int32_t* ref, int ref_width,
                         const int32_t* ref_len, int batch, const SpaceIds& sp, int32_t* counts, hipStream_t st);
 
+// ---- classification scoring (cls_eval.hip) ----
+// per row of logits [B][classes]: the first k classes of the order (value descending, NaN first, lower index first among
+// equals) with their logits and softmax probabilities, the target's 0-based position in that order and its cross-entropy loss;
+// every output may be nullptr; the caller checks classes <= kClassScoresMaxClasses, k <= min(kClassScoresMaxK, classes) and
+// that rank / loss come with targets; returns 0 or a hipError_t
+constexpr int kClassScoresMaxClasses = 65536;
+constexpr int kClassScoresMaxK = 16;
+int launch_class_scores(const float* logits, int batch, int classes, const int64_t* targets, int k, int32_t* topk_idx,
+                        float* topk_val, float* topk_prob, int32_t* rank, float* loss, hipStream_t st);
+
 // ---- audio ingest (audio.hip) ----
 void launch_pcm16_to_f32(const short* in, int64_t n, float* out, hipStream_t st);
 void launch_resample(const float* x, int64_t ld_in, const int64_t* len_in, int batch, const float* table, int nwin,

@@ -1,4 +1,5 @@
-"""Batched manifest-driven data layer: counterpart of ``AudioToTextDataLayer`` for inference / evaluation.
+"""Batched manifest-driven data layers: counterparts of ``AudioToTextDataLayer`` and ``AudioToSpeechLabelDataLayer`` for
+inference / evaluation.
 
 Reference: nemo/collections/asr/data_layer.py:42-190 (ports, manifest arguments),
 parts/manifest.py:21-94 (JSON-lines entries with ``audio_filepath``, ``duration``, ``text``),
@@ -10,6 +11,7 @@ duration-balanced length buckets (``dist.balanced_shards``; ``shard_by="count"``
 in manifest order -- the reference shards with a DistributedSampler, data_layer.py:161-165, equal counts too).
 """
 import json
+import os
 
 import numpy as np
 import torch
@@ -23,7 +25,54 @@ class ChannelIndexType(LengthsType):
     pass
 
 
-class AudioToTextDataLayer(DataLayerNM):
+class _ManifestBatches:
+    """What the manifest-driven layers share: the cut of the kept items (path, duration, target) into this rank's batches
+    -- sharding, length buckets, ``drop_last`` -- and the iteration protocol over them (``_BatchIter``)."""
+
+    def _plan(self, items, batch_size, bucket_by_length, drop_last, shard_by):
+        if shard_by not in ("duration", "count"):
+            raise ValueError(f"shard_by must be 'duration' or 'count', got {shard_by!r}")
+        self.manifest_index = list(range(len(items)))        # position of every kept item in the (filtered) manifest
+        batches = None
+        if self.placement == DeviceType.AllGpu and torch.distributed.is_available() and torch.distributed.is_initialized():
+            rank, world = torch.distributed.get_rank(), torch.distributed.get_world_size()
+            # duration-balanced dealing fixes the batch composition (length buckets), so it is only taken when the caller did
+            # not ask for something it cannot honour: shuffle=True (the reference's DistributedSampler shuffles
+            # utterances, actions.py:669-693) and bucket_by_length=False fall back to equal-count contiguous shards
+            if shard_by == "duration" and all(it[1] > 0 for it in items) and bucket_by_length and not self._shuffle:
+                # length buckets of batch_size utterances dealt heaviest-first to the least loaded rank: the ranks'
+                # padded work (rows x longest row, summed over batches) ends up within a few percent of each other
+                batches = [sorted(b, key=lambda i: (items[i][1], i)) for b in balanced_shards([it[1] for it in items], world, batch_size)[rank]]
+                batches.sort(key=lambda b: items[b[0]][1])
+            else:
+                lo, hi = shard_range(len(items), rank, world)
+                self.manifest_index = self.manifest_index[lo:hi]
+                items = items[lo:hi]
+        order = list(range(len(items)))
+        if bucket_by_length and not self._shuffle:
+            order.sort(key=lambda i: items[i][1])    # similar lengths share a batch: less padding work
+        self._items, self._order = items, order
+        self._batches = batches if batches is not None else [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+        if drop_last:     # (the duration-balanced path sorts its batches by length: the short one is not the last)
+            self._batches = [b for b in self._batches if len(b) == batch_size]
+
+    def __len__(self):
+        return len(self._batches)
+
+    @property
+    def dataset(self):
+        return None
+
+    @property
+    def data_iterator(self):
+        return _BatchIter(self)
+
+    def utterance_order(self):
+        """Indices into the (duration-filtered) manifest, in the order the batches deliver them."""
+        return [self.manifest_index[i] for b in self._batches for i in b]
+
+
+class AudioToTextDataLayer(_ManifestBatches, DataLayerNM):
     @property
     def output_ports(self):
         return {"audio_signal": NeuralType(("B", "T"), AudioSignal(freq=self._sample_rate)),
@@ -49,49 +98,85 @@ class AudioToTextDataLayer(DataLayerNM):
                     if (min_duration and d and d < min_duration) or (max_duration and d > max_duration):
                         continue                       # manifest.py filters by duration the same way
                     items.append((e["audio_filepath"], d, e.get("text", "")))
-        if shard_by not in ("duration", "count"):
-            raise ValueError(f"shard_by must be 'duration' or 'count', got {shard_by!r}")
-        self.manifest_index = list(range(len(items)))        # position of every kept item in the (filtered) manifest
-        batches = None
-        if self.placement == DeviceType.AllGpu and torch.distributed.is_available() and torch.distributed.is_initialized():
-            rank, world = torch.distributed.get_rank(), torch.distributed.get_world_size()
-            # duration-balanced dealing fixes the batch composition (length buckets), so it is only taken when the caller did
-            # not ask for something it cannot honour: shuffle=True (the reference's DistributedSampler shuffles
-            # utterances, actions.py:669-693) and bucket_by_length=False fall back to equal-count contiguous shards
-            if shard_by == "duration" and all(it[1] > 0 for it in items) and bucket_by_length and not shuffle:
-                # length buckets of batch_size utterances dealt heaviest-first to the least loaded rank: the ranks'
-                # padded work (rows x longest row, summed over batches) ends up within a few percent of each other
-                batches = [sorted(b, key=lambda i: (items[i][1], i)) for b in balanced_shards([it[1] for it in items], world, batch_size)[rank]]
-                batches.sort(key=lambda b: items[b[0]][1])
-            else:
-                lo, hi = shard_range(len(items), rank, world)
-                self.manifest_index = self.manifest_index[lo:hi]
-                items = items[lo:hi]
-        order = list(range(len(items)))
-        if bucket_by_length and not shuffle:
-            order.sort(key=lambda i: items[i][1])    # similar lengths share a batch: less padding work
-        self._items, self._order = items, order
-        self._batches = batches if batches is not None else [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
-        if drop_last:     # (the duration-balanced path sorts its batches by length: the short one is not the last)
-            self._batches = [b for b in self._batches if len(b) == batch_size]
+        self._plan(items, batch_size, bucket_by_length, drop_last, shard_by)
 
     def tokens(self, text):
         return [self._lab[c] for c in text if c in self._lab]
 
-    def __len__(self):
-        return len(self._batches)
+    def _targets(self, texts):
+        """seq_collate_fn's token half: pad_id-padded token rows and their lengths."""
+        toks = [self.tokens(t) for t in texts]
+        t_len = torch.tensor([len(t) for t in toks], dtype=torch.int64)
+        tokens = torch.full((len(toks), max(int(t_len.max()), 1)), self.pad_id, dtype=torch.int64)
+        for k, t in enumerate(toks):
+            tokens[k, : len(t)] = torch.tensor(t, dtype=torch.int64)
+        return tokens, t_len
+
+
+class SpeechLabelsType(ChannelIndexType):
+    pass
+
+
+class AudioToSpeechLabelDataLayer(_ManifestBatches, DataLayerNM):
+    """Counterpart of ``AudioToSpeechLabelDataLayer`` (data_layer.py:449-620) for evaluation: clips with one target class
+    each.  Manifest lines as ``ASRSpeechLabel.__parse_item`` reads them (parts/collections.py:242-277): the audio under
+    ``audio_filename`` or ``audio_filepath`` (through ``expanduser``), a required ``duration``, the label under ``command``,
+    ``target`` or ``label`` in that precedence; ``offset`` is ignored, as ``AudioLabelDataset.__getitem__`` ignores it
+    (parts/dataset.py:380-391).  Duration filtering as ``SpeechLabel`` (collections.py:195-203).  Labels are mapped by
+    ``label2id``; an unknown one raises KeyError (here when the manifest is read, in the reference when the item is).
+    Batches: signals zero padded to the batch maximum (seq_collate_fn), ``label`` [B] int64, ``label_length`` [B] int64, all
+    ones.  PCM WAV only; ``trim_silence`` and ``augmentor`` are not implemented.  Sharding, length buckets and
+    ``utterance_order`` as in ``AudioToTextDataLayer``, whose defaults (no shuffle) it shares."""
 
     @property
-    def dataset(self):
-        return None
+    def output_ports(self):
+        return {"audio_signal": NeuralType(("B", "T"), AudioSignal(freq=self._sample_rate)),
+                "a_sig_length": NeuralType(tuple("B"), LengthsType()),
+                "label": NeuralType(tuple("B"), SpeechLabelsType()),
+                "label_length": NeuralType(tuple("B"), LengthsType())}
 
-    @property
-    def data_iterator(self):
-        return _BatchIter(self)
+    def __init__(self, manifest_filepath, labels, batch_size, sample_rate=16000, int_values=False, num_workers=0,
+                 shuffle=False, min_duration=0.1, max_duration=None, trim_silence=False, drop_last=False, load_audio=True,
+                 augmentor=None, bucket_by_length=True, shard_by="duration"):
+        super().__init__()
+        if trim_silence:
+            raise NotImplementedError("trim_silence=True (librosa.effects.trim) is not implemented")
+        if augmentor is not None:
+            raise NotImplementedError("audio augmentors are not implemented")
+        if not load_audio:
+            raise NotImplementedError("load_audio=False is not implemented")
+        self._sample_rate, self._batch_size, self._shuffle = sample_rate, batch_size, shuffle
+        self.labels = list(labels)
+        self.label2id = {label: i for i, label in enumerate(self.labels)}
+        self.id2label = dict(enumerate(self.labels))
+        items = []
+        for path in str(manifest_filepath).split(","):
+            with open(path, encoding="utf-8") as f:
+                for line in f:
+                    if not line.strip():
+                        continue
+                    audio_file, duration, label = self._parse_item(line)
+                    if (min_duration is not None and duration < min_duration) or \
+                            (max_duration is not None and duration > max_duration):
+                        continue
+                    items.append((audio_file, duration, self.label2id[label]))
+        self._plan(items, batch_size, bucket_by_length, drop_last, shard_by)
 
-    def utterance_order(self):
-        """Indices into the (duration-filtered) manifest, in the order the batches deliver them."""
-        return [self.manifest_index[i] for b in self._batches for i in b]
+    _AUDIO_KEYS, _LABEL_KEYS = ("audio_filename", "audio_filepath"), ("command", "target", "label")
+
+    @classmethod
+    def _parse_item(cls, line):
+        """One manifest line -> (path, duration, label); the first key present wins, in the reference's precedence."""
+        entry = json.loads(line)
+        first = lambda keys: next((entry[k] for k in keys if k in entry), None)  # noqa: E731
+        found = (("audio file", first(cls._AUDIO_KEYS)), ("duration", entry.get("duration")), ("label", first(cls._LABEL_KEYS)))
+        for what, value in found:
+            if value is None:
+                raise ValueError(f"Manifest file has invalid json line structure: {line} without proper {what} key.")
+        return os.path.expanduser(found[0][1]), found[1][1], found[2][1]
+
+    def _targets(self, labels):
+        return torch.tensor(labels, dtype=torch.int64), torch.ones(len(labels), dtype=torch.int64)
 
 
 class _BatchIter:
@@ -112,23 +197,19 @@ class _BatchIter:
             raise StopIteration
         idx = L._batches[self.i]
         self.i += 1
-        sigs, toks = [], []
+        sigs, targets = [], []
         for j in idx:
-            path, _, text = L._items[j]
+            path, _, target = L._items[j]
             x, sr = read_wav(path)
             if sr != L._sample_rate:
                 raise ValueError(f"{path}: sample rate {sr} != {L._sample_rate}; resample first (audio.resample)")
             sigs.append(x)
-            toks.append(L.tokens(text))
+            targets.append(target)
         a_len = torch.tensor([len(s) for s in sigs], dtype=torch.int64)
         audio = torch.zeros((len(sigs), int(a_len.max())), dtype=torch.float32)
         for k, s in enumerate(sigs):
             audio[k, : len(s)] = torch.from_numpy(s)
-        t_len = torch.tensor([len(t) for t in toks], dtype=torch.int64)
-        tokens = torch.full((len(toks), max(int(t_len.max()), 1)), L.pad_id, dtype=torch.int64)
-        for k, t in enumerate(toks):
-            tokens[k, : len(t)] = torch.tensor(t, dtype=torch.int64)
-        return audio, a_len, tokens, t_len
+        return (audio, a_len) + tuple(L._targets(targets))
 
 
 def word_error_rate(hypotheses, references, use_cer=False):

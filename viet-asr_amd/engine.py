@@ -504,6 +504,12 @@ class QuartzNetClassifier:
         """List of 1-D arrays (model sample rate; float, or integer PCM) -> the arg-max class index per signal, or its label
         where ``labels`` was given; zero-pad-to-max collate (parts/dataset.py:14-53).  Short inputs follow QuartzNetCTC's
         rules: no empty batch or signal, and more than n_fft / 2 samples per signal with row_independent."""
+        out = self.forward(*self._collate(signals, row_independent), offsets=offsets, row_independent=row_independent)
+        idx = out.argmax(-1).cpu().tolist()
+        return [self.labels[i] for i in idx] if self.labels is not None else idx
+
+    def _collate(self, signals, row_independent):
+        """classify's collate: (wav [B, L] f32, length [B] i64) on the device, rows zero padded to the longest."""
         if len(signals) == 0:
             raise ValueError("empty batch")
         lens = [len(s) for s in signals]
@@ -515,10 +521,71 @@ class QuartzNetClassifier:
         batch = np.zeros((len(signals), max(lens)), dtype=np.float32)
         for i, s in enumerate(signals):
             batch[i, : lens[i]] = _pcm_to_float(np.asarray(s))
-        out = self.forward(torch.from_numpy(batch).to(self.device), torch.tensor(lens, device=self.device), offsets=offsets,
-                           row_independent=row_independent)
-        idx = out.argmax(-1).cpu().tolist()
-        return [self.labels[i] for i in idx] if self.labels is not None else idx
+        return torch.from_numpy(batch).to(self.device), torch.tensor(lens, device=self.device)
+
+    def classify_topk(self, signals, k, offsets=None, row_independent=False):
+        """``classify``'s input -> per signal the list of its k best (label or index, softmax probability) pairs, best first:
+        larger logit first, the lower class index first among equal ones (``stages.classification_scores``).  The same
+        collate and forward pass as ``classify``; one device-to-host copy at the end."""
+        from . import stages
+        k = int(k)
+        if not 1 <= k <= min(16, self.num_classes):
+            raise ValueError(f"k must be in 1..{min(16, self.num_classes)}, got {k}")
+        out = self.forward(*self._collate(signals, row_independent), offsets=offsets, row_independent=row_independent)
+        top = stages.classification_scores(out, k=k, want_prob=True)
+        # one copy: the indices (exact in float32, below 2^24) next to the probabilities
+        both = torch.cat([top["indices"].to(torch.float32), top["probs"]], dim=1).cpu().tolist()
+        name = (lambda i: self.labels[i]) if self.labels is not None else (lambda i: i)
+        return [[(name(int(r[j])), r[k + j]) for j in range(k)] for r in both]
+
+    def evaluate_manifest(self, manifest_filepath, batch_size=64, top_k=(1,), offsets=None, row_independent=False):
+        """Top-k accuracy and evaluation loss over a labelled manifest: -> (predictions, ``TopKAccuracy.compute()``), the
+        dict {"accuracy": {k: float}, "correct": {k: int}, "samples": int, "eval_loss": float}; predictions: the top-1 class
+        (label, or index without ``labels``) per kept manifest entry, in manifest order.
+        Where the data layer shards the manifest over a process group, "entry" -- here and for ``offsets`` -- means THIS
+        rank's entries, still in manifest order; a ``TopKAccuracy`` of your own with ``compute(reduce=True)`` gives the
+        global figure.
+
+        The manifest is walked by ``AudioToSpeechLabelDataLayer`` (its line format and duration filter; the ``labels`` given
+        to this engine map the manifest's labels to classes, without them the manifest must hold class indices).  Each
+        batch crosses from pinned memory, and its scoring (one vasr_class_scores_f32 launch: top-1, rank and loss) is
+        enqueued right behind its forward pass; the only synchronisation before the final ``compute`` is the copy of the
+        predictions after the last batch.  offsets: None (drawn per batch as ``forward`` draws them) or one crop offset per
+        kept manifest entry, in manifest order."""
+        from . import stages
+        from .data_layer import AudioToSpeechLabelDataLayer
+        from .metrics import TopKAccuracy
+        labels = self.labels if self.labels is not None else list(range(self.num_classes))
+        layer = AudioToSpeechLabelDataLayer(manifest_filepath, labels, batch_size, sample_rate=self.frontend["sample_rate"])
+        order = layer.utterance_order()          # positions in the whole filtered manifest, of this rank's entries only
+        slot = {g: p for p, g in enumerate(sorted(order))}
+        if offsets is not None and len(offsets) != len(order):
+            raise ValueError(f"{len(offsets)} offsets for {len(order)} manifest entries")
+        metric = TopKAccuracy(top_k)
+        picks, staged, pos = [], [], 0          # staged: pinned batches, alive until the copies that read them have run
+        for audio, a_len, label, _ in layer.data_iterator:
+            B = audio.shape[0]
+            if row_independent and int(a_len.min()) <= self.frontend["n_fft"] // 2:
+                raise ValueError(f"row-independent batching needs more than n_fft/2 = {self.frontend['n_fft'] // 2} samples "
+                                 f"per signal (got {int(a_len.min())}): an unbatched call refuses such input too")
+            off = None
+            if offsets is not None:
+                off = torch.tensor([int(offsets[slot[i]]) for i in order[pos : pos + B]], dtype=torch.int64).pin_memory()
+            pos += B
+            host = [t.pin_memory() for t in (audio, a_len, label)] + ([off] if off is not None else [])
+            dev = [t.to(self.device, non_blocking=True) for t in host]
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(self.device))
+            staged = [(e, h) for e, h in staged if not e.query()] + [(done, host)]
+            out = self.forward(dev[0], dev[1], offsets=dev[3] if off is not None else None, row_independent=row_independent)
+            scores = stages.classification_scores(out, dev[2], k=1)
+            metric.add_scores(scores["rank"], scores["loss"])
+            picks.append(scores["indices"].view(-1))
+        idx = torch.cat(picks).cpu().tolist() if picks else []
+        predictions = [None] * len(order)
+        for i, c in zip(order, idx):
+            predictions[slot[i]] = self.labels[c] if self.labels is not None else c
+        return predictions, metric.compute()
 
 
 class PendingBatch:

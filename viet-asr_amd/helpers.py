@@ -4,10 +4,17 @@ The reference collapses predictions in a Python loop over every frame of every u
 collapse runs on the device (vasr_ctc_collapse: ballot + popcount compaction, one wavefront per
 utterance) and only the id -> label join happens on the host.  Like the reference it walks ALL T'
 frames, including padded ones (quirk Q4).
+
+Classification (helpers.py:81-113, 215-288): the three functions keep the reference's signatures and ``global_vars`` keys
+and take their top-k hits from ``stages.classification_scores``; the per-batch entries stay device tensors until the epoch
+function, which is the one place that synchronises.
 """
+import logging
+
 import torch
 
 from . import stages
+from .metrics import top_k_hits
 
 
 def ctc_decoder_predictions_tensor(tensor, labels):
@@ -30,3 +37,70 @@ def post_process_predictions(predictions, labels):
     for prediction in predictions:
         results += ctc_decoder_predictions_tensor(prediction, labels=labels)
     return results
+
+
+def _k_list(eval_metric):
+    if eval_metric is None:
+        return [1]
+    return list(eval_metric) if isinstance(eval_metric, (list, tuple)) else [eval_metric]
+
+
+def _reference_accuracy(rank, top_k):
+    """Per k of top_k, the figure the reference's classification_accuracy returns (metrics.classification_accuracy: hits /
+    (k * B)) as a float32 device scalar."""
+    hits = top_k_hits(rank, top_k).to(torch.float32)
+    rows = int(rank.shape[0])
+    # tensor / tensor: a correctly rounded float32 division, as the reference's mean (a scalar divisor may be turned into a
+    # multiplication by its reciprocal)
+    return [hits[i] / torch.full((), float(k * rows), dtype=torch.float32, device=rank.device) for i, k in enumerate(top_k)]
+
+
+def monitor_classification_training_progress(tensors, eval_metric=None, tb_logger=None):
+    """Counterpart of helpers.py:81-113.  tensors: [loss, logits, targets]; eval_metric: a k or a list of them (default
+    [1]).  Logs the loss and, per k, ``training_batch_top@k`` in percent; ``tb_logger.add_scalar`` gets the same tag with the
+    fraction.  The figures come back from the device in one copy."""
+    top_k = _k_list(eval_metric)
+    loss, logits, targets = tensors
+    rank = stages.classification_scores(logits, targets, want_loss=False)["rank"]
+    accs = torch.stack(_reference_accuracy(rank, [int(k) for k in top_k])).cpu().numpy()
+    logging.info("Loss: %s", loss)
+    for k, acc in zip(top_k, accs):
+        name = f"training_batch_top@{k}"
+        if tb_logger is not None:
+            tb_logger.add_scalar(name, acc)
+        logging.info("%s: %.4f", name, acc * 100.0)
+
+
+def process_classification_evaluation_batch(tensors, global_vars, top_k=1):
+    """Counterpart of helpers.py:215-253: one batch into the running lists of ``global_vars`` -- ``EvalLoss`` (the batch's
+    mean loss), ``batchsize`` and, per k of the sorted top_k, ``CorrectCount@k`` (``classification_accuracy`` x batch size).
+    tensors: lists of tensors under keys starting with ``logits`` and ``label`` (concatenated), optionally the batch's loss
+    tensors under a key starting with ``loss``; without one the loss is the stage's, the mean cross entropy of the batch,
+    and only then does the launch compute it.  Everything appended but the batch size is a device scalar; nothing
+    synchronises."""
+    ks = sorted([top_k] if isinstance(top_k, int) else top_k)
+    own_loss = [v for name, v in tensors.items() if name.startswith("loss")]
+    logits = torch.cat(list(next(v for name, v in tensors.items() if name.startswith("logits"))), 0)
+    labels = torch.cat(list(next(v for name, v in tensors.items() if name.startswith("label"))), 0)
+    scores = stages.classification_scores(logits, labels, want_loss=not own_loss)
+    rows = int(labels.shape[0])
+    batch_losses = [torch.stack(list(v)).mean() for v in own_loss] or [scores["loss"].mean()]
+    global_vars.setdefault("EvalLoss", []).extend(batch_losses)
+    global_vars.setdefault("batchsize", []).append(rows)
+    for k, acc in zip(ks, _reference_accuracy(scores["rank"], ks)):
+        global_vars.setdefault(f"CorrectCount@{k}", []).append(acc * rows)
+
+
+def process_classification_evaluation_epoch(global_vars, eval_metric=None, tag=None):
+    """Counterpart of helpers.py:256-288: the epoch's dict from what the batch function gathered -- ``Evaluation_Loss {tag}``,
+    the mean of the batch means, and per k of eval_metric ``Evaluation_Accuracy_Top@{k} {tag}`` in percent (a float32
+    tensor, as there).  The one place that synchronises: the entries are copied to the host and reduced there in float32."""
+    tag = "" if tag is None else tag
+    host = lambda entries: torch.stack([torch.as_tensor(v, dtype=torch.float32) for v in entries]).cpu()  # noqa: E731
+    samples = torch.tensor(global_vars["batchsize"]).sum().float()
+    logs = {f"Evaluation_Loss {tag}": host(global_vars["EvalLoss"]).mean().item()}
+    for k in _k_list(eval_metric):
+        logs[f"Evaluation_Accuracy_Top@{k} {tag}"] = host(global_vars[f"CorrectCount@{k}"]).sum() / samples * 100.0
+    for name, value in logs.items():
+        logging.info("%s: %s", name, float(value))
+    return logs

@@ -1,4 +1,4 @@
-"""Word and character error rate on device id sequences.
+"""Word and character error rate on device id sequences; top-k accuracy and evaluation loss on classification logits.
 
 Reference: nemo/collections/asr/metrics.py:30-63 (``word_error_rate``, both ``use_cer`` settings) as
 ``process_evaluation_epoch`` reports them (helpers.py:188-189), scored on the parsed token tensors the data layer delivers
@@ -6,6 +6,10 @@ Reference: nemo/collections/asr/metrics.py:30-63 (``word_error_rate``, both ``us
 ``stages.error_counts`` (vasr_error_counts_i32, csrc/metrics.hip); this module only sums four integers on the device and
 divides them once on the host.  ``data_layer.word_error_rate`` is the same metric on host strings; the two differ only
 where a reference holds characters outside the labels, which the character parser drops before the tokens are made.
+
+``classification_accuracy`` (metrics.py:66-99) and ``TopKAccuracy`` (the running form of
+process_classification_evaluation_batch / _epoch, helpers.py:215-288) rest on ``stages.classification_scores``
+(vasr_class_scores_f32, csrc/cls_eval.hip): the target's rank among the row's classes and its cross-entropy loss per row.
 """
 import torch
 
@@ -74,3 +78,96 @@ def word_error_rate_ids(ids, id_len, transcripts, transcript_length, labels, use
     m = ErrorRate(labels)
     m.update(ids, id_len, transcripts, transcript_length)
     return m.compute()["cer" if use_cer else "wer"]
+
+
+def _top_k_list(top_k):
+    ks = [int(k) for k in ([top_k] if isinstance(top_k, int) else top_k)]
+    if not ks or min(ks) < 1:
+        raise ValueError(f"top_k must hold integers >= 1, got {top_k!r}")
+    return ks
+
+
+def top_k_hits(rank, top_k):
+    """rank [B] i32 of ``stages.classification_scores`` -> int64 [len(top_k)] on its device: the rows with 0 <= rank < k,
+    per k.  The k are kernel arguments: nothing is copied from the host."""
+    valid = rank >= 0
+    return torch.stack([(valid & (rank < int(k))).sum(dtype=torch.int64) for k in top_k])
+
+
+def classification_accuracy(logits, targets, top_k=None):
+    """metrics.py:66-99 for device tensors: one float32 per entry of ``top_k`` (default [1]), in the order given.  The
+    reference takes ``logits.topk(max(top_k))`` and compares; here a row is top-k correct iff its target's rank
+    (``stages.classification_scores``) is below k.  One synchronisation.
+
+    The RESULT is the reference's, as written there: ``correct[:k].view(-1).float().mean()`` averages over the k x B
+    comparison matrix, of which at most one entry per row is true, so the value is hits / (k * B) -- the top-k accuracy
+    divided by k (equal to it for k = 1).  ``TopKAccuracy.compute()["accuracy"]`` is hits / B.  Where a row's values tie at
+    the target, torch.topk's order is unspecified and this library puts the lower class index first."""
+    import numpy as np
+    ks = _top_k_list([1] if top_k is None else top_k)
+    rank = stages.classification_scores(logits, targets, want_loss=False)["rank"]
+    n = int(rank.shape[0])
+    # float32 division of two integers below 2^24, as torch's mean of a float32 tensor of zeros and ones
+    return [np.float32(c) / np.float32(k * n) for c, k in zip(top_k_hits(rank, ks).cpu().tolist(), ks)]
+
+
+class TopKAccuracy:
+    """Running top-k accuracy and evaluation loss over batches of logits: process_classification_evaluation_batch / _epoch
+    (helpers.py:215-288) without their per-batch host round trips.  ``update`` enqueues and never synchronises; ``compute``
+    is the one sync.  The loss is kept as the reference keeps it -- one float32 batch mean per ``update``, and ``eval_loss``
+    the mean of those batch means (EvalLoss), not the mean over the samples."""
+
+    def __init__(self, top_k=(1,)):
+        self.top_k = sorted(set(_top_k_list(top_k)))
+        self._acc = None          # int64 [len(top_k) + 2]: correct rows per k, rows, rows whose target was out of range
+        self._loss = None         # float32 [2]: the sum of the batch means, the number of batches
+
+    def update(self, logits, targets):
+        """logits [B,C] / targets [B] on the device; enqueued on the current stream."""
+        out = stages.classification_scores(logits, targets)
+        self.add_scores(out["rank"], out["loss"])
+
+    def add_scores(self, rank, loss):
+        """One batch as ``stages.classification_scores`` scored it -- rank [B] i32, loss [B] f32 -- for callers that made
+        that launch themselves (``QuartzNetClassifier.evaluate_manifest`` takes its top-1 from the same one).  No host
+        round trip."""
+        n = torch.full((1,), rank.shape[0], dtype=torch.int64, device=rank.device)
+        row = torch.cat([top_k_hits(rank, self.top_k), n, (rank < 0).sum(dtype=torch.int64).reshape(1)])
+        pair = torch.stack([loss.mean(dtype=torch.float32), torch.ones((), dtype=torch.float32, device=loss.device)])
+        self._acc = row if self._acc is None else self._acc + row
+        self._loss = pair if self._loss is None else self._loss + pair
+
+    def reset(self):
+        self._acc = self._loss = None
+
+    def compute(self, reduce=False, group=None):
+        """-> {"accuracy": {k: correct / samples}, "correct": {k: int}, "samples": int, "eval_loss": float}.  reduce=True sums
+        the integers (``dist.all_reduce_counts``) and the (sum of batch means, batches) pair (one float all-reduce) over the
+        process group first.  The division of the loss pair is done here, in float64 on the host.  No sample gives NaN.
+        Raises VasrError when a target was outside [0, num_classes)."""
+        nk = len(self.top_k)
+        acc = self._acc if self._acc is not None else torch.zeros(nk + 2, dtype=torch.int64)
+        pair = self._loss if self._loss is not None else torch.zeros(2, dtype=torch.float32)
+        if reduce:
+            acc, pair = dist.all_reduce_counts(acc, group), dist.all_reduce_counts(pair, group)
+        host, (loss_sum, batches) = acc.cpu().tolist(), pair.cpu().tolist()
+        samples, bad = host[nk], host[nk + 1]
+        if bad:
+            raise _lib.VasrError(f"{bad} scored rows carried a target outside [0, num_classes): no accuracy or loss is "
+                                 "returned for them")
+        nan = float("nan")
+        return dict(accuracy={k: host[i] / samples if samples else nan for i, k in enumerate(self.top_k)},
+                    correct={k: host[i] for i, k in enumerate(self.top_k)}, samples=samples,
+                    eval_loss=float(loss_sum) / float(batches) if batches else nan)
+
+    def logs(self, tag=None, reduce=False, group=None):
+        """process_classification_evaluation_epoch's dict (helpers.py:256-288): ``Evaluation_Loss {tag}`` and
+        ``Evaluation_Accuracy_Top@{k} {tag}``, in percent.  The reference's figure, as its batch function accumulates it:
+        CorrectCount@k holds ``classification_accuracy`` x batch size = hits / k, so the logged value is 100 x hits /
+        (k x samples) -- the accuracy of ``compute`` divided by k (see ``classification_accuracy``)."""
+        r = self.compute(reduce, group)
+        tag = "" if tag is None else tag
+        out = {f"Evaluation_Loss {tag}": r["eval_loss"]}
+        for k in self.top_k:
+            out[f"Evaluation_Accuracy_Top@{k} {tag}"] = r["accuracy"][k] / k * 100.0
+        return out

@@ -161,3 +161,47 @@ def error_counts(hyp_ids, hyp_len, ref_ids, ref_len, space_ids):
         _lib.check(_lib.lib().vasr_error_counts_i32(hp.data_ptr(), h.shape[1], hn.data_ptr(), rp.data_ptr(), r.shape[1],
                                                     rn.data_ptr(), B, arr, len(sp), counts.data_ptr(), _st()))
     return counts
+
+
+def classification_scores(logits, targets=None, k=0, want_prob=False, want_loss=True):
+    """Per-row scores of classification logits [B,C] (vasr_class_scores_f32) -> a dict with the requested tensors:
+    ``rank`` [B] i32 and (unless want_loss=False, which spares the kernel its logsumexp pass) ``loss`` [B] f32 when ``targets`` [B] is given -- the target's 0-based position among the row's classes
+    (top-k correct iff 0 <= rank < k; metrics.classification_accuracy, metrics.py:66-99) and
+    nn.CrossEntropyLoss(reduction='none'); ``indices`` [B,k] i32 and ``values`` [B,k] f32 when k > 0 (1..16, k <= C), plus
+    ``probs`` [B,k] f32, the softmax probabilities, with want_prob.  The order: larger value first, NaN above every number,
+    the lower class index first among equal values (include/vasr.h).  A target outside [0, C) gives rank -1 and loss 0.
+    logits: float32 cuda (other floating types are cast on the device); targets: any integer type, cast to int64 on the
+    device.  Enqueued on the current stream; nothing synchronises."""
+    _need_cuda(logits)
+    if logits.dim() != 2:
+        raise ValueError(f"logits must be [B, C], got {tuple(logits.shape)}")
+    if not logits.dtype.is_floating_point:
+        raise ValueError(f"logits must be floating point, got {logits.dtype}")
+    B, Cn = logits.shape
+    k = int(k)
+    if targets is None and k == 0:
+        raise ValueError("nothing requested: give targets, k > 0, or both")
+    if want_prob and k == 0:
+        raise ValueError("want_prob needs k > 0")
+    dev = logits.device
+    x = logits.to(torch.float32).contiguous()
+    out, t = {}, None
+    if targets is not None:
+        if targets.dtype.is_floating_point or targets.dtype == torch.bool or tuple(targets.shape) != (B,):
+            raise ValueError(f"targets must be {B} integers, got {targets.dtype} {tuple(targets.shape)}")
+        t = targets.to(device=dev, dtype=torch.int64).contiguous()
+        out["rank"] = torch.empty((B,), dtype=torch.int32, device=dev)
+        if want_loss:
+            out["loss"] = torch.empty((B,), dtype=torch.float32, device=dev)
+    if k:
+        out["indices"] = torch.empty((B, k), dtype=torch.int32, device=dev)
+        out["values"] = torch.empty((B, k), dtype=torch.float32, device=dev)
+        if want_prob:
+            out["probs"] = torch.empty((B, k), dtype=torch.float32, device=dev)
+    ptr = lambda name: out[name].data_ptr() if name in out else None  # noqa: E731
+    with torch.cuda.device(dev):
+        # (an empty batch or k out of range is refused by the library before anything is launched)
+        _lib.check(_lib.lib().vasr_class_scores_f32(x.data_ptr() if x.numel() else None, B, Cn,
+                                                    t.data_ptr() if t is not None and B else None, k, ptr("indices"),
+                                                    ptr("values"), ptr("probs"), ptr("rank"), ptr("loss"), _st()))
+    return out
