@@ -269,6 +269,60 @@ VASR_API int vasr_error_counts_i32(const int32_t* d_hyp, int64_t hyp_width, cons
                                    const int32_t* h_space_ids, int n_space,   /* host, 0..8 ids */
                                    int32_t* d_counts /* [B][4] */, vasr_stream stream);
 
+/* The alignment rule.  vasr_error_ops_i32 splits the distance above into substitutions, deletions and insertions; the sum is
+ * unique, the split is not (other tools break ties differently), so the rule is part of the interface.  For a hypothesis
+ * h[0..n) and a reference r[0..m), unit costs:
+ *   borders:   D[i][0] = i (every hypothesis element there is an insertion), D[0][j] = j (every reference element a deletion);
+ *   interior:  diag = D[i-1][j-1] + (h[i-1] != r[j-1]),
+ *              dele = D[i][j-1] + 1   (reference element j has no partner),
+ *              ins  = D[i-1][j] + 1   (hypothesis element i has no partner);
+ *   tie-break: the cell's predecessor is diag if diag <= min(dele, ins), otherwise dele if dele <= ins, otherwise ins;
+ *   the alignment is the one path from (n, m) back to (0, 0) along those predecessors; a diagonal step is a hit if the two
+ *   elements are equal and a substitution if not.
+ * A cell's predecessor depends on its three neighbours' costs alone, so the path is the same in whatever order the cells are
+ * computed (the kernel walks anti-diagonals).  hits + sub + del = m, hits + sub + ins = n, sub + del + ins = D[n][m].
+ *
+ * vasr_error_ops_i32: inputs, word and character semantics, clamping and refusals of vasr_error_counts_i32
+ *   -> d_ops_counts [B][8] i32 = {word_sub, word_del, word_ins, word_hits, char_sub, char_del, char_ins, char_hits}, 16-byte
+ *      aligned (two vector stores per row); eight -1 for a row with a negative length on either side;
+ *   -> optionally the WORD-level edit script: d_script [B][L] i32 and d_script_len [B] i32, both or neither, with
+ *      L = (hyp_width + 1) / 2 + (ref_width + 1) / 2 (a word needs a separator: no alignment of the rows' words is longer).
+ *      d_script[b][0 .. len) is the alignment from the first word to the last as op codes 0 = hit, 1 = substitution,
+ *      2 = deletion, 3 = insertion; word indices are implied: a hit or a substitution consumes one word of each side, a deletion
+ *      one reference word, an insertion one hypothesis word.  Entries at or beyond len are not written; a -1 row gets
+ *      d_script_len = -1.  The script's op counts equal the row's four word counts.
+ * Counts alone take widths up to 4096 in the LDS vasr_error_counts_i32 takes (a cell carries its cost and its path's
+ * substitutions in one word; deletions - insertions = j - i on every path into (i, j)).  A script keeps the predecessor of
+ * every word cell, 2 bits each, in LDS: both widths must then be <= 1024 (512 words per side, about 66 KB of bits, 98 KB in
+ * all); wider requests return VASR_ERR_UNSUPPORTED with the limit in vasr_last_error().  One script pointer without the other
+ * returns VASR_ERR_INVALID.  All refusals come before a device is touched.  No handle, no workspace, no atomics, integers only:
+ * one workgroup per row, and a row's outputs do not depend on the batch it sits in.  (ABI 8) */
+VASR_API int vasr_error_ops_i32(const int32_t* d_hyp, int64_t hyp_width, const int32_t* d_hyp_len,
+                                const int32_t* d_ref, int64_t ref_width, const int32_t* d_ref_len, int batch,
+                                const int32_t* h_space_ids, int n_space,   /* host, 0..8 ids */
+                                int32_t* d_ops_counts /* [B][8] */, int32_t* d_script /* [B][L] or NULL */,
+                                int32_t* d_script_len /* [B] or NULL */, vasr_stream stream);
+
+/* vasr_error_counts_i32 of every hypothesis of an n-best list against the row's ONE reference, and the oracle: the best slot
+ * per row.  Inputs as vasr_beam_search_nbest_f32 writes them:
+ *   d_ids [B][nbest][width] i32, d_id_len [B][nbest] i32, d_count [B] i32 (slots filled; clamped to nbest),
+ *   d_ref [B][ref_width] i32, d_ref_len [B] i32 -- row b serves all its slots, it is not replicated in memory
+ *   -> d_slot_counts [B][nbest][4] i32 (required, 16-byte aligned): vasr_error_counts_i32's four numbers of every filled slot,
+ *      four -1 in slots at or beyond d_count[b];
+ *   -> d_counts [B][4] i32 (may be NULL; 16-byte aligned) = {min word_edits, ref_words, min char_edits, ref_chars}: the two
+ *      minima are taken independently over the FILLED slots only (an unfilled slot has length 0 and never wins, even where
+ *      the empty string would beat every hypothesis); the layout is vasr_error_counts_i32's and accumulates the same way;
+ *   -> d_slot [B][2] i32 (may be NULL): the slot of the word minimum and of the character minimum, the lower slot among equals.
+ * A row with a negative d_id_len in a filled slot (the search's overflow report), a negative d_ref_len or d_count < 1 gives
+ * -1 in every output of that row.  Refusals as vasr_error_counts_i32, plus nbest < 1 (VASR_ERR_INVALID) and nbest > 65535
+ * (VASR_ERR_UNSUPPORTED; the beam search returns at most 128).  B x nbest
+ * workgroups, then one wavefront per row for the minima in a fixed order: no atomics, no workspace.  (ABI 8) */
+VASR_API int vasr_nbest_error_counts_i32(const int32_t* d_ids, int64_t width, const int32_t* d_id_len,
+                                         const int32_t* d_count, int nbest, const int32_t* d_ref, int64_t ref_width,
+                                         const int32_t* d_ref_len, int batch, const int32_t* h_space_ids, int n_space,
+                                         int32_t* d_slot_counts /* [B][nbest][4] */, int32_t* d_counts /* [B][4] or NULL */,
+                                         int32_t* d_slot /* [B][2] or NULL */, vasr_stream stream);
+
 /* Scores of classification logits, per row: metrics.classification_accuracy (nemo/collections/asr/metrics.py:66-99) for
  * every k at once, nn.CrossEntropyLoss(reduction='none') as CrossEntropyLossNM calls it, and the top-k classes.
  *   d_logits [B][num_classes] f32 contiguous; d_targets [B] i64 or NULL; k: 0, or 1..16 with k <= num_classes

@@ -1644,6 +1644,60 @@ int vasr_error_counts_i32(const int32_t* d_hyp, int64_t hyp_width, const int32_t
   return check_launch("error_counts");
 }
 
+int vasr_error_ops_i32(const int32_t* d_hyp, int64_t hyp_width, const int32_t* d_hyp_len, const int32_t* d_ref,
+                       int64_t ref_width, const int32_t* d_ref_len, int batch, const int32_t* h_space_ids, int n_space,
+                       int32_t* d_ops_counts, int32_t* d_script, int32_t* d_script_len, vasr_stream stream) {
+  // every refusal comes before a device is touched
+  if (!d_hyp || !d_hyp_len || !d_ref || !d_ref_len || !d_ops_counts) return fail(VASR_ERR_INVALID, "error_ops: NULL pointer");
+  if (!d_script != !d_script_len) return fail(VASR_ERR_INVALID, "error_ops: d_script and d_script_len go together (both or neither)");
+  if (batch <= 0 || hyp_width < 0 || ref_width < 0)
+    return fail(VASR_ERR_INVALID, "error_ops: batch %d, widths %lld / %lld", batch, (long long)hyp_width, (long long)ref_width);
+  if (n_space < 0 || n_space > kMetricsMaxSpace || (n_space > 0 && !h_space_ids))
+    return fail(VASR_ERR_INVALID, "error_ops: n_space %d outside 0..%d (or no ids given)", n_space, kMetricsMaxSpace);
+  if (reinterpret_cast<uintptr_t>(d_ops_counts) & 15) return fail(VASR_ERR_INVALID, "error_ops: d_ops_counts is not 16-byte aligned");
+  if (hyp_width > kMetricsMaxWidth || ref_width > kMetricsMaxWidth)
+    return fail(VASR_ERR_UNSUPPORTED, "error_ops: rows of %lld / %lld ids, at most %d per side", (long long)hyp_width,
+                (long long)ref_width, kMetricsMaxWidth);
+  if (d_script && (hyp_width > kMetricsMaxScriptWidth || ref_width > kMetricsMaxScriptWidth))
+    return fail(VASR_ERR_UNSUPPORTED, "error_ops: rows of %lld / %lld ids with a script, at most %d per side (counts alone: %d)",
+                (long long)hyp_width, (long long)ref_width, kMetricsMaxScriptWidth, kMetricsMaxWidth);
+  SpaceIds sp{};
+  sp.n = n_space;
+  for (int k = 0; k < n_space; ++k) sp.id[k] = h_space_ids[k];
+  const int rc = launch_error_ops(d_hyp, (int)hyp_width, d_hyp_len, d_ref, (int)ref_width, d_ref_len, batch, sp, d_ops_counts,
+                                  d_script, d_script_len, static_cast<hipStream_t>(stream));
+  if (rc) return fail(VASR_ERR_HIP, "error_ops: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
+  return check_launch("error_ops");
+}
+
+int vasr_nbest_error_counts_i32(const int32_t* d_ids, int64_t width, const int32_t* d_id_len, const int32_t* d_count, int nbest,
+                                const int32_t* d_ref, int64_t ref_width, const int32_t* d_ref_len, int batch,
+                                const int32_t* h_space_ids, int n_space, int32_t* d_slot_counts, int32_t* d_counts,
+                                int32_t* d_slot, vasr_stream stream) {
+  // every refusal comes before a device is touched
+  if (!d_ids || !d_id_len || !d_count || !d_ref || !d_ref_len || !d_slot_counts)
+    return fail(VASR_ERR_INVALID, "nbest_error_counts: NULL pointer");
+  if (batch <= 0 || nbest < 1 || width < 0 || ref_width < 0)
+    return fail(VASR_ERR_INVALID, "nbest_error_counts: batch %d, nbest %d, widths %lld / %lld", batch, nbest, (long long)width,
+                (long long)ref_width);
+  if (n_space < 0 || n_space > kMetricsMaxSpace || (n_space > 0 && !h_space_ids))
+    return fail(VASR_ERR_INVALID, "nbest_error_counts: n_space %d outside 0..%d (or no ids given)", n_space, kMetricsMaxSpace);
+  if ((reinterpret_cast<uintptr_t>(d_slot_counts) | reinterpret_cast<uintptr_t>(d_counts)) & 15)
+    return fail(VASR_ERR_INVALID, "nbest_error_counts: d_slot_counts / d_counts is not 16-byte aligned");
+  if (nbest > kMetricsMaxNbest)
+    return fail(VASR_ERR_UNSUPPORTED, "nbest_error_counts: nbest %d, at most %d", nbest, kMetricsMaxNbest);
+  if (width > kMetricsMaxWidth || ref_width > kMetricsMaxWidth)
+    return fail(VASR_ERR_UNSUPPORTED, "nbest_error_counts: rows of %lld / %lld ids, at most %d per side", (long long)width,
+                (long long)ref_width, kMetricsMaxWidth);
+  SpaceIds sp{};
+  sp.n = n_space;
+  for (int k = 0; k < n_space; ++k) sp.id[k] = h_space_ids[k];
+  const int rc = launch_nbest_error_counts(d_ids, (int)width, d_id_len, d_count, nbest, d_ref, (int)ref_width, d_ref_len, batch,
+                                           sp, d_slot_counts, d_counts, d_slot, static_cast<hipStream_t>(stream));
+  if (rc) return fail(VASR_ERR_HIP, "nbest_error_counts: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
+  return check_launch("nbest_error_counts");
+}
+
 int vasr_class_scores_f32(const float* d_logits, int batch, int num_classes, const int64_t* d_targets, int k,
                           int32_t* d_topk_idx, float* d_topk_val, float* d_topk_prob, int32_t* d_rank, float* d_loss,
                           vasr_stream stream) {

@@ -351,6 +351,18 @@ constexpr int kMetricsMaxSpace = 8;
 struct SpaceIds { int32_t id[kMetricsMaxSpace]; int n; };   // the label ids str.split() separates on
 int launch_error_counts(const int32_t* hyp, int hyp_width, const int32_t* hyp_len, const int32_t* ref, int ref_width,
                         const int32_t* ref_len, int batch, const SpaceIds& sp, int32_t* counts, hipStream_t st);
+// ops [B][8], 32-byte rows at a 16-byte aligned base; script [B][(hyp_width + 1) / 2 + (ref_width + 1) / 2] and script_len [B]
+// both or neither, and with them both widths <= kMetricsMaxScriptWidth (the 2-bit predecessors of the word table sit in LDS)
+constexpr int kMetricsMaxScriptWidth = 1024;
+int launch_error_ops(const int32_t* hyp, int hyp_width, const int32_t* hyp_len, const int32_t* ref, int ref_width,
+                     const int32_t* ref_len, int batch, const SpaceIds& sp, int32_t* ops, int32_t* script, int32_t* script_len,
+                     hipStream_t st);
+// ids [B][nbest][width], id_len [B][nbest], count [B]; ref [B][ref_width] serves every slot of its row; slot_counts
+// [B][nbest][4] 16-byte aligned; counts [B][4] (16-byte aligned) and slot [B][2] may be NULL; nbest <= kMetricsMaxNbest (the grid is batch x nbest)
+constexpr int kMetricsMaxNbest = 65535;
+int launch_nbest_error_counts(const int32_t* ids, int width, const int32_t* id_len, const int32_t* count, int nbest,
+                              const int32_t* ref, int ref_width, const int32_t* ref_len, int batch, const SpaceIds& sp,
+                              int32_t* slot_counts, int32_t* counts, int32_t* slot, hipStream_t st);
 
 // ---- classification scoring (cls_eval.hip) ----
 // per row of logits [B][classes]: the first k classes of the order (value descending, NaN first, lower index first among

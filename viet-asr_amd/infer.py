@@ -109,10 +109,9 @@ class VietASR:
         sigs = [self._to_model_rate(s, sample_rate) for s in signals]
         return self._fused_engine().transcribe_beam(sigs, self.beam.decoder, self.beam.beam_width, row_independent)
 
-    def _walk_manifest(self, manifest_filepath, batch_size, row_independent, after_forward=None):
-        """The entries of a NeMo JSON-lines manifest and their greedy transcripts, in manifest order: sorted by duration, cut
-        into batches of ``batch_size``, two batches in flight (engine.QuartzNetCTC.launch).  after_forward(entries, idx) -> the
-        ``launch`` hook of the batch holding entries ``idx`` (or None)."""
+    def _manifest_batches(self, manifest_filepath, batch_size):
+        """-> (the entries of a NeMo JSON-lines manifest, or of several separated by commas; a generator of (idx, signals): the
+        entries sorted by duration and cut into batches of ``batch_size``, each batch's audio read as it is asked for)."""
         import json
         from . import audio
         entries = []
@@ -120,6 +119,22 @@ class VietASR:
             with open(path, encoding="utf-8") as f:
                 entries += [json.loads(line) for line in f if line.strip()]
         order = sorted(range(len(entries)), key=lambda i: float(entries[i].get("duration", 0.0)))
+
+        def batches():
+            for lo in range(0, len(order), batch_size):
+                idx = order[lo : lo + batch_size]
+                sigs = []
+                for i in idx:
+                    x, sr = audio.read_wav(entries[i]["audio_filepath"])
+                    sigs.append(self._to_model_rate(x, sr))
+                yield idx, sigs
+        return entries, batches()
+
+    def _walk_manifest(self, manifest_filepath, batch_size, row_independent, after_forward=None):
+        """The entries of a NeMo JSON-lines manifest and their greedy transcripts, in manifest order: sorted by duration, cut
+        into batches of ``batch_size``, two batches in flight (engine.QuartzNetCTC.launch).  after_forward(entries, idx) -> the
+        ``launch`` hook of the batch holding entries ``idx`` (or None)."""
+        entries, batches = self._manifest_batches(manifest_filepath, batch_size)
         hyps, pending = [None] * len(entries), []
 
         def collect(job):
@@ -127,12 +142,7 @@ class VietASR:
             for i, t in zip(idx, handle.texts()):
                 hyps[i] = t
 
-        for lo in range(0, len(order), batch_size):
-            idx = order[lo : lo + batch_size]
-            sigs = []
-            for i in idx:
-                x, sr = audio.read_wav(entries[i]["audio_filepath"])
-                sigs.append(self._to_model_rate(x, sr))
+        for idx, sigs in batches:
             hook = after_forward(entries, idx) if after_forward is not None else None
             pending.append((idx, self._fused_engine().launch(sigs, row_independent, hook)))
             if len(pending) == 2:
@@ -160,7 +170,19 @@ class VietASR:
         wer = word_error_rate([hyps[i] for i in scored], [refs[i] for i in scored]) if scored else None
         return hyps, wer
 
-    def evaluate_manifest(self, manifest_filepath, batch_size=64, row_independent=True):
+    def _reference_tokens(self, entries, rows):
+        """The parsed references of ``rows`` as pinned (ref [R,width] i32, ref_len [R] i32): the character parser of
+        ``AudioToTextDataLayer`` drops what is not among the labels."""
+        lab = {c: i for i, c in enumerate(self.labels)}
+        toks = [[lab[c] for c in entries[i]["text"] if c in lab] for i in rows]
+        width = max(1, max(len(t) for t in toks))
+        ref = torch.zeros((len(rows), width), dtype=torch.int32).pin_memory()
+        ref_len = torch.tensor([len(t) for t in toks], dtype=torch.int32).pin_memory()
+        for k, t in enumerate(toks):
+            ref[k, : len(t)] = torch.tensor(t, dtype=torch.int32)
+        return ref, ref_len
+
+    def evaluate_manifest(self, manifest_filepath, batch_size=64, row_independent=True, breakdown=False, nbest=None):
         """``transcribe_manifest``'s walk with WER and CER scored on the device: -> (hyps, ``ErrorRate.compute()``), the
         dict {"wer", "cer", "word_edits", "ref_words", "char_edits", "ref_chars"}.
 
@@ -170,22 +192,27 @@ class VietASR:
         before its ids are copied out: no transcript has to reach the host to be scored, two batches stay in flight, and
         the one synchronisation is the final ``compute``.  Entries without ``text`` are transcribed and not scored.
         ``transcribe_manifest``'s rate is on the raw text: it differs from this "wer" only where a reference contains
-        characters outside the labels."""
-        from .metrics import ErrorRate
-        lab = {c: i for i, c in enumerate(self.labels)}
-        metric = ErrorRate(self.labels)
+        characters outside the labels.
+
+        breakdown=True scores with ``metrics.ErrorBreakdown`` instead: the same six keys with the same values, plus
+        substitutions, deletions, insertions and hits at both levels ("word_sub" ... "char_hits").
+
+        nbest=N (instances built with decoder="beam"; ValueError otherwise) decodes every batch with this instance's beam
+        search (``decode_beams_ids``, N <= beam_width), returns and scores slot 0 -- the beam search's hypothesis, not the
+        greedy one -- and adds "oracle_wer" / "oracle_cer": the rates of the best of the N hypotheses per utterance
+        (``metrics.OracleErrorRate``).  The pipelined ``launch`` hook does not reach the log-probs, so this form is a plain
+        batch loop: one forward pass, one search and one host copy of the transcripts per batch."""
+        from .metrics import ErrorBreakdown, ErrorRate
+        metric = (ErrorBreakdown if breakdown else ErrorRate)(self.labels)
+        if nbest is not None:
+            return self._evaluate_manifest_nbest(manifest_filepath, batch_size, row_independent, metric, int(nbest))
         keep = []                   # pinned reference batches, alive until the copies that read them have run
 
         def after_forward(entries, idx):
             rows = [k for k, i in enumerate(idx) if entries[i].get("text")]
             if not rows:
                 return None
-            toks = [[lab[c] for c in entries[idx[k]]["text"] if c in lab] for k in rows]
-            width = max(1, max(len(t) for t in toks))
-            ref = torch.zeros((len(rows), width), dtype=torch.int32).pin_memory()
-            ref_len = torch.tensor([len(t) for t in toks], dtype=torch.int32).pin_memory()
-            for k, t in enumerate(toks):
-                ref[k, : len(t)] = torch.tensor(t, dtype=torch.int32)
+            ref, ref_len = self._reference_tokens(entries, [idx[k] for k in rows])
             sel = None if len(rows) == len(idx) else torch.tensor(rows, dtype=torch.int64).pin_memory()
             keep.append((ref, ref_len, sel))
 
@@ -200,6 +227,40 @@ class VietASR:
 
         _, hyps = self._walk_manifest(manifest_filepath, batch_size, row_independent, after_forward)
         return hyps, metric.compute()
+
+    def _evaluate_manifest_nbest(self, manifest_filepath, batch_size, row_independent, metric, nbest):
+        from .engine import _pcm_to_float
+        from .metrics import OracleErrorRate
+        if self.mode != "beam":
+            raise ValueError("nbest needs an instance constructed with decoder='beam'")
+        eng, dec, oracle = self._fused_engine(), self.beam.decoder, OracleErrorRate(self.labels)
+        entries, batches = self._manifest_batches(manifest_filepath, batch_size)
+        hyps = [None] * len(entries)
+        for idx, sigs in batches:
+            lens = [len(s) for s in sigs]
+            if row_independent and min(lens) <= eng.frontend["n_fft"] // 2:
+                raise ValueError(f"row-independent batching needs more than n_fft/2 = {eng.frontend['n_fft'] // 2} samples "
+                                 f"per signal (got {min(lens)})")
+            batch = np.zeros((len(sigs), max(lens)), dtype=np.float32)
+            for k, s in enumerate(sigs):
+                batch[k, : lens[k]] = _pcm_to_float(s)
+            r = eng.forward(torch.from_numpy(batch).to(eng.device), torch.tensor(lens, device=eng.device), want_logp=True,
+                            want_pred=False, row_independent=row_independent)
+            own = [eng.frames(n)[1] for n in lens] if row_independent else None
+            ids, id_len, count, _, _ = dec.decode_beams_ids(r["logp"], self.beam.beam_width, nbest, frames=own)
+            rows = [k for k, i in enumerate(idx) if entries[i].get("text")]
+            if rows:
+                ref, ref_len = self._reference_tokens(entries, [idx[k] for k in rows])
+                ref, ref_len = ref.to(eng.device), ref_len.to(eng.device)
+                sel = torch.tensor(rows, dtype=torch.int64, device=eng.device)
+                s_ids, s_len, s_count = ids.index_select(0, sel), id_len.index_select(0, sel), count.index_select(0, sel)
+                metric.update(s_ids[:, 0], s_len[:, 0], ref, ref_len)
+                oracle.update(s_ids, s_len, s_count, ref, ref_len)
+            for i, t in zip(idx, eng.texts(ids[:, 0], id_len[:, 0])):
+                hyps[i] = t
+        res, best = metric.compute(), oracle.compute()
+        res["oracle_wer"], res["oracle_cer"] = best["oracle_wer"], best["oracle_cer"]
+        return hyps, res
 
     def launch_batch(self, signals, sample_rate=None, row_independent=False):
         """Asynchronous ``transcribe_batch``: returns a handle at once, ``.texts()`` waits (engine.QuartzNetCTC.launch)."""

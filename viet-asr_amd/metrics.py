@@ -6,6 +6,9 @@ Reference: nemo/collections/asr/metrics.py:30-63 (``word_error_rate``, both ``us
 ``stages.error_counts`` (vasr_error_counts_i32, csrc/metrics.hip); this module only sums four integers on the device and
 divides them once on the host.  ``data_layer.word_error_rate`` is the same metric on host strings; the two differ only
 where a reference holds characters outside the labels, which the character parser drops before the tokens are made.
+``ErrorBreakdown`` splits the edits into substitutions, deletions and insertions (``stages.error_ops``, vasr_error_ops_i32),
+``word_alignment`` / ``confusion_pairs`` report which words were confused, and ``OracleErrorRate`` scores the best hypothesis
+of the beam search's n-best list (``stages.nbest_error_counts``, vasr_nbest_error_counts_i32).
 
 ``classification_accuracy`` (metrics.py:66-99) and ``TopKAccuracy`` (the running form of
 process_classification_evaluation_batch / _epoch, helpers.py:215-288) rest on ``stages.classification_scores``
@@ -71,6 +74,114 @@ class ErrorRate:
             raise _lib.VasrError(f"{host[4]} scored rows carried a negative length (the beam search's id_len = -1 overflow "
                                  "report): no error rate is returned for them")
         return _rates(host[:4])
+
+
+OPS_KEYS = ("word_sub", "word_del", "word_ins", "word_hits", "char_sub", "char_del", "char_ins", "char_hits")
+
+
+class ErrorBreakdown:
+    """``ErrorRate`` with the edits split into substitutions, deletions and insertions, and the hits, at both levels
+    (``stages.error_ops``, the alignment rule of include/vasr.h).  ``update`` enqueues and never synchronises; ``compute`` is
+    the one sync.  The six keys it shares with ``ErrorRate`` carry the same values: edits = sub + del + ins, reference
+    count = hits + sub + del."""
+
+    def __init__(self, labels):
+        self.space_ids = space_ids(labels)
+        self._acc = None          # int64 [9]: the eight sums + the number of rows that came back as -1
+
+    def update(self, ids, id_len, transcripts, transcript_length):
+        """Arguments as ``ErrorRate.update``; all on the device, enqueued on the current stream."""
+        self._add(stages.error_ops(ids, id_len, transcripts, transcript_length, self.space_ids))
+
+    def _add(self, ops):
+        """ops [B,8] i32 of ``stages.error_ops`` -> the accumulator, without a host round trip."""
+        sums = ops.clamp_min(0).sum(dim=0, dtype=torch.int64)
+        row = torch.cat([sums, (ops[:, 0] < 0).sum(dtype=torch.int64).reshape(1)])
+        self._acc = row if self._acc is None else self._acc + row
+
+    def reset(self):
+        self._acc = None
+
+    def compute(self, reduce=False, group=None):
+        """-> ``ErrorRate.compute``'s six keys + "word_sub", "word_del", "word_ins", "word_hits", "char_sub", "char_del",
+        "char_ins", "char_hits".  reduce=True sums over the process group first.  Raises VasrError on -1 rows."""
+        acc = self._acc if self._acc is not None else torch.zeros(9, dtype=torch.int64)
+        if reduce:
+            acc = dist.all_reduce_counts(acc, group)
+        host = [int(v) for v in acc.cpu().tolist()]
+        if host[8]:
+            raise _lib.VasrError(f"{host[8]} scored rows carried a negative length (the beam search's id_len = -1 overflow "
+                                 "report): no error rate is returned for them")
+        ws, wd, wi, wh, cs, cd, ci, ch = host[:8]
+        out = _rates([ws + wd + wi, wh + ws + wd, cs + cd + ci, ch + cs + cd])
+        out.update(zip(OPS_KEYS, host[:8]))
+        return out
+
+
+class OracleErrorRate:
+    """Running oracle WER / CER of n-best lists: per utterance the hypothesis with the fewest word edits, and (independently)
+    the one with the fewest character edits, among the slots the search filled (``stages.nbest_error_counts``).  The gap to
+    the 1-best ``ErrorRate`` is what rescoring the list could gain at most.  ``update`` enqueues and never synchronises."""
+
+    def __init__(self, labels):
+        self.space_ids = space_ids(labels)
+        self._acc = None          # as ErrorRate's
+
+    def update(self, nbest_ids, nbest_len, count, transcripts, transcript_length):
+        """nbest_ids [B,N,T] / nbest_len [B,N] / count [B]: ``DeviceBeamDecoder.decode_beams_ids``' first three results;
+        transcripts [B,Tr] / transcript_length [B].  All on the device; enqueued on the current stream."""
+        self._add(stages.nbest_error_counts(nbest_ids, nbest_len, count, transcripts, transcript_length, self.space_ids)["counts"])
+
+    _add = ErrorRate._add
+    reset = ErrorRate.reset
+
+    def compute(self, reduce=False, group=None):
+        """-> {"oracle_wer", "oracle_cer", "word_edits", "ref_words", "char_edits", "ref_chars"} (the edits are the minima's
+        sums).  Raises VasrError when a row could not be scored (a negative length, no filled slot)."""
+        r = ErrorRate.compute(self, reduce, group)
+        return dict(oracle_wer=r["wer"], oracle_cer=r["cer"], word_edits=r["word_edits"], ref_words=r["ref_words"],
+                    char_edits=r["char_edits"], ref_chars=r["ref_chars"])
+
+
+OP_NAMES = ("hit", "sub", "del", "ins")
+
+
+def word_alignment(ids, id_len, transcripts, transcript_length, labels):
+    """The word alignment of every (hypothesis, reference) row: per row a list of (op, hyp_word | None, ref_word | None), op
+    in "hit", "sub", "del", "ins", first word to last, by the alignment rule of include/vasr.h (``stages.error_ops`` with
+    script=True: rows of at most 1024 ids).  Words are strings over ``labels``.  For reporting: this call synchronises (the
+    scripts and the ids are copied to the host).  Raises VasrError for a row with a negative length."""
+    labels = list(labels)
+    sp = space_ids(labels)
+    _, script, script_len = stages.error_ops(ids, id_len, transcripts, transcript_length, sp, script=True)
+    script, script_len = script.cpu().numpy(), script_len.cpu().numpy()
+    if (script_len < 0).any():
+        raise _lib.VasrError("rows %s carried a negative length (the beam search's id_len = -1 overflow report): no alignment "
+                             "is returned for them" % (script_len < 0).nonzero()[0].tolist())
+    hyp, hyp_n = ids.cpu().numpy(), id_len.cpu().numpy()
+    ref, ref_n = transcripts.cpu().numpy(), transcript_length.cpu().numpy()
+    rows = []
+    for b in range(script.shape[0]):
+        h = "".join(labels[c] for c in hyp[b, : hyp_n[b]].tolist()).split()
+        r = "".join(labels[c] for c in ref[b, : ref_n[b]].tolist()).split()
+        i = j = 0
+        row = []
+        for code in script[b, : script_len[b]].tolist():
+            hw = rw = None
+            if code != 2:
+                hw, i = h[i], i + 1
+            if code != 3:
+                rw, j = r[j], j + 1
+            row.append((OP_NAMES[code], hw, rw))
+        assert i == len(h) and j == len(r), (b, i, len(h), j, len(r))
+        rows.append(row)
+    return rows
+
+
+def confusion_pairs(alignments):
+    """``word_alignment``'s rows -> collections.Counter of (ref_word, hyp_word) over the substitutions."""
+    from collections import Counter
+    return Counter((rw, hw) for row in alignments for op, hw, rw in row if op == "sub")
 
 
 def word_error_rate_ids(ids, id_len, transcripts, transcript_length, labels, use_cer=False):

@@ -135,12 +135,21 @@ def ctc_collapse(predictions, blank_id):
     return ids, n
 
 
-def error_counts(hyp_ids, hyp_len, ref_ids, ref_len, space_ids):
-    """word_error_rate (metrics.py:30-63) per row, both use_cer settings -> counts [B,4] i32 =
-    {word_edits, ref_words, char_edits, ref_chars} (vasr_error_counts_i32).  hyp_ids [B,Th] / hyp_len [B]: collapsed ids
-    (greedy or beam); ref_ids [B,Tr] / ref_len [B]: the data layer's transcripts / transcript_length -- int64 is cast on
-    the device.  space_ids: the label ids str.split() separates on (host integers, at most 8).  Enqueued on the current
-    stream; nothing synchronises.  A row with a negative length comes back as four -1."""
+def _space_array(space_ids):
+    sp = [int(s) for s in space_ids]
+    return (_lib.C.c_int32 * max(len(sp), 1))(*sp), len(sp)
+
+
+def _i32_rows(t, dev):
+    """-> (t as a contiguous int32 tensor on dev, the tensor whose data_ptr() to pass: a stand-in where t has no storage)"""
+    x = t.to(device=dev, dtype=torch.int32).contiguous()
+    return x, (x if x.numel() else torch.empty(1, dtype=torch.int32, device=dev))
+
+
+def _pair_args(hyp_ids, hyp_len, ref_ids, ref_len, space_ids):
+    """The arguments ``error_counts`` and ``error_ops`` share, checked and cast on the device -> (B, dev, h, hp, hn, r, rp, rn,
+    arr, n_space): h / r the int32 id batches, hp / rp the tensors whose data_ptr() to pass (a [B, 0] tensor has no storage to
+    point at: the library wants a pointer it never reads), hn / rn the int32 lengths, arr the host array of space ids."""
     _need_cuda(hyp_ids, hyp_len, ref_ids, ref_len)
     if hyp_ids.dim() != 2 or ref_ids.dim() != 2:
         raise ValueError(f"hyp_ids / ref_ids must be [B, T], got {tuple(hyp_ids.shape)} / {tuple(ref_ids.shape)}")
@@ -149,18 +158,76 @@ def error_counts(hyp_ids, hyp_len, ref_ids, ref_len, space_ids):
         raise ValueError(f"batch sizes differ: ids {tuple(hyp_ids.shape)} / {tuple(ref_ids.shape)}, lengths "
                          f"{tuple(hyp_len.shape)} / {tuple(ref_len.shape)}")
     dev = hyp_ids.device
-    h, r = hyp_ids.to(torch.int32).contiguous(), ref_ids.to(device=dev, dtype=torch.int32).contiguous()
+    (h, hp), (r, rp) = _i32_rows(hyp_ids, dev), _i32_rows(ref_ids, dev)
     hn, rn = hyp_len.to(torch.int32).contiguous(), ref_len.to(device=dev, dtype=torch.int32).contiguous()
-    # a [B, 0] tensor has no storage to point at: the library wants a pointer it never reads
-    hp = h if h.numel() else torch.empty(1, dtype=torch.int32, device=dev)
-    rp = r if r.numel() else torch.empty(1, dtype=torch.int32, device=dev)
-    sp = [int(s) for s in space_ids]
-    arr = (_lib.C.c_int32 * max(len(sp), 1))(*sp)
+    arr, ns = _space_array(space_ids)
+    return B, dev, h, hp, hn, r, rp, rn, arr, ns
+
+
+def error_counts(hyp_ids, hyp_len, ref_ids, ref_len, space_ids):
+    """word_error_rate (metrics.py:30-63) per row, both use_cer settings -> counts [B,4] i32 =
+    {word_edits, ref_words, char_edits, ref_chars} (vasr_error_counts_i32).  hyp_ids [B,Th] / hyp_len [B]: collapsed ids
+    (greedy or beam); ref_ids [B,Tr] / ref_len [B]: the data layer's transcripts / transcript_length -- int64 is cast on
+    the device.  space_ids: the label ids str.split() separates on (host integers, at most 8).  Enqueued on the current
+    stream; nothing synchronises.  A row with a negative length comes back as four -1."""
+    B, dev, h, hp, hn, r, rp, rn, arr, ns = _pair_args(hyp_ids, hyp_len, ref_ids, ref_len, space_ids)
     counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().vasr_error_counts_i32(hp.data_ptr(), h.shape[1], hn.data_ptr(), rp.data_ptr(), r.shape[1],
-                                                    rn.data_ptr(), B, arr, len(sp), counts.data_ptr(), _st()))
+                                                    rn.data_ptr(), B, arr, ns, counts.data_ptr(), _st()))
     return counts
+
+
+def error_ops(hyp_ids, hyp_len, ref_ids, ref_len, space_ids, script=False):
+    """``error_counts``' two distances split by the alignment rule of include/vasr.h (vasr_error_ops_i32) -> ops [B,8] i32 =
+    {word_sub, word_del, word_ins, word_hits, char_sub, char_del, char_ins, char_hits}; with script=True ->
+    (ops, script [B,L] i32, script_len [B] i32): the word-level edit script of every row, op codes 0 hit / 1 substitution /
+    2 deletion / 3 insertion over script[b, :script_len[b]], L = (Th + 1) // 2 + (Tr + 1) // 2 (entries behind a length are
+    not written); both widths must then be <= 1024 (NotImplementedError beyond).  Arguments as ``error_counts``.  Enqueued
+    on the current stream; nothing synchronises.  A row with a negative length comes back as eight -1 (script_len -1)."""
+    B, dev, h, hp, hn, r, rp, rn, arr, ns = _pair_args(hyp_ids, hyp_len, ref_ids, ref_len, space_ids)
+    ops = torch.empty((B, 8), dtype=torch.int32, device=dev)
+    steps = steps_len = None
+    if script:
+        steps = torch.empty((B, max(1, (h.shape[1] + 1) // 2 + (r.shape[1] + 1) // 2)), dtype=torch.int32, device=dev)
+        steps_len = torch.empty((B,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().vasr_error_ops_i32(hp.data_ptr(), h.shape[1], hn.data_ptr(), rp.data_ptr(), r.shape[1],
+                                                 rn.data_ptr(), B, arr, ns, ops.data_ptr(),
+                                                 steps.data_ptr() if script else None,
+                                                 steps_len.data_ptr() if script else None, _st()))
+    return (ops, steps, steps_len) if script else ops
+
+
+def nbest_error_counts(ids, id_len, count, ref_ids, ref_len, space_ids):
+    """``error_counts`` of every slot of an n-best list against the row's one reference, and the best slot per row
+    (vasr_nbest_error_counts_i32).  ids [B,N,T] / id_len [B,N] / count [B]: ``DeviceBeamDecoder.decode_beams_ids``' first
+    three results; ref_ids [B,Tr] / ref_len [B]: the transcripts, one row per utterance.  -> dict(slot_counts [B,N,4] i32 --
+    four -1 in the slots behind count --, counts [B,4] i32 = {min word_edits, ref_words, min char_edits, ref_chars} over the
+    filled slots (``error_counts``' layout: it accumulates the same way), slot [B,2] i32: the slots of the two minima, the
+    lower among equals).  A row that cannot be scored (a negative length, count < 1) is -1 throughout.  Enqueued on the
+    current stream; nothing synchronises."""
+    _need_cuda(ids, id_len, count, ref_ids, ref_len)
+    if ids.dim() != 3 or ref_ids.dim() != 2:
+        raise ValueError(f"ids must be [B, N, T] and ref_ids [B, T], got {tuple(ids.shape)} / {tuple(ref_ids.shape)}")
+    B, N = ids.shape[0], ids.shape[1]
+    if ref_ids.shape[0] != B or tuple(id_len.shape) != (B, N) or tuple(count.shape) != (B,) or tuple(ref_len.shape) != (B,):
+        raise ValueError(f"shapes differ: ids {tuple(ids.shape)}, id_len {tuple(id_len.shape)}, count {tuple(count.shape)}, "
+                         f"ref_ids {tuple(ref_ids.shape)}, ref_len {tuple(ref_len.shape)}")
+    dev = ids.device
+    (h, hp), (r, rp) = _i32_rows(ids, dev), _i32_rows(ref_ids, dev)
+    hn, cn = id_len.to(torch.int32).contiguous(), count.to(torch.int32).contiguous()
+    rn = ref_len.to(device=dev, dtype=torch.int32).contiguous()
+    arr, ns = _space_array(space_ids)
+    slot_counts = torch.empty((B, N, 4), dtype=torch.int32, device=dev)
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    slot = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().vasr_nbest_error_counts_i32(hp.data_ptr(), h.shape[2], hn.data_ptr() if hn.numel() else None,
+                                                          cn.data_ptr(), N, rp.data_ptr(), r.shape[1], rn.data_ptr(), B,
+                                                          arr, ns, slot_counts.data_ptr() if N else None, counts.data_ptr(),
+                                                          slot.data_ptr(), _st()))
+    return dict(slot_counts=slot_counts, counts=counts, slot=slot)
 
 
 def classification_scores(logits, targets=None, k=0, want_prob=False, want_loss=True):
