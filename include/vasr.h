@@ -347,6 +347,39 @@ VASR_API int vasr_class_scores_f32(const float* d_logits, int batch, int num_cla
                                    int32_t* d_topk_idx, float* d_topk_val, float* d_topk_prob, int32_t* d_rank,
                                    float* d_loss, vasr_stream stream);
 
+/* The CTC forward score, per row: nn.CTCLoss(blank, reduction='none', zero_infinity=False) as CTCLossNM builds it
+ * (nemo/collections/asr/losses.py) -- the reference's Evaluation_Loss for the ASR path, and minus log P(transcript | audio) of
+ * any transcript.  Forward only: no alignment, no gradient.
+ *   d_logp [B][frames][num_classes] f32 contiguous (d_logp of the calls below), d_frames [B] i32: the row's own frames,
+ *   d_tgt [B][tgt_width] i32, d_tgt_len [B] i32 (the data layer's transcripts / transcript_length)
+ *   -> d_loss [B] f32 = -log sum_paths prod_t p(t, path_t) over row b's own T = d_frames[b] frames and L = d_tgt_len[b] ids.
+ * The formula, in float32 log space with expf / logf (no fast intrinsics).  The extended sequence e has S = 2 L + 1 states
+ * (blank, y1, blank, ..., yL, blank).
+ *   alpha(0, 0) = logp[0][blank], alpha(0, 1) = logp[0][y1], alpha(0, s) = -inf for s >= 2;
+ *   for t >= 1:  x0 = alpha(t-1, s), x1 = alpha(t-1, s-1), and x2 = alpha(t-1, s-2) only where e_s is not blank and
+ *                e_s != e_(s-2); a term that does not exist (s-1 < 0, no x2) counts as -inf;
+ *                lse(x0, x1, x2) = m + logf((expf(x0 - m) + expf(x1 - m)) + expf(x2 - m)) with m the largest of them -- the
+ *                terms in the fixed order s, s-1, s-2 -- and -inf where m = -inf;
+ *                alpha(t, s) = lse(x0, x1, x2) + logp[t][e_s];
+ *   d_loss[b] = -lse(alpha(T-1, S-1), alpha(T-1, S-2), -inf)   (of the only state when L = 0).
+ * expf(-inf) adds an exact zero, so a sum of two terms and a sum of three with one -inf have the same bits.  A -inf
+ * log-prob is legal input and never produces a NaN.  What torch defines comes out as torch gives it: a row without a path
+ * (T < L + the number of adjacent equal label pairs; T == 0 with L > 0) has loss +inf; L == 0 gives minus the sum of the
+ * blank's log-probs over the row's frames, taken frame by frame; T == 0 and L == 0 give 0.
+ * This library's own conventions, where torch raises or does not check: lengths are clamped into [0, frames] and
+ * [0, tgt_width]; a NEGATIVE length on either side gives a quiet NaN for that row; a target id INSIDE the row's length that
+ * is < 0, >= num_classes or == blank gives a quiet NaN for that row -- NaN means "never a plausible number", the float
+ * counterpart of vasr_error_counts_i32's -1 rows.  Nothing behind a row's lengths is ever read: neither frames >= d_frames[b]
+ * nor ids >= d_tgt_len[b].  A state's value depends on its three predecessors alone and the order above is fixed, so a row's
+ * loss is bit-identical whatever batch, `frames` or `tgt_width` it is launched with.  No atomics, no workspace, no handle.
+ * NULL pointers, batch <= 0, frames < 0, tgt_width < 0, num_classes < 2 and blank outside [0, num_classes) return
+ * VASR_ERR_INVALID; tgt_width > 4096 (the limit of vasr_error_counts_i32) returns VASR_ERR_UNSUPPORTED with the limit in
+ * vasr_last_error() -- all before a device is touched.  frames == 0 and tgt_width == 0 are legal.  One workgroup per row, the
+ * alpha vector double-buffered in LDS (64 KB at tgt_width 4096); DESIGN section 7d has the measured times.  (ABI 8) */
+VASR_API int vasr_ctc_loss_f32(const float* d_logp, const int32_t* d_frames, int batch, int64_t frames, int num_classes,
+                               int blank, const int32_t* d_tgt, int64_t tgt_width, const int32_t* d_tgt_len,
+                               float* d_loss /* [B] */, vasr_stream stream);
+
 /* ---- the whole path in one call (the fast path bench.py times) ------------------------ */
 /* wav -> mel -> encoder -> CTC head -> log-softmax/argmax -> collapse, all intermediates in
  * the workspace (padded time stride, no port tensors materialised).

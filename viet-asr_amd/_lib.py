@@ -60,6 +60,7 @@ SIGNATURES = {
     "vasr_nbest_error_counts_i32": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, _P, C.c_int64, _P, C.c_int, C.POINTER(C.c_int32),
                                               C.c_int, _P, _P, _P, _P]),
     "vasr_class_scores_f32": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "vasr_ctc_loss_f32": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, _P, _P]),
     "vasr_transcribe_greedy_f32": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P,
                                              C.c_size_t, _P]),
     "vasr_transcribe_greedy_pcm16": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P,

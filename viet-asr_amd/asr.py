@@ -13,15 +13,15 @@ import torch
 import torch.nn as nn
 
 from . import _lib, stages
-from .core import (AcousticEncodedRepresentation, AudioSignal, DataLayerNM, DeviceType, LengthsType,
-                   LogitsType, LogprobsType, MelSpectrogramType, NeuralType, NonTrainableNM, PredictionsType,
+from .core import (AcousticEncodedRepresentation, AudioSignal, DataLayerNM, DeviceType, LabelsType, LengthsType,
+                   LogitsType, LogprobsType, LossType, MelSpectrogramType, NeuralType, NonTrainableNM, PredictionsType,
                    SpectrogramType, TrainableNM)
 from .engine import (activation_from_config, blocks_from_config, check_dense_layout, norm_from_config, groups_from_config,
                      se_from_config)
 from .frontend_tables import frontend_description
 
 __all__ = ["AudioToMelSpectrogramPreprocessor", "CropOrPadSpectrogramAugmentation", "JasperEncoder", "JasperDecoderForCTC",
-           "JasperDecoderForClassification", "GreedyCTCDecoder", "BeamSearchDecoderWithLM", "AudioDataLayer"]
+           "JasperDecoderForClassification", "GreedyCTCDecoder", "BeamSearchDecoderWithLM", "AudioDataLayer", "CTCLossNM"]
 
 
 def _no_gpu():
@@ -379,6 +379,33 @@ class GreedyCTCDecoder(TrainableNM):
 
     def forward(self, log_probs):
         return stages.greedy_argmax(log_probs)
+
+
+class CTCLossNM(NonTrainableNM):
+    """nemo/collections/asr/losses.py:10-61, forward only: the loss an evaluation reports next to WER and CER
+    (``Evaluation_Loss``, helpers.py:146-204).  num_classes: the number of labels without the blank, which is id
+    ``num_classes``.  ``forward`` returns the reference's ``torch.mean(loss)`` of the per-row ``nn.CTCLoss(reduction='none')``
+    values -- not divided by the target lengths -- as a 0-dim float32 device tensor (``stages.ctc_loss``,
+    vasr_ctc_loss_f32).  The result carries no graph: there is no backward pass, training stays out of scope (DESIGN.md
+    section 8)."""
+
+    @property
+    def input_ports(self):
+        return {"log_probs": NeuralType(("B", "T", "D"), LogprobsType()),
+                "targets": NeuralType(("B", "T"), LabelsType()),
+                "input_length": NeuralType(tuple("B"), LengthsType()),
+                "target_length": NeuralType(tuple("B"), LengthsType())}
+
+    @property
+    def output_ports(self):
+        return {"loss": NeuralType(elements_type=LossType())}
+
+    def __init__(self, num_classes):
+        super().__init__()
+        self._blank = int(num_classes)
+
+    def forward(self, log_probs, targets, input_length, target_length):
+        return stages.ctc_loss(log_probs, input_length, targets, target_length, self._blank).mean(dtype=torch.float32)
 
 
 class BeamSearchDecoderWithLM(NonTrainableNM):

@@ -122,6 +122,14 @@ class LogitsType(ElementType):
     pass
 
 
+class LabelsType(ElementType):
+    pass
+
+
+class LossType(ElementType):
+    pass
+
+
 class NeuralType:
     """axes ('B','D','T') + element type (neural_types/neural_type.py:34-187)."""
 

@@ -1718,6 +1718,22 @@ int vasr_class_scores_f32(const float* d_logits, int batch, int num_classes, con
   return check_launch("class_scores");
 }
 
+int vasr_ctc_loss_f32(const float* d_logp, const int32_t* d_frames, int batch, int64_t frames, int num_classes, int blank,
+                      const int32_t* d_tgt, int64_t tgt_width, const int32_t* d_tgt_len, float* d_loss, vasr_stream stream) {
+  // every refusal comes before a device is touched
+  if (!d_logp || !d_frames || !d_tgt || !d_tgt_len || !d_loss) return fail(VASR_ERR_INVALID, "ctc_loss: NULL pointer");
+  if (batch <= 0 || frames < 0 || tgt_width < 0)
+    return fail(VASR_ERR_INVALID, "ctc_loss: batch %d, frames %lld, tgt_width %lld", batch, (long long)frames, (long long)tgt_width);
+  if (num_classes < 2 || blank < 0 || blank >= num_classes)
+    return fail(VASR_ERR_INVALID, "ctc_loss: num_classes %d (at least 2), blank %d outside [0, num_classes)", num_classes, blank);
+  if (tgt_width > kCtcLossMaxWidth)
+    return fail(VASR_ERR_UNSUPPORTED, "ctc_loss: targets of %lld ids, at most %d", (long long)tgt_width, kCtcLossMaxWidth);
+  const int rc = launch_ctc_loss(d_logp, d_frames, batch, frames, num_classes, blank, d_tgt, (int)tgt_width, d_tgt_len, d_loss,
+                                 static_cast<hipStream_t>(stream));
+  if (rc) return fail(VASR_ERR_HIP, "ctc_loss: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
+  return check_launch("ctc_loss");
+}
+
 // One contiguous slice of the batch through the whole path on one stream.
 static int transcribe_part(vasr_handle* h, const void* d_wav, bool pcm16, const int64_t* d_len, int batch, int64_t samples,
                            int64_t* d_pred, int32_t* d_ids, int32_t* d_id_len, float* d_logp, float* d_enc_len,

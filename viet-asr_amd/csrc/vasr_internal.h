@@ -374,6 +374,18 @@ constexpr int kClassScoresMaxK = 16;
 int launch_class_scores(const float* logits, int batch, int classes, const int64_t* targets, int k, int32_t* topk_idx,
                         float* topk_val, float* topk_prob, int32_t* rank, float* loss, hipStream_t st);
 
+// ---- CTC forward score (ctc_loss.hip) ----
+// per row -log P(tgt | logp) over the row's own frames and ids (include/vasr.h has the formula and the conventions); logp
+// [B][frames][classes], frames_in / tgt_len [B], tgt [B][tgt_width], loss [B]; one workgroup of kCtcLossLanes per row, lane l
+// owning the states l, l + kCtcLossLanes, ...: kCtcLossNarrowSlots of them per lane while 2 * tgt_width + 1 fits, otherwise
+// kCtcLossWideSlots; the caller checks tgt_width <= kCtcLossMaxWidth; returns 0 or a hipError_t
+constexpr int kCtcLossMaxWidth = 4096;
+constexpr int kCtcLossLanes = 256;
+constexpr int kCtcLossNarrowSlots = 4;
+constexpr int kCtcLossWideSlots = 33;
+int launch_ctc_loss(const float* logp, const int32_t* frames_in, int batch, int64_t frames, int classes, int blank,
+                    const int32_t* tgt, int tgt_width, const int32_t* tgt_len, float* loss, hipStream_t st);
+
 // ---- audio ingest (audio.hip) ----
 void launch_pcm16_to_f32(const short* in, int64_t n, float* out, hipStream_t st);
 void launch_resample(const float* x, int64_t ld_in, const int64_t* len_in, int batch, const float* table, int nwin,

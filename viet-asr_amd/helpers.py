@@ -5,6 +5,10 @@ collapse runs on the device (vasr_ctc_collapse: ballot + popcount compaction, on
 utterance) and only the id -> label join happens on the host.  Like the reference it walks ALL T'
 frames, including padded ones (quirk Q4).
 
+Evaluation of the CTC path (helpers.py:128-212): ``process_evaluation_batch`` / ``process_evaluation_epoch`` /
+``post_process_transcripts`` keep the reference's signatures, ``global_vars`` keys and returned dict.  The batch's loss is what
+``asr.CTCLossNM`` (or ``stages.ctc_loss``) computed on the device; it stays a device scalar until the epoch function.
+
 Classification (helpers.py:81-113, 215-288): the three functions keep the reference's signatures and ``global_vars`` keys
 and take their top-k hits from ``stages.classification_scores``; the per-batch entries stay device tensors until the epoch
 function, which is the one place that synchronises.
@@ -37,6 +41,62 @@ def post_process_predictions(predictions, labels):
     for prediction in predictions:
         results += ctc_decoder_predictions_tensor(prediction, labels=labels)
     return results
+
+
+def post_process_transcripts(transcript_list, transcript_len_list, labels):
+    """helpers.py:211-212 -> __gather_transcripts (:128-143): lists of [B,T] id tensors and [B] lengths (any device) -> flat
+    list of strings, every row over its own length.  One host copy per tensor."""
+    results = []
+    for t, ln in zip(transcript_list, transcript_len_list):
+        ids, n = torch.as_tensor(t).long().cpu().numpy(), torch.as_tensor(ln).long().cpu().numpy()
+        results += ["".join(labels[c] for c in ids[b, : n[b]]) for b in range(ids.shape[0])]
+    return results
+
+
+def process_evaluation_batch(tensors, global_vars, labels):
+    """Counterpart of helpers.py:146-172: one batch into the running lists of ``global_vars`` -- ``EvalLoss`` (the mean of
+    the batch's loss tensors), ``predictions`` and ``transcripts`` (strings) and ``logits``.  tensors: lists of tensors under
+    keys matched by prefix, in the reference's order of precedence: ``loss*`` (what ``asr.CTCLossNM`` returned), ``predictions*``
+    ([B,T'] greedy predictions, collapsed on the device), ``transcript_length*``, ``transcript*`` and ``output*``.  The loss
+    entry stays a device scalar: nothing synchronises on it before the epoch function."""
+    for key in ("EvalLoss", "predictions", "transcripts", "logits"):
+        global_vars.setdefault(key, [])
+    transcript_list = transcript_len_list = None
+    for kv, v in tensors.items():
+        if kv.startswith("loss"):
+            global_vars["EvalLoss"] += [torch.mean(torch.stack([torch.as_tensor(x) for x in v]))]
+        elif kv.startswith("predictions"):
+            global_vars["predictions"] += post_process_predictions(v, labels)
+        elif kv.startswith("transcript_length"):
+            transcript_len_list = v
+        elif kv.startswith("transcript"):
+            transcript_list = v
+        elif kv.startswith("output"):
+            global_vars["logits"] += list(v)
+    if transcript_list is None or transcript_len_list is None:
+        raise ValueError("tensors must hold the transcripts and their lengths (keys starting with 'transcript' and "
+                         "'transcript_length')")
+    global_vars["transcripts"] += post_process_transcripts(transcript_list, transcript_len_list, labels)
+
+
+def process_evaluation_epoch(global_vars, eval_metric="WER", tag=None):
+    """Counterpart of helpers.py:175-204: ``Evaluation_Loss`` (``Evaluation_Loss_{tag}`` with a tag) -- the float32 mean of
+    the batch means in ``EvalLoss`` --, ``Evaluation_Valid_WER`` and ``Evaluation_Valid_CER`` over the gathered strings.  Both
+    rates are always returned; eval_metric is only checked ('WER' or 'CER', ValueError otherwise), as there.  The one place
+    that synchronises on the losses."""
+    from .data_layer import word_error_rate
+    eloss = torch.stack([torch.as_tensor(v, dtype=torch.float32).cpu() for v in global_vars["EvalLoss"]]).mean().item()
+    hypotheses, references = global_vars["predictions"], global_vars["transcripts"]
+    eval_metric = eval_metric.upper()
+    if eval_metric not in {"WER", "CER"}:
+        raise ValueError("eval_metric must be 'WER' or 'CER'")
+    wer = word_error_rate(hypotheses, references, use_cer=False)
+    cer = word_error_rate(hypotheses, references, use_cer=True)
+    logging.info("==========>>>>>>Evaluation Loss%s: %s", "" if tag is None else f" {tag}", eloss)
+    logging.info("==========>>>>>>Evaluation Valid WER: %5.2f%%", wer * 100)
+    logging.info("==========>>>>>>Evaluation Valid CER: %5.2f%%", cer * 100)
+    return {"Evaluation_Loss" if tag is None else f"Evaluation_Loss_{tag}": eloss, "Evaluation_Valid_WER": wer,
+            "Evaluation_Valid_CER": cer}
 
 
 def _k_list(eval_metric):

@@ -182,7 +182,8 @@ class VietASR:
             ref[k, : len(t)] = torch.tensor(t, dtype=torch.int32)
         return ref, ref_len
 
-    def evaluate_manifest(self, manifest_filepath, batch_size=64, row_independent=True, breakdown=False, nbest=None):
+    def evaluate_manifest(self, manifest_filepath, batch_size=64, row_independent=True, breakdown=False, nbest=None,
+                          eval_loss=False):
         """``transcribe_manifest``'s walk with WER and CER scored on the device: -> (hyps, ``ErrorRate.compute()``), the
         dict {"wer", "cer", "word_edits", "ref_words", "char_edits", "ref_chars"}.
 
@@ -201,9 +202,22 @@ class VietASR:
         search (``decode_beams_ids``, N <= beam_width), returns and scores slot 0 -- the beam search's hypothesis, not the
         greedy one -- and adds "oracle_wer" / "oracle_cer": the rates of the best of the N hypotheses per utterance
         (``metrics.OracleErrorRate``).  The pipelined ``launch`` hook does not reach the log-probs, so this form is a plain
-        batch loop: one forward pass, one search and one host copy of the transcripts per batch."""
+        batch loop: one forward pass, one search and one host copy of the transcripts per batch.
+
+        eval_loss=True adds the CTC evaluation loss of the scored entries (``metrics.CTCEvalLoss``: each batch's log-probs
+        against the same parsed reference tokens, over each row's own encoded frames): "eval_loss", the reference's
+        ``Evaluation_Loss`` -- the mean of the batches' mean losses, which DEPENDS on ``batch_size`` (and on the sort by
+        duration that cuts the batches): a last, smaller batch weighs as much as a full one --, and "loss_sum", "scored",
+        "infeasible" per utterance: ``loss_sum / scored``, the mean over the utterances that have a path, does not depend
+        on the batch size.  A reference with more tokens than its audio has frames for counts in "infeasible" and makes
+        "eval_loss" inf, as the reference's mean would be.  Like the ``nbest`` form this is a plain batch loop with
+        ``forward(want_logp=True)``; it cannot be combined with ``nbest`` (ValueError)."""
         from .metrics import ErrorBreakdown, ErrorRate
         metric = (ErrorBreakdown if breakdown else ErrorRate)(self.labels)
+        if eval_loss:
+            if nbest is not None:
+                raise ValueError("eval_loss=True cannot be combined with nbest")
+            return self._evaluate_manifest_loss(manifest_filepath, batch_size, row_independent, metric)
         if nbest is not None:
             return self._evaluate_manifest_nbest(manifest_filepath, batch_size, row_independent, metric, int(nbest))
         keep = []                   # pinned reference batches, alive until the copies that read them have run
@@ -261,6 +275,70 @@ class VietASR:
         res, best = metric.compute(), oracle.compute()
         res["oracle_wer"], res["oracle_cer"] = best["oracle_wer"], best["oracle_cer"]
         return hyps, res
+
+    def _forward_logp(self, sigs, row_independent):
+        """One zero-padded batch of signals at the model's rate through ``forward(want_logp=True)`` -> (its result dict, the
+        frames of every row [B] on the device: the row's own encoded frames when row_independent, otherwise the encoder's
+        lengths of the padded batch)."""
+        from .engine import _pcm_to_float
+        eng = self._fused_engine()
+        lens = [len(s) for s in sigs]
+        if row_independent and min(lens) <= eng.frontend["n_fft"] // 2:
+            raise ValueError(f"row-independent batching needs more than n_fft/2 = {eng.frontend['n_fft'] // 2} samples "
+                             f"per signal (got {min(lens)})")
+        batch = np.zeros((len(sigs), max(lens)), dtype=np.float32)
+        for k, s in enumerate(sigs):
+            batch[k, : lens[k]] = _pcm_to_float(s)
+        r = eng.forward(torch.from_numpy(batch).to(eng.device), torch.tensor(lens, device=eng.device), want_logp=True,
+                        row_independent=row_independent)
+        if row_independent:
+            frames = torch.tensor([eng.frames(n)[1] for n in lens], dtype=torch.int32).to(eng.device)
+        else:
+            frames = r["enc_len"]
+        return r, frames
+
+    def _evaluate_manifest_loss(self, manifest_filepath, batch_size, row_independent, metric):
+        from .metrics import CTCEvalLoss
+        eng, loss = self._fused_engine(), CTCEvalLoss(len(self.labels))
+        entries, batches = self._manifest_batches(manifest_filepath, batch_size)
+        hyps = [None] * len(entries)
+        for idx, sigs in batches:
+            r, frames = self._forward_logp(sigs, row_independent)
+            rows = [k for k, i in enumerate(idx) if entries[i].get("text")]
+            if rows:
+                ref, ref_len = self._reference_tokens(entries, [idx[k] for k in rows])
+                ref, ref_len = ref.to(eng.device), ref_len.to(eng.device)
+                ids, id_len, logp = r["ids"], r["id_len"], r["logp"]
+                if len(rows) != len(idx):
+                    sel = torch.tensor(rows, dtype=torch.int64, device=eng.device)
+                    ids, id_len, logp, frames = (t.index_select(0, sel) for t in (ids, id_len, logp, frames))
+                metric.update(ids, id_len, ref, ref_len)
+                loss.update(logp, frames, ref, ref_len)
+            for i, t in zip(idx, eng.texts(r["ids"], r["id_len"])):
+                hyps[i] = t
+        res = metric.compute()
+        res.update(loss.compute())
+        return hyps, res
+
+    def score(self, signals, texts, sample_rate=None, row_independent=True):
+        """log P(text | audio) of every (signal, text) pair -> a list of Python floats, minus the CTC loss of the row
+        (``stages.ctc_loss`` on the batch's log-probs, over each row's own encoded frames): the forced score of ANY
+        transcript -- a reference, or a greedy or beam hypothesis as a sequence confidence or for rescoring.  The texts go
+        through the character parser the references go through (characters outside the labels are dropped).  A text that
+        has no path through its audio (more tokens, counting one more per repeated character, than frames) scores -inf.
+        row_independent (default): every score is what the signal alone would give.  One synchronisation."""
+        signals, texts = list(signals), list(texts)
+        if len(signals) != len(texts) or not signals:
+            raise ValueError(f"score needs as many texts as signals, and at least one (got {len(signals)} and {len(texts)})")
+        eng = self._fused_engine()
+        r, frames = self._forward_logp([self._to_model_rate(s, sample_rate) for s in signals], row_independent)
+        ref, ref_len = self._reference_tokens([{"text": t} for t in texts], range(len(texts)))
+        from . import stages
+        loss = stages.ctc_loss(r["logp"], frames, ref.to(eng.device), ref_len.to(eng.device), len(self.labels))
+        host = loss.cpu().tolist()
+        if any(v != v for v in host):
+            raise RuntimeError("the CTC score came back NaN for rows %s" % [k for k, v in enumerate(host) if v != v])
+        return [-v for v in host]
 
     def launch_batch(self, signals, sample_rate=None, row_independent=False):
         """Asynchronous ``transcribe_batch``: returns a handle at once, ``.texts()`` waits (engine.QuartzNetCTC.launch)."""

@@ -13,6 +13,9 @@ of the beam search's n-best list (``stages.nbest_error_counts``, vasr_nbest_erro
 ``classification_accuracy`` (metrics.py:66-99) and ``TopKAccuracy`` (the running form of
 process_classification_evaluation_batch / _epoch, helpers.py:215-288) rest on ``stages.classification_scores``
 (vasr_class_scores_f32, csrc/cls_eval.hip): the target's rank among the row's classes and its cross-entropy loss per row.
+
+``CTCEvalLoss`` is the ``Evaluation_Loss`` of the ASR path (helpers.py:146-204 with CTCLossNM, losses.py): the running mean
+of the batch means of ``stages.ctc_loss`` (vasr_ctc_loss_f32, csrc/ctc_loss.hip), with the per-utterance sums beside it.
 """
 import torch
 
@@ -282,3 +285,55 @@ class TopKAccuracy:
         for k in self.top_k:
             out[f"Evaluation_Accuracy_Top@{k} {tag}"] = r["accuracy"][k] / k * 100.0
         return out
+
+
+class CTCEvalLoss:
+    """Running CTC evaluation loss over batches of log-probs: ``Evaluation_Loss`` of process_evaluation_batch / _epoch
+    (helpers.py:146-204) with ``CTCLossNM`` (losses.py) without their per-batch host round trips.  ``update`` enqueues and
+    never synchronises; ``compute`` is the one sync.  The loss is kept as the reference keeps it -- one float32 batch mean
+    per ``update`` (``torch.mean`` of the per-row losses, not divided by the target lengths), and ``eval_loss`` the mean of
+    those batch means, which depends on how the utterances were cut into batches; ``loss_sum`` / ``scored`` does not."""
+
+    def __init__(self, num_classes):
+        self.blank = int(num_classes)         # CTCLossNM: the blank follows the labels
+        self._acc = None          # int64 [3]: finite rows, +inf rows (no path), NaN rows (a length or an id the kernel refused)
+        self._loss = None         # float32 [2]: the sum of the batch means, the number of batches
+        self._sums = []           # float32 [] per batch: the sum of its finite per-row losses (added up in float64 on the host)
+
+    def update(self, log_probs, input_length, targets, target_length):
+        """log_probs [B,T',C] / input_length [B] / targets [B,W] / target_length [B] on the device (``stages.ctc_loss``);
+        enqueued on the current stream."""
+        self.add_losses(stages.ctc_loss(log_probs, input_length, targets, target_length, self.blank))
+
+    def add_losses(self, loss):
+        """One batch as ``stages.ctc_loss`` scored it -- loss [B] f32 -- for callers that made that launch themselves.  No
+        host round trip."""
+        finite = torch.isfinite(loss)
+        row = torch.stack([finite.sum(dtype=torch.int64), torch.isinf(loss).sum(dtype=torch.int64),
+                           torch.isnan(loss).sum(dtype=torch.int64)])
+        pair = torch.stack([loss.mean(dtype=torch.float32), torch.ones((), dtype=torch.float32, device=loss.device)])
+        self._sums.append(torch.where(finite, loss, torch.zeros_like(loss)).sum(dtype=torch.float32))
+        self._acc = row if self._acc is None else self._acc + row
+        self._loss = pair if self._loss is None else self._loss + pair
+
+    def reset(self):
+        self._acc, self._loss, self._sums = None, None, []
+
+    def compute(self, reduce=False, group=None):
+        """-> {"eval_loss": the mean of the float32 batch means (inf once a batch held a row without a path, as the
+        reference's), "loss_sum": the sum of the finite per-row losses, "scored": the rows counted in it, "infeasible":
+        the rows that came back +inf}.  reduce=True sums the accumulators over the process group first
+        (``dist.all_reduce_counts``).  No batch gives eval_loss NaN.  Raises VasrError when a row came back NaN (a negative
+        length, or a target id inside its length that is out of range or the blank)."""
+        acc = self._acc if self._acc is not None else torch.zeros(3, dtype=torch.int64)
+        pair = self._loss if self._loss is not None else torch.zeros(2, dtype=torch.float32)
+        total = torch.stack(self._sums).cpu().to(torch.float64).sum().reshape(1) if self._sums else torch.zeros(1, dtype=torch.float64)
+        if reduce:
+            acc, pair = dist.all_reduce_counts(acc, group), dist.all_reduce_counts(pair, group)
+            total = dist.all_reduce_counts(total, group)
+        (scored, infeasible, bad), (mean_sum, batches) = acc.cpu().tolist(), pair.cpu().tolist()
+        if bad:
+            raise _lib.VasrError(f"{bad} scored rows came back NaN (a negative length, or a target id inside the row's length "
+                                 "that is out of range or the blank): no loss is returned for them")
+        return dict(eval_loss=float(mean_sum) / float(batches) if batches else float("nan"), loss_sum=float(total.cpu()[0]),
+                    scored=int(scored), infeasible=int(infeasible))

@@ -272,3 +272,42 @@ def classification_scores(logits, targets=None, k=0, want_prob=False, want_loss=
                                                     t.data_ptr() if t is not None and B else None, k, ptr("indices"),
                                                     ptr("values"), ptr("probs"), ptr("rank"), ptr("loss"), _st()))
     return out
+
+
+def _i32_lengths(t, dev):
+    """Lengths of any dtype -> int32 on dev.  Float lengths (the encoder's, quirk Q3) are truncated as ``.long()`` truncates
+    them; values outside int32 are clamped so that a negative length stays negative and a huge one stays huge."""
+    x = torch.as_tensor(t).to(device=dev)
+    return x.to(torch.int64).clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
+
+
+def ctc_loss(log_probs, input_length, targets, target_length, blank):
+    """nn.CTCLoss(blank, reduction='none', zero_infinity=False) per row, as CTCLossNM builds it (vasr_ctc_loss_f32) -> loss
+    [B] f32 on the device = -log P(targets[b, :target_length[b]] | log_probs[b, :input_length[b]]).  log_probs [B,T',C] f32
+    cuda, batch first as the decoder delivers them (other floating types are cast on the device); input_length [B]: any
+    dtype, float lengths from the encoder are truncated as ``CTCLossNM._loss``'s ``.long()`` truncates them; targets [B,W] /
+    target_length [B]: the data layer's transcripts / transcript_length, W <= 4096 (NotImplementedError beyond).  +inf for a
+    row without a path; a quiet NaN for a row with a negative length or with an id inside its length that is out of range
+    or the blank (include/vasr.h).  Forward only: the result carries no graph.  Enqueued on the current stream; nothing
+    synchronises."""
+    _need_cuda(log_probs)
+    if log_probs.dim() != 3 or not log_probs.dtype.is_floating_point:
+        raise ValueError(f"log_probs must be a floating-point [B, T, C] tensor, got {log_probs.dtype} {tuple(log_probs.shape)}")
+    if targets.dim() != 2:
+        raise ValueError(f"targets must be [B, W], got {tuple(targets.shape)}")
+    B, T1, Cn = log_probs.shape
+    if targets.shape[0] != B or tuple(torch.as_tensor(input_length).shape) != (B,) or \
+            tuple(torch.as_tensor(target_length).shape) != (B,):
+        raise ValueError(f"batch sizes differ: log_probs {tuple(log_probs.shape)}, targets {tuple(targets.shape)}, lengths "
+                         f"{tuple(torch.as_tensor(input_length).shape)} / {tuple(torch.as_tensor(target_length).shape)}")
+    dev = log_probs.device
+    x = log_probs.detach().to(torch.float32).contiguous()
+    xp = x if x.numel() else torch.empty(1, dtype=torch.float32, device=dev)      # (a pointer the library never reads)
+    y, yp = _i32_rows(targets, dev)
+    fn, yn = _i32_lengths(input_length, dev), _i32_lengths(target_length, dev)
+    loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().vasr_ctc_loss_f32(xp.data_ptr(), fn.data_ptr() if B else None, B, T1, Cn, int(blank),
+                                                yp.data_ptr(), y.shape[1], yn.data_ptr() if B else None,
+                                                loss.data_ptr() if B else None, _st()))
+    return loss
