@@ -353,7 +353,10 @@ def test_split_gemms_are_as_accurate_as_fp32_mfma(gpu, cin, kind):
     products; 2 x fp16 scaled, three products) may be less accurate than the exact-fp32 MFMA chain, and all three must
     agree to fp32 round-off.  Inputs: Gaussian; ReLU'd Gaussian (what the layers actually see); and "wide" -- rows whose
     magnitudes span 2^-24 ... 2^6 inside one utterance, far more than the 18 octaves the fp16 split carries at full
-    precision, where its error must stay below fp32 round-off of the LARGEST terms (absolute, not relative)."""
+    precision, where its error must stay below fp32 round-off of the LARGEST terms (absolute, not relative).
+    At B = 2, T = 300 (six 64-column tiles) the launcher's own rule reaches only the 64 x 32 tile (bf16x3) and the latency
+    kernel of encoder_pw_lat.hip (f16x2), with scale 1, shift 0, no lengths and no residual; the other tiles, the BN affine,
+    the RES and DUAL forms and the fused kernel are held to float64 by tests/test_gpu_sep.py."""
     from viet_asr_amd import _lib
     import ctypes as C
     L = _lib.dev_lib()      # include/vasr_devtools.h lives in the devtools build
