@@ -380,6 +380,50 @@ VASR_API int vasr_ctc_loss_f32(const float* d_logp, const int32_t* d_frames, int
                                int blank, const int32_t* d_tgt, int64_t tgt_width, const int32_t* d_tgt_len,
                                float* d_loss /* [B] */, vasr_stream stream);
 
+/* Forced (Viterbi) CTC alignment, per row: the best SINGLE path of a transcript through the row's log-probs -- the trellis of
+ * vasr_ctc_loss_f32 with max in place of log-sum-exp -- and from it the frames each token occupies: character time offsets.
+ * The transcript may be a reference, a beam hypothesis, or the row's own greedy transcript (d_ids / d_id_len of the calls
+ * below: the best path of the greedy collapse is the per-frame argmax path).
+ *   d_logp, d_frames, d_tgt, d_tgt_len, blank: the meaning, the clamping -- T = clamp(d_frames[b], 0, frames), L =
+ *   clamp(d_tgt_len[b], 0, tgt_width) -- and the conventions of vasr_ctc_loss_f32.
+ * The formula.  The extended sequence e has S = 2 L + 1 states (blank, y1, blank, ..., yL, blank).
+ *   delta(0, 0) = logp[0][blank], delta(0, 1) = logp[0][y1], delta(0, s) = -inf for s >= 2;
+ *   for t >= 1:  x0 = delta(t-1, s), x1 = delta(t-1, s-1), and x2 = delta(t-1, s-2) only where e_s is not blank and
+ *                e_s != e_(s-2); a term that does not exist counts as -inf;
+ *                best = x0, bp = 0;  if x1 > best: best = x1, bp = 1;  if x2 > best: best = x2, bp = 2;
+ *                delta(t, s) = best + logp[t][e_s];
+ *   a later candidate wins only STRICTLY (the order s, s-1, s-2 of the loss).  The final state is S-1, unless
+ *   delta(T-1, S-2) > delta(T-1, S-1) strictly; d_score[b] = that delta; the path follows bp back from there to frame 0.
+ * Only comparisons and float32 additions: no transcendental function, no multiply, nothing a compiler can contract -- the
+ * same recursion in IEEE float32 gives the same bits, in score, path and spans.
+ * Rows: a row whose score is -inf has NO PATH (T < L + the number of adjacent equal label pairs; T == 0 with L > 0; -inf
+ * log-probs that block every path).  A negative length on either side, or an id inside the row's length that is < 0, >=
+ * num_classes or == blank, gives a quiet NaN score.  T == 0 and L == 0 give score 0.  A -inf log-prob is legal and never
+ * makes a NaN.
+ * Outputs:
+ *   d_score [B] f32
+ *   d_start, d_end [B][tgt_width] i32: token j holds the frames [start, end) whose state is 2 j + 1; blank frames belong to no
+ *                  token; on a path every token has end > start
+ *   d_tok_logp [B][tgt_width] f32 (may be NULL): the sum over t = start .. end-1, ascending, of logp[t][y_j], starting from
+ *                  the first term
+ *   d_path [B][frames] i32 (may be NULL): the state index s(t) for t < T
+ * Unfilled entries -- j >= L, t >= T, every entry of a row with no path or a NaN score -- are -1 in the three i32 arrays and
+ * +0.0f in d_tok_logp.  EVERY element of every non-NULL output is written; nothing behind a row's lengths is ever read.
+ * No atomics; a row's outputs are bit-identical whatever batch, `frames` or `tgt_width` it is launched with.
+ * The back-pointers (2 bits per frame and state) go through d_workspace: vasr_ctc_align_workspace_bytes(batch, frames,
+ * tgt_width) bytes of device memory at any address, contents undefined before and after; the function is host only, touches
+ * no device, and returns 0 for arguments the call below refuses (batch <= 0, frames < 0, tgt_width outside 0..4096).  At
+ * most 2 bits per frame and state slot (256 lanes x 4 slots while 2 * tgt_width + 1 <= 1024, x 33 slots above) + 256 bytes.
+ * NULL d_logp / d_frames / d_tgt / d_tgt_len / d_score / d_start / d_end, batch <= 0, frames < 0, tgt_width < 0, num_classes < 2,
+ * blank outside [0, num_classes) and a workspace that is NULL or smaller than required return VASR_ERR_INVALID; tgt_width >
+ * 4096 returns VASR_ERR_UNSUPPORTED with the limit in vasr_last_error() -- all before a device is touched.  frames == 0 and
+ * tgt_width == 0 are legal.  No handle; one workgroup per row; DESIGN section 7e has the measured times.  (ABI 8) */
+VASR_API size_t vasr_ctc_align_workspace_bytes(int batch, int64_t frames, int64_t tgt_width);
+VASR_API int vasr_ctc_align_f32(const float* d_logp, const int32_t* d_frames, int batch, int64_t frames, int num_classes,
+                                int blank, const int32_t* d_tgt, int64_t tgt_width, const int32_t* d_tgt_len,
+                                float* d_score /* [B] */, int32_t* d_start, int32_t* d_end, float* d_tok_logp, int32_t* d_path,
+                                void* d_workspace, size_t workspace_bytes, vasr_stream stream);
+
 /* ---- the whole path in one call (the fast path bench.py times) ------------------------ */
 /* wav -> mel -> encoder -> CTC head -> log-softmax/argmax -> collapse, all intermediates in
  * the workspace (padded time stride, no port tensors materialised).

@@ -61,6 +61,9 @@ SIGNATURES = {
                                               C.c_int, _P, _P, _P, _P]),
     "vasr_class_scores_f32": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "vasr_ctc_loss_f32": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, _P, _P]),
+    "vasr_ctc_align_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64]),
+    "vasr_ctc_align_f32": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P,
+                                     C.c_size_t, _P]),
     "vasr_transcribe_greedy_f32": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P,
                                              C.c_size_t, _P]),
     "vasr_transcribe_greedy_pcm16": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P,

@@ -1734,6 +1734,34 @@ int vasr_ctc_loss_f32(const float* d_logp, const int32_t* d_frames, int batch, i
   return check_launch("ctc_loss");
 }
 
+size_t vasr_ctc_align_workspace_bytes(int batch, int64_t frames, int64_t tgt_width) {
+  if (batch <= 0 || frames < 0 || tgt_width < 0 || tgt_width > kCtcLossMaxWidth) return 0;
+  return ctc_align_workspace_bytes(batch, frames, (int)tgt_width);
+}
+
+int vasr_ctc_align_f32(const float* d_logp, const int32_t* d_frames, int batch, int64_t frames, int num_classes, int blank,
+                       const int32_t* d_tgt, int64_t tgt_width, const int32_t* d_tgt_len, float* d_score, int32_t* d_start,
+                       int32_t* d_end, float* d_tok_logp, int32_t* d_path, void* d_workspace, size_t workspace_bytes,
+                       vasr_stream stream) {
+  // every refusal comes before a device is touched
+  if (!d_logp || !d_frames || !d_tgt || !d_tgt_len || !d_score || !d_start || !d_end)
+    return fail(VASR_ERR_INVALID, "ctc_align: NULL pointer");
+  if (batch <= 0 || frames < 0 || tgt_width < 0)
+    return fail(VASR_ERR_INVALID, "ctc_align: batch %d, frames %lld, tgt_width %lld", batch, (long long)frames, (long long)tgt_width);
+  if (num_classes < 2 || blank < 0 || blank >= num_classes)
+    return fail(VASR_ERR_INVALID, "ctc_align: num_classes %d (at least 2), blank %d outside [0, num_classes)", num_classes, blank);
+  if (!d_workspace) return fail(VASR_ERR_INVALID, "ctc_align: NULL workspace");
+  if (tgt_width > kCtcLossMaxWidth)
+    return fail(VASR_ERR_UNSUPPORTED, "ctc_align: targets of %lld ids, at most %d", (long long)tgt_width, kCtcLossMaxWidth);
+  const size_t need = ctc_align_workspace_bytes(batch, frames, (int)tgt_width);
+  if (workspace_bytes < need)
+    return fail(VASR_ERR_INVALID, "ctc_align: workspace of %zu bytes, %zu needed (vasr_ctc_align_workspace_bytes)", workspace_bytes, need);
+  const int rc = launch_ctc_align(d_logp, d_frames, batch, frames, num_classes, blank, d_tgt, (int)tgt_width, d_tgt_len, d_score,
+                                  d_start, d_end, d_tok_logp, d_path, d_workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+  if (rc) return fail(VASR_ERR_HIP, "ctc_align: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
+  return check_launch("ctc_align");
+}
+
 // One contiguous slice of the batch through the whole path on one stream.
 static int transcribe_part(vasr_handle* h, const void* d_wav, bool pcm16, const int64_t* d_len, int batch, int64_t samples,
                            int64_t* d_pred, int32_t* d_ids, int32_t* d_id_len, float* d_logp, float* d_enc_len,

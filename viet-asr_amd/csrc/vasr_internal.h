@@ -386,6 +386,24 @@ constexpr int kCtcLossWideSlots = 33;
 int launch_ctc_loss(const float* logp, const int32_t* frames_in, int batch, int64_t frames, int classes, int blank,
                     const int32_t* tgt, int tgt_width, const int32_t* tgt_len, float* loss, hipStream_t st);
 
+// ---- CTC forced alignment (ctc_align.hip) ----
+// per row the best single path of tgt through logp, on the trellis, the mapping and the conventions of launch_ctc_loss
+// (include/vasr.h has the formula): score [B], start / end [B][tgt_width], tok_logp [B][tgt_width] or NULL, path [B][frames] or
+// NULL.  The back-pointers, 2 bits per (frame, state slot), go through `workspace` (ctc_align_workspace_bytes; any address:
+// the first multiple of kCtcAlignWorkspaceAlign inside it is used): kCtcAlignNarrowFrameBytes per row and frame in the
+// 4-slot form, kCtcAlignWideFrameBytes in the 33-slot form (two words per lane + one for state 8192, padded to 16 bytes).
+// The back-trace stages them in LDS kCtcAlignNarrowBlock / kCtcAlignWideBlock frames at a time.  The caller checks tgt_width
+// <= kCtcLossMaxWidth; returns 0 or a hipError_t
+constexpr int kCtcAlignNarrowFrameBytes = 256;
+constexpr int kCtcAlignWideFrameBytes = 2064;
+constexpr int kCtcAlignNarrowBlock = 64;
+constexpr int kCtcAlignWideBlock = 16;
+constexpr int kCtcAlignWorkspaceAlign = 256;
+size_t ctc_align_workspace_bytes(int batch, int64_t frames, int tgt_width);   // host only; SIZE_MAX where it does not fit
+int launch_ctc_align(const float* logp, const int32_t* frames_in, int batch, int64_t frames, int classes, int blank,
+                     const int32_t* tgt, int tgt_width, const int32_t* tgt_len, float* score, int32_t* start, int32_t* end,
+                     float* tok_logp, int32_t* path, void* workspace, size_t workspace_bytes, hipStream_t st);
+
 // ---- audio ingest (audio.hip) ----
 void launch_pcm16_to_f32(const short* in, int64_t n, float* out, hipStream_t st);
 void launch_resample(const float* x, int64_t ld_in, const int64_t* len_in, int batch, const float* table, int nwin,

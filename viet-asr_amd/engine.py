@@ -197,6 +197,14 @@ class QuartzNetCTC:
         t = self.handle.mel_frames(samples)
         return t, self.handle.encoded_frames(t)
 
+    def frame_seconds(self):
+        """Seconds of audio per encoded frame: the front end's hop times the encoder's stride product -- what ``frames``
+        divides by -- over the model's sample rate."""
+        stride = 1
+        for b in self._blocks:
+            stride *= b["stride"]
+        return self.hop * stride / float(self.frontend["sample_rate"])
+
     def _workspace(self, batch, samples):
         need = self.handle.workspace_bytes(batch, samples=samples)
         if self._ws is None or self._ws.numel() < need:

@@ -20,6 +20,26 @@ from .engine import QuartzNetCTC
 from .helpers import post_process_predictions
 
 
+def alignment_entries(chars, start, end, logp, frame_seconds):
+    """The host side of ``VietASR.align`` for one row that has a path: chars (the row's labels, one per token) with their
+    frame spans [start[j], end[j]) and log-probs logp[j] -> (chars, words): lists of {"char" | "word", "start", "end",
+    "logp"}, times in seconds = frames * frame_seconds.  Words are the maximal runs of non-whitespace labels, as the error
+    rates split them (metrics.space_ids); a word starts with its first character, ends with its last, and its "logp" is the
+    sum of its characters', in order.  Whitespace labels are characters and belong to no word."""
+    cs, ws, run = [], [], []
+    for j, c in enumerate(chars):
+        cs.append({"char": c, "start": int(start[j]) * frame_seconds, "end": int(end[j]) * frame_seconds, "logp": float(logp[j])})
+        if not c.isspace():
+            run.append(cs[-1])
+        if run and (c.isspace() or j == len(chars) - 1):
+            total = 0.0
+            for x in run:
+                total += x["logp"]
+            ws.append({"word": "".join(x["char"] for x in run), "start": run[0]["start"], "end": run[-1]["end"], "logp": total})
+            run = []
+    return cs, ws
+
+
 class VietASR:
     def __init__(self, config_file, encoder_checkpoint, decoder_checkpoint, device="gpu", lm_path=None,
                  beam_width=20, lm_alpha=0.5, lm_beta=1.5, decoder="beam", allow_missing_lm=False, lm_unigrams="auto"):
@@ -339,6 +359,49 @@ class VietASR:
         if any(v != v for v in host):
             raise RuntimeError("the CTC score came back NaN for rows %s" % [k for k, v in enumerate(host) if v != v])
         return [-v for v in host]
+
+    def align(self, signals, texts=None, sample_rate=None, row_independent=True):
+        """Character and word time spans of every (signal, text) pair: the forced (Viterbi) alignment of the text to the
+        batch's log-probs (``stages.ctc_align``, over each row's own encoded frames) -> per row a dict {"text", "score",
+        "chars", "words"} (``alignment_entries``): "score" is the log-probability of the best single path, at most
+        ``score``'s; every character and word carries "start" / "end" in seconds and "logp", the sum of its log-probs over
+        its frames.  The texts go through the character parser the references go through (characters outside the labels are
+        dropped); "text" is the parsed text.  texts=None aligns every row's own greedy transcript, from the same forward
+        pass: the collapsed ids of the pass are the targets on the device, the spans are the runs of the per-frame argmax.
+        A text with no path through its audio gets score -inf and empty lists.  row_independent (default): every row is what
+        the signal alone would give.  One synchronisation."""
+        from . import stages
+        signals = list(signals)
+        if texts is not None:
+            texts = list(texts)
+        if not signals or (texts is not None and len(signals) != len(texts)):
+            raise ValueError(f"align needs at least one signal, and as many texts as signals (got {len(signals)} and "
+                             f"{None if texts is None else len(texts)})")
+        eng = self._fused_engine()
+        r, frames = self._forward_logp([self._to_model_rate(s, sample_rate) for s in signals], row_independent)
+        if texts is None:
+            tgt, tgt_len = r["ids"], r["id_len"]
+        else:
+            ref, ref_len = self._reference_tokens([{"text": t} for t in texts], range(len(texts)))
+            tgt, tgt_len = ref.to(eng.device, non_blocking=True), ref_len.to(eng.device, non_blocking=True)
+        out = stages.ctc_align(r["logp"], frames, tgt, tgt_len, len(self.labels))
+        dev = [out["score"], out["start"], out["end"], out["token_logp"], tgt.to(torch.int32), tgt_len.to(torch.int32)]
+        host = [torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in dev]
+        for h, d in zip(host, dev):
+            h.copy_(d, non_blocking=True)
+        torch.cuda.current_stream(eng.device).synchronize()
+        score, start, end, logp, ids, n = (h.numpy() for h in host)
+        if np.isnan(score).any():
+            raise RuntimeError("the alignment score came back NaN for rows %s" % np.isnan(score).nonzero()[0].tolist())
+        sec = eng.frame_seconds()
+        rows = []
+        for b in range(len(signals)):
+            chars = [self.labels[c] for c in ids[b, : n[b]]]
+            row = {"text": "".join(chars), "score": float(score[b]), "chars": [], "words": []}
+            if score[b] != -np.inf:
+                row["chars"], row["words"] = alignment_entries(chars, start[b], end[b], logp[b], sec)
+            rows.append(row)
+        return rows
 
     def launch_batch(self, signals, sample_rate=None, row_independent=False):
         """Asynchronous ``transcribe_batch``: returns a handle at once, ``.texts()`` waits (engine.QuartzNetCTC.launch)."""

@@ -311,3 +311,52 @@ def ctc_loss(log_probs, input_length, targets, target_length, blank):
                                                 yp.data_ptr(), y.shape[1], yn.data_ptr() if B else None,
                                                 loss.data_ptr() if B else None, _st()))
     return loss
+
+
+def ctc_align(log_probs, input_length, targets, target_length, blank, want_path=False):
+    """Forced (Viterbi) CTC alignment per row (vasr_ctc_align_f32): the best single path of targets[b, :target_length[b]]
+    through log_probs[b, :input_length[b]] -> a dict of device tensors: ``score`` [B] f32 (the path's log-probability; -inf
+    for a row without a path, a quiet NaN where ``ctc_loss`` gives one), ``start`` / ``end`` [B,W] i32 (token j occupies the
+    frames [start, end); -1 behind the row's length and on rows without a path), ``token_logp`` [B,W] f32 (the sum of the
+    token's log-probs over its frames; 0 where unfilled) and, with want_path, ``path`` [B,T'] i32 (the state 0 .. 2 L of every
+    frame: 2 j + 1 is token j, even states are blanks; -1 from the row's length on).  The arguments, the validation and the
+    casts are those of ``ctc_loss``; W <= 4096 (NotImplementedError beyond).  The back-pointer workspace is allocated here.
+    Enqueued on the current stream; nothing synchronises."""
+    if log_probs.dim() != 3 or not log_probs.dtype.is_floating_point:
+        raise ValueError(f"log_probs must be a floating-point [B, T, C] tensor, got {log_probs.dtype} {tuple(log_probs.shape)}")
+    if targets.dim() != 2:
+        raise ValueError(f"targets must be [B, W], got {tuple(targets.shape)}")
+    B, T1, Cn = log_probs.shape
+    if targets.shape[0] != B or tuple(torch.as_tensor(input_length).shape) != (B,) or \
+            tuple(torch.as_tensor(target_length).shape) != (B,):
+        raise ValueError(f"batch sizes differ: log_probs {tuple(log_probs.shape)}, targets {tuple(targets.shape)}, lengths "
+                         f"{tuple(torch.as_tensor(input_length).shape)} / {tuple(torch.as_tensor(target_length).shape)}")
+    _need_cuda(log_probs)
+    dev = log_probs.device
+    x = log_probs.detach().to(torch.float32).contiguous()
+    xp = x if x.numel() else torch.empty(1, dtype=torch.float32, device=dev)      # (a pointer the library never reads)
+    y, yp = _i32_rows(targets, dev)
+    W = y.shape[1]
+    fn, yn = _i32_lengths(input_length, dev), _i32_lengths(target_length, dev)
+    out = {"score": torch.empty((B,), dtype=torch.float32, device=dev),
+           "start": torch.empty((B, W), dtype=torch.int32, device=dev), "end": torch.empty((B, W), dtype=torch.int32, device=dev),
+           "token_logp": torch.empty((B, W), dtype=torch.float32, device=dev)}
+    if want_path:
+        out["path"] = torch.empty((B, T1), dtype=torch.int32, device=dev)
+
+    spare = torch.empty(1, dtype=torch.int32, device=dev)    # stands in for an output without storage: never written
+
+    def ptr(name, need=True):
+        t = out.get(name)
+        if t is None:
+            return None
+        return t.data_ptr() if t.numel() else (spare.data_ptr() if need else None)
+
+    L = _lib.lib()
+    nbytes = L.vasr_ctc_align_workspace_bytes(B, T1, W)       # 0 where the call below refuses its arguments
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.vasr_ctc_align_f32(xp.data_ptr(), fn.data_ptr() if B else None, B, T1, Cn, int(blank), yp.data_ptr(), W,
+                                        yn.data_ptr() if B else None, ptr("score") if B else None, ptr("start"), ptr("end"),
+                                        ptr("token_logp", need=False), ptr("path", need=False), ws.data_ptr(), nbytes, _st()))
+    return out
