@@ -135,11 +135,13 @@ def torch_stft_magnitude(x, n_fft, hop, win_length, window="hann"):
 
 def melspec_forward(x, length, sample_rate=16000, n_window_size=320, n_window_stride=160, n_fft=512,
                     preemph=0.97, nfilt=64, lowfreq=0, highfreq=None, log_zero_guard_value=2 ** -24,
-                    normalize="per_feature", pad_value=0.0, fb=None, stft_conv=False, log_zero_guard_type="add", dither=0.0):
+                    normalize="per_feature", pad_value=0.0, fb=None, stft_conv=False, log_zero_guard_type="add", dither=0.0,
+                    window=None):
     """FilterbankFeatures.forward (parts/features.py:245-301) with dither=0 (default), pad_to=0
     (infer.py:89-90; quirk Q1: the featurizer is never put in eval mode, so no pad-to-16),
     mag_power=2, log guard "add", frame_splicing=1.  stft_conv=True (unpinned, see
-    torch_stft_magnitude) squares the package's magnitude and skips the re/im sum (:260-263).
+    torch_stft_magnitude) squares the package's magnitude and skips the re/im sum (:260-263).  window: the window tensor
+    of another of the constructor's window functions (:171-180); default the symmetric hann window.
 
     x [B, L] float32, length [B] int64 -> (mel [B, nfilt, 1 + L//hop] f32, seq_len [B] i64)
     """
@@ -153,7 +155,9 @@ def melspec_forward(x, length, sample_rate=16000, n_window_size=320, n_window_st
     if stft_conv:
         p = torch_stft_magnitude(x, n_fft, n_window_stride, n_window_size).pow(2.0)     # :155-166, :260-261
     else:
-        window = torch.hann_window(n_window_size, periodic=False)              # :179-180
+        if window is None:
+            window = torch.hann_window(n_window_size, periodic=False)          # :179-180
+        window = torch.as_tensor(window, dtype=torch.float32)
         # :181-188 torch.stft(center=True) -> reflect pad n_fft//2, window centred in n_fft
         spec = torch.stft(x, n_fft=n_fft, hop_length=n_window_stride, win_length=n_window_size,
                           center=True, window=window, return_complex=True, pad_mode="reflect")
