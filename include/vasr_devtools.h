@@ -20,6 +20,10 @@ VASR_API int vasr_profile_bracket_overhead(vasr_stream stream, int n, double* ou
 /* The form a 256-channel separable sub-block takes (csrc/vasr_internal.h fused_tile_choice; pure host arithmetic): 128 / 64 =
  * the fused depthwise + pointwise kernel on tiles of that many frames, 0 = two kernels.  tiles128 = batch x padded frames / 128. */
 VASR_API int vasr_fused_tile_choice(int64_t tiles128, int compute_units);
+/* Wavefronts per workgroup (8 or 16) the fused kernel is launched with for a sub-block of depthwise kernel 33 | 39, with
+ * (dual != 0) or without the folded residual, on tiles of tile_cols = 128 | 64 frames: VASR_FUSED_WAVES where it is set and the
+ * form exists (the 128-frame tile), else the library's default (csrc/encoder_fused.hip fused_waves_choice; pure host arithmetic). */
+VASR_API int vasr_fused_waves_choice(int kernel, int dual, int tile_cols);
 /* Run ONE encoder layer kind in isolation for benchmarking/roofline measurement:
  * kind 0 = depthwise (K, stride 1, dilation 1), 1 = pointwise GEMM (+BN+ReLU epilogue).
  * Buffers are caller provided [B][C][Tp] with Tp = vasr_padded_frames(T). */

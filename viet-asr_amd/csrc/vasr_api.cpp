@@ -1181,6 +1181,7 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
         if (fuse_res) { f.x2 = blk_in; f.ldx2 = blk_ld; f.lens2 = lens(B.first_step); f.amax_x2 = blk_amax; }
         f.batch = batch; f.kernel = S.dw.kernel;
         f.tile_cols = f_cols;
+        f.waves = h->sw.fused_waves;
         int e;
         {
           ProfScope ps(h, kProfFused, st, 2.0 * WF.cin * WF.cout * (double)cur_T * batch,

@@ -37,6 +37,7 @@ const vasr::DevSwitches& vasr::dev_switches() {
     s.fused = num("VASR_FUSED", 1, {0, 1}) != 0;
     s.fused_min_tiles = getenv("VASR_FUSED_MIN_TILES") ? atoi(getenv("VASR_FUSED_MIN_TILES")) : 0;
     s.fused_tile = num("VASR_FUSED_TILE", 0, {0, 64, 128});
+    s.fused_waves = num("VASR_FUSED_WAVES", 0, {0, 8, 16});
     s.fused_residual = num("VASR_NO_FUSED_RESIDUAL", 0, {0, 1}) == 0;
     s.beam_group = num("VASR_BEAM_GROUP", -1, {-1, 0, 1, 4});
     s.no_grouped = num("VASR_NO_GROUPED", 0, {0, 1}) != 0;
@@ -48,6 +49,9 @@ const vasr::DevSwitches& vasr::dev_switches() {
 extern "C" {
 
 int vasr_fused_tile_choice(int64_t tiles128, int compute_units) { return vasr::fused_tile_choice(tiles128, compute_units); }
+int vasr_fused_waves_choice(int kernel, int dual, int tile_cols) {
+  return vasr::fused_waves_choice(kernel, dual != 0, tile_cols, vasr::dev_switches().fused_waves);
+}
 
 static __global__ void dev_noop_kernel() {}
 

@@ -25,6 +25,7 @@ struct DevSwitches {
   bool fused = true;            // VASR_FUSED=0: depthwise and GEMM of a 256-channel sub-block as two kernels
   int fused_min_tiles = 0;      // VASR_FUSED_MIN_TILES=n: fuse from n tiles on, whatever the round-filling rule says
   int fused_tile = 0;           // VASR_FUSED_TILE=64|128: pins the fused kernel's tile width
+  int fused_waves = 0;          // VASR_FUSED_WAVES=8|16: pins the wavefronts per workgroup of the fused kernel's 128-frame tile
   bool fused_residual = true;   // VASR_NO_FUSED_RESIDUAL=1: a block's residual branch as its own GEMM, not as a second K range
   int beam_group = -1;          // VASR_BEAM_GROUP=0|1: always one wavefront per utterance, 4: always four
   bool no_grouped = false;      // VASR_NO_GROUPED=1: every grouped layer as its block-diagonal dense form (no grouped GEMM)
@@ -253,7 +254,10 @@ struct FusedLaunch {
   const float* x2; int64_t ldx2; const int32_t* lens2; AmaxTab amax_x2;   // residual source (nullptr = none)
   int32_t batch, kernel;
   int32_t tile_cols;                           // frames per workgroup: 128 (0 = default) or 64
+  int32_t waves;                               // wavefronts per workgroup of the 128-frame tile: 8 or 16 (0 = default)
 };
+// wavefronts per workgroup launch_fused_dwpw takes: `forced` (8 | 16, DevSwitches::fused_waves) or its default (forced = 0)
+int fused_waves_choice(int kernel, bool dual, int tile_cols, int forced);
 bool fused_dwpw_supported(int channels, int cout, int kernel, int stride, int dilation);
 // Which form a 256-channel sub-block takes for `tiles128` tiles of 128 frames (batch x padded frames / 128) on `cus` free
 // compute units: 128 or 64 = the fused kernel on tiles of that many frames, 0 = depthwise and GEMM as two kernels.
