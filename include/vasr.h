@@ -522,6 +522,50 @@ VASR_API int vasr_resample_f32(const float* d_in, int64_t ld_in, const int64_t* 
                       int nwin, int num_table, double ratio, float* d_out, int64_t ld_out, int64_t* d_len_out,
                       vasr_stream stream);
 
+/* Leading / trailing silence trim of a padded batch: AudioSegment(trim=True) (parts/segment.py:19-32) ->
+ * librosa.effects.trim(samples, top_db) of librosa < 0.10, which the shipped QuartzNet15x5 config turns on
+ * (AudioToTextDataLayer.trim_silence: true).  Third-party arithmetic restated from its published form, parity unpinned
+ * (librosa is not available to the tests; tests/trim_reference.py is the float64 restatement they use).
+ * Per row of n = clamp(d_len[b], 0, ld_in) samples x, with frame_length (librosa: 2048), hop_length (512), top_db (60):
+ *   y      = x padded by frame_length / 2 on both sides in numpy's `reflect` mode: periodic mirroring with period 2 (n - 1),
+ *            the edge sample not repeated; for n == 1 every padded sample is that sample;
+ *   F      = 1 + n / hop_length frames; frame f covers y[f hop : f hop + frame_length]; mse[f] = the mean of its squares;
+ *   ref    = max_f mse[f], amin = 1e-10; frame f is NON-SILENT iff
+ *            10 log10(max(amin, mse[f])) - 10 log10(max(amin, ref)) > -top_db,
+ *            decided here in the product form max(amin, mse[f]) > max(amin, ref) * 10^(-top_db / 10), in float64, the factor
+ *            computed on the host (squares and sums are float64 too: a float32 square is exact there);
+ *   start  = first * hop, end = min(n, (last + 1) * hop) over the first and last non-silent frame; start = end = 0 if none;
+ *   d_out[b] = x[start : end] bit for bit, then zeros up to ld_out; d_len_out[b] = end - start; d_start[b] = start.
+ * Consequences, as in librosa:
+ *   - a row whose loudest frame has mse < 1e-10 is NOT trimmed: every frame sits at the amin floor, 0 dB below ref (all-zero
+ *     rows, rows at the 1e-6 level);
+ *   - for top_db > 0 the loudest frame is always non-silent; with frame_length >= 2 hop_length and top_db > 3.02 so is the
+ *     frame in front of the last one whenever the last one is (it holds every sample the last one mirrors: at least half its
+ *     energy), hence d_len_out[b] >= min(n, hop_length).  (With frame_length == hop_length a row whose only loud frame is
+ *     the last one, which starts at n when hop_length divides n, comes out empty.);
+ *   - n == 0 gives start = d_len_out = 0; an inner gap is kept.
+ * int16 rows (the _pcm16 form): energies are of value * 2^-15, as AudioSegment scales -- the scale matters only through
+ * amin --; the copy stays int16.
+ * Samples at or beyond a row's length are never read as data (the mirror indexes inside [0, n)): the caller's padding may
+ * hold anything.  A row's outputs do not depend on the other rows, on the batch size, on ld_in or on the row's alignment.
+ * Three launches, no atomics, no host synchronisation, no handle.  EVERY element of every non-NULL output is written.
+ * d_out must not alias d_in; ld_out >= ld_in; ld_in == 0 is legal; d_start may be NULL.
+ * The chunk sums go through d_workspace: vasr_trim_silence_workspace_bytes(batch, ld_in, frame_length, hop_length) bytes of
+ * device memory at any address, contents undefined before and after (8 bytes per hop_length samples + 8 per row + 512); the
+ * function is host only and returns 0 for arguments the calls refuse.
+ * NULL d_in / d_len / d_out / d_len_out / d_workspace, d_out == d_in, batch <= 0, a negative ld, ld_out < ld_in, a non-finite
+ * top_db and a workspace smaller than required (the byte count is in vasr_last_error()) return VASR_ERR_INVALID; hop_length < 1,
+ * frame_length not a multiple of hop_length or frame_length > 8192 return VASR_ERR_UNSUPPORTED with the limit in
+ * vasr_last_error(); an argument error wins over the limit -- all before a device is touched.  DESIGN section 7f has the
+ * measured times.  (ABI 8) */
+VASR_API size_t vasr_trim_silence_workspace_bytes(int batch, int64_t ld_in, int frame_length, int hop_length);
+VASR_API int vasr_trim_silence_f32(const float* d_in, int64_t ld_in, const int64_t* d_len, int batch, float top_db,
+                                   int frame_length, int hop_length, float* d_out, int64_t ld_out, int64_t* d_len_out,
+                                   int64_t* d_start, void* d_workspace, size_t workspace_bytes, vasr_stream stream);
+VASR_API int vasr_trim_silence_pcm16(const int16_t* d_in, int64_t ld_in, const int64_t* d_len, int batch, float top_db,
+                                     int frame_length, int hop_length, int16_t* d_out, int64_t ld_out, int64_t* d_len_out,
+                                     int64_t* d_start, void* d_workspace, size_t workspace_bytes, vasr_stream stream);
+
 /* The fused call can cut the batch into `slices` contiguous parts (1..4; default 1 = off, because on MI355X it
  * measured slower: 11.7 -> 13.5 ms at 2 slices) and run each on its own
  * internal HIP stream, forked from / joined to `stream` with events: one part's HBM-bound kernels (depthwise,

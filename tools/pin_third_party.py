@@ -7,7 +7,7 @@ Run this script ONCE on a machine that has the packages -- e.g. `pip install "li
 kenlm` -- and commit what it writes: from then on `tests/test_thirdparty_pins.py` compares BOTH the CPU oracle and the
 device kernels with the packages' own outputs instead of skipping with "parity unpinned".
 
-    python tools/pin_third_party.py [--out tests/golden] [--only mel,resample,stftconv,beam]
+    python tools/pin_third_party.py [--out tests/golden] [--only mel,resample,stftconv,beam,trim]
 
 fixture                                 produced by (reference call site)                              pins
 tests/golden/thirdparty_mel.npz         librosa.filters.mel(16000, 512, n_mels=64, fmin=0, fmax=8000)  oracle.slaney_mel_filterbank,
@@ -19,6 +19,9 @@ tests/golden/thirdparty_stftconv.npz    torch_stft.STFT(512, 160, 320, "hann").t
 tests/golden/thirdparty_beam.npz        pyctcdecode.build_ctcdecoder(vocab, kenlm_model_path=arpa,     oracle/beam_oracle.decode_beams,
                                         alpha, beta).decode_beams(probs, beam_width)                   vasr_beam_search_f32 (row A12)
                                         (nemo/collections/asr/beam_search_decoder.py:82-102)
+tests/golden/thirdparty_trim.npz        librosa.effects.trim(samples, top_db) of librosa < 0.10         tests/trim_reference.trim_bounds,
+                                        (parts/segment.py:24-28, AudioSegment(trim=True)), a fifth     vasr_trim_silence_f32 / _pcm16
+                                        piece: every row of the case table of tests/trim_reference.py
 
 Inputs are regenerated from seeds by the tests (viet_asr_amd.synth), except where the package output depends on an input
 file: those inputs are stored in the fixture.  Only numpy arrays are written -- data, no package source.
@@ -136,12 +139,33 @@ def pin_beam(out):
     np.savez_compressed(os.path.join(out, "thirdparty_beam.npz"), **store)
 
 
+def pin_trim(out):
+    """librosa's own (start, end) for every row of the trim tests' case table, next to the restatement's; the rows themselves are
+    regenerated from the table's seeds by the tests."""
+    import librosa
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import trim_reference as R
+    names, got, want = [], [], []
+    for i, row in enumerate(R.TABLE):
+        for dtype in R.DTYPES:
+            c = R.case(i, dtype)
+            if c["n"] == 0:
+                continue                                                                # np.pad refuses an empty row: librosa raises
+            x = R.as_float64(c["x"]).astype(np.float32)                                 # what AudioSegment hands over
+            _, idx = librosa.effects.trim(x, top_db=c["top_db"], frame_length=c["frame_length"], hop_length=c["hop_length"])
+            names.append(f"{row[0]}/{dtype}"), got.append([int(idx[0]), int(idx[1])]), want.append([c["start"], c["end"]])
+    got, want = np.array(got, dtype=np.int64), np.array(want, dtype=np.int64)
+    np.savez_compressed(os.path.join(out, "thirdparty_trim.npz"), names=np.array(names), bounds=got, restated=want,
+                        versions=str(versions("librosa", "numpy")))
+    print("trim", len(names), "rows | rows where the restatement differs from librosa:", int((got != want).any(axis=1).sum()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
-    ap.add_argument("--only", default="mel,resample,stftconv,beam")
+    ap.add_argument("--only", default="mel,resample,stftconv,beam,trim")
     a = ap.parse_args()
-    todo = {"mel": pin_mel, "resample": pin_resample, "stftconv": pin_stftconv, "beam": pin_beam}
+    todo = {"mel": pin_mel, "resample": pin_resample, "stftconv": pin_stftconv, "beam": pin_beam, "trim": pin_trim}
     failed = []
     for name in a.only.split(","):
         try:

@@ -70,6 +70,11 @@ SIGNATURES = {
                                                C.c_size_t, _P]),
     "vasr_pcm16_to_f32": (C.c_int, [_P, C.c_int64, _P, _P]),
     "vasr_resample_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, C.c_int, C.c_int, C.c_double, _P, C.c_int64, _P, _P]),
+    "vasr_trim_silence_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int, C.c_int]),
+    "vasr_trim_silence_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_float, C.c_int, C.c_int, _P, C.c_int64, _P, _P, _P,
+                                        C.c_size_t, _P]),
+    "vasr_trim_silence_pcm16": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_float, C.c_int, C.c_int, _P, C.c_int64, _P, _P, _P,
+                                          C.c_size_t, _P]),
     "vasr_set_gemm_mode": (C.c_int, [_P, C.c_int]),
     "vasr_get_gemm_mode": (C.c_int, [_P]),
     "vasr_set_slices": (C.c_int, [_P, C.c_int]),

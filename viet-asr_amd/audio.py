@@ -99,6 +99,40 @@ def resample(signal, length, sr_in, sr_out, filter="kaiser_best"):
     return y, ln_out
 
 
+def trim_silence(signal, length, top_db=60.0, frame_length=2048, hop_length=512, out=None, start=None, workspace=None):
+    """signal [B, L] float32 or int16 cuda (padding: anything), length [B] int64 cuda ->
+    (trimmed [B, L] of the same dtype, zero behind each row, length' [B] int64, start [B] int64).
+
+    ``AudioSegment(trim=True)`` -> ``librosa.effects.trim(samples, top_db)`` (parts/segment.py:19-32; librosa < 0.10,
+    third-party arithmetic restated from its published form, parity unpinned) on the device: vasr_trim_silence_f32 / _pcm16 in
+    include/vasr.h have the semantics.  Three launches on the current stream, no synchronisation: the padded width stays L.
+    out / start / workspace: buffers of the caller's to write into ([B, L] of signal's dtype; [B] int64; uint8 of at least
+    vasr_trim_silence_workspace_bytes) instead of fresh ones."""
+    if signal.device.type != "cuda":
+        raise _lib.VasrError("viet-asr_amd kernels need HIP-resident tensors; there is no CPU fallback for this path")
+    if signal.dtype not in (torch.float32, torch.int16) or signal.dim() != 2:
+        raise ValueError("trim_silence expects a [B, L] float32 or int16 cuda tensor")
+    x = signal.contiguous()
+    ln = length.to(device=x.device, dtype=torch.int64).contiguous()
+    B, L = x.shape
+    L_lib = _lib.lib()
+    if out is None:
+        out = torch.empty((B, L), dtype=x.dtype, device=x.device)
+    if out.dtype != x.dtype or out.device != x.device or tuple(out.shape) != (B, L) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous [B, L] tensor of signal's dtype on its device")
+    ln_out = torch.empty((B,), dtype=torch.int64, device=x.device)
+    if start is None:
+        start = torch.empty((B,), dtype=torch.int64, device=x.device)
+    need = int(L_lib.vasr_trim_silence_workspace_bytes(B, L, int(frame_length), int(hop_length)))
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+    entry = L_lib.vasr_trim_silence_pcm16 if x.dtype == torch.int16 else L_lib.vasr_trim_silence_f32
+    _lib.check(entry(x.data_ptr(), L, ln.data_ptr(), B, float(top_db), int(frame_length), int(hop_length), out.data_ptr(),
+                     out.shape[1], ln_out.data_ptr(), start.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                     torch.cuda.current_stream(x.device).cuda_stream))
+    return out, ln_out, start
+
+
 def pcm16_to_float(pcm):
     """int16 cuda tensor -> float32 / 32768 on the device (halves the host->device bytes of a batch)."""
     if pcm.device.type != "cuda" or pcm.dtype != torch.int16:

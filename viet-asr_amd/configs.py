@@ -62,18 +62,22 @@ def builtin(name):
     reference side of the golden generator); the builtin 15x5 keeps ``stft_conv=False`` like the two Vietnamese configs,
     which is how tests/golden/make_golden.py runs the reference.  Loading the real YAML selects the conv-STFT's
     periodic window (frontend_tables.frontend_description)."""
+    # trim: the YAML's AudioToTextDataLayer.trim_silence (quartznet15x5.yaml:6 true; quartznet12x1*.yaml false) -- what
+    # VietASR's trim_silence="config" follows
+    trim = False
     if name in ("quartznet12x1_vi", "quartznet12x1_vi.yaml"):
         body, labels = _quartznet(1, False), LABELS_VI
     elif name in ("quartznet12x1", "quartznet12x1.yaml"):
         body, labels = _quartznet(1, False), LABELS_VI_DIGITS
     elif name in ("quartznet15x5", "quartznet15x5.yaml"):
-        body, labels = _quartznet(5, True), LABELS_EN
+        body, labels, trim = _quartznet(5, True), LABELS_EN, True
     elif name in ("jasper10x5dr", "jasper10x5dr.yaml"):
         body, labels = _jasper10x5dr(), LABELS_EN
     else:
         raise ValueError(f"unknown builtin model {name!r}")
     return {
         "model": name.replace(".yaml", ""),
+        "AudioToTextDataLayer": {"max_duration": 16.7, "trim_silence": trim},
         "AudioToMelSpectrogramPreprocessor": dict(_PRE),
         "JasperEncoder": {"activation": "relu", "conv_mask": True, "jasper": body},
         "labels": list(labels),

@@ -2007,6 +2007,56 @@ int vasr_resample_f32(const float* d_in, int64_t ld_in, const int64_t* d_len_in,
   return check_launch("resample");
 }
 
+static bool trim_shape_supported(int frame_length, int hop_length) {
+  return hop_length >= 1 && frame_length >= hop_length && frame_length <= kTrimMaxFrame && frame_length % hop_length == 0;
+}
+
+size_t vasr_trim_silence_workspace_bytes(int batch, int64_t ld_in, int frame_length, int hop_length) {
+  if (batch <= 0 || ld_in < 0 || !trim_shape_supported(frame_length, hop_length)) return 0;
+  return trim_workspace_bytes(batch, ld_in, frame_length, hop_length);
+}
+
+extern "C++" {
+template <typename T>
+static int trim_silence(const T* d_in, int64_t ld_in, const int64_t* d_len, int batch, float top_db, int frame_length,
+                        int hop_length, T* d_out, int64_t ld_out, int64_t* d_len_out, int64_t* d_start, void* d_workspace,
+                        size_t workspace_bytes, vasr_stream stream) {
+  // every refusal comes before a device is touched
+  if (!d_in || !d_len || !d_out || !d_len_out) return fail(VASR_ERR_INVALID, "trim_silence: NULL pointer");
+  if (d_in == d_out) return fail(VASR_ERR_INVALID, "trim_silence: d_out must not alias d_in");
+  if (batch <= 0 || ld_in < 0 || ld_out < 0 || ld_out < ld_in)
+    return fail(VASR_ERR_INVALID, "trim_silence: batch %d, ld_in %lld, ld_out %lld (ld_out >= ld_in >= 0)", batch, (long long)ld_in,
+                (long long)ld_out);
+  if (!std::isfinite(top_db)) return fail(VASR_ERR_INVALID, "trim_silence: top_db is not finite");
+  if (!d_workspace) return fail(VASR_ERR_INVALID, "trim_silence: NULL workspace");
+  if (!trim_shape_supported(frame_length, hop_length))
+    return fail(VASR_ERR_UNSUPPORTED, "trim_silence: frame_length %d, hop_length %d: hop_length >= 1 and frame_length a multiple of "
+                "it, at most %d", frame_length, hop_length, kTrimMaxFrame);
+  const size_t need = trim_workspace_bytes(batch, ld_in, frame_length, hop_length);
+  if (workspace_bytes < need)
+    return fail(VASR_ERR_INVALID, "trim_silence: workspace of %zu bytes, %zu needed (vasr_trim_silence_workspace_bytes)",
+                workspace_bytes, need);
+  const double factor = std::pow(10.0, -(double)top_db / 10.0);
+  launch_trim_silence<T>(d_in, ld_in, d_len, batch, factor, frame_length, hop_length, d_out, ld_out, d_len_out, d_start, d_workspace,
+                         static_cast<hipStream_t>(stream));
+  return check_launch("trim_silence");
+}
+}  // extern "C++"
+
+int vasr_trim_silence_f32(const float* d_in, int64_t ld_in, const int64_t* d_len, int batch, float top_db, int frame_length,
+                          int hop_length, float* d_out, int64_t ld_out, int64_t* d_len_out, int64_t* d_start, void* d_workspace,
+                          size_t workspace_bytes, vasr_stream stream) {
+  return trim_silence<float>(d_in, ld_in, d_len, batch, top_db, frame_length, hop_length, d_out, ld_out, d_len_out, d_start,
+                             d_workspace, workspace_bytes, stream);
+}
+
+int vasr_trim_silence_pcm16(const int16_t* d_in, int64_t ld_in, const int64_t* d_len, int batch, float top_db, int frame_length,
+                            int hop_length, int16_t* d_out, int64_t ld_out, int64_t* d_len_out, int64_t* d_start,
+                            void* d_workspace, size_t workspace_bytes, vasr_stream stream) {
+  return trim_silence<short>(d_in, ld_in, d_len, batch, top_db, frame_length, hop_length, d_out, ld_out, d_len_out, d_start,
+                             d_workspace, workspace_bytes, stream);
+}
+
 int vasr_set_gemm_mode(vasr_handle* h, int mode) {
   if (!h || mode < 0 || mode > 3)
     return fail(VASR_ERR_INVALID, "gemm mode must be 0 (fp32 MFMA), 1 (3 x bf16 split), 2 (2 x bf16 split, reduced) or "

@@ -413,6 +413,16 @@ void launch_pcm16_to_f32(const short* in, int64_t n, float* out, hipStream_t st)
 void launch_resample(const float* x, int64_t ld_in, const int64_t* len_in, int batch, const float* table, int nwin,
                      int num_table, double ratio, float* y, int64_t ld_out, int64_t* len_out, hipStream_t st);
 
+// ---- silence trim (trim.hip): librosa.effects.trim on a padded batch, include/vasr.h has the semantics ----
+// T = float or short (int16 PCM, energies of value * 2^-15).  factor = 10^(-top_db / 10) in double.  The chunk sums (float64)
+// and the row starts go through `workspace` (trim_workspace_bytes; any address: the first multiple of 256 inside it is
+// used).  The caller checks hop >= 1, frame_length a multiple of hop, ld_out >= ld_in >= 0; three launches, no host sync.
+constexpr int kTrimMaxFrame = 8192;
+size_t trim_workspace_bytes(int batch, int64_t ld_in, int frame_length, int hop);   // host only; SIZE_MAX where it does not fit
+template <typename T>
+void launch_trim_silence(const T* in, int64_t ld_in, const int64_t* len, int batch, double factor, int frame_length, int hop,
+                         T* out, int64_t ld_out, int64_t* len_out, int64_t* start, void* workspace, hipStream_t st);
+
 // ---- beam search (beam_wave.hip, beam_group.hip) ----
 struct BeamLm {  // device-resident hashed back-off n-gram model
   const void* vocab; int vcap;    // [vcap] 16-byte entries {u64 word hash | 1, i32 word id, u32 flags}, vcap a power of two

@@ -82,6 +82,9 @@ class AudioToTextDataLayer(_ManifestBatches, DataLayerNM):
 
     def __init__(self, manifest_filepath, labels, batch_size, sample_rate=16000, min_duration=0.1, max_duration=None,
                  shuffle=False, bucket_by_length=True, drop_last=False, pad_id=None, shard_by="duration", **_unused):
+        """``trim_silence`` (among the reference's options taken and not used here) does not act in this layer: it hands out
+        host tensors, and the trim (librosa.effects.trim) runs on the device in the engine call that consumes them --
+        ``VietASR.evaluate_manifest(..., trim_silence="config")`` follows the YAML's value, ``audio.trim_silence`` is the call."""
         super().__init__()
         self._sample_rate, self._batch_size, self._shuffle = sample_rate, batch_size, shuffle
         self.labels = list(labels)
@@ -125,7 +128,9 @@ class AudioToSpeechLabelDataLayer(_ManifestBatches, DataLayerNM):
     (parts/dataset.py:380-391).  Duration filtering as ``SpeechLabel`` (collections.py:195-203).  Labels are mapped by
     ``label2id``; an unknown one raises KeyError (here when the manifest is read, in the reference when the item is).
     Batches: signals zero padded to the batch maximum (seq_collate_fn), ``label`` [B] int64, ``label_length`` [B] int64, all
-    ones.  PCM WAV only; ``trim_silence`` and ``augmentor`` are not implemented.  Sharding, length buckets and
+    ones.  PCM WAV only; ``trim_silence`` and ``augmentor`` are not implemented HERE: the layer hands out host tensors, and the
+    trim (librosa.effects.trim) runs on the device, in the engine call that consumes them
+    (``engine.QuartzNetClassifier.evaluate_manifest(..., trim_silence=True)``, ``audio.trim_silence``).  Sharding, length buckets and
     ``utterance_order`` as in ``AudioToTextDataLayer``, whose defaults (no shuffle) it shares."""
 
     @property

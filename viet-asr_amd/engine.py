@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .audio import trim_silence as trim_audio
 from .frontend_tables import frontend_description
 
 
@@ -212,7 +213,19 @@ class QuartzNetCTC:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
 
-    def forward(self, wav, length, want_logp=False, want_pred=True, row_independent=False):
+    def frames_of(self, length):
+        """``frames(n)[1]`` for a [B] int64 tensor of sample counts, on its device: the encoded frames of each row alone -- the
+        conv chain of vasr_encoded_frames in integer tensor ops, for lengths that exist on the device only (trim_silence)."""
+        t = 1 + torch.div(length, self.hop, rounding_mode="floor")
+        for b in self._blocks:
+            k = b["kernel"] + (1 if b["kernel"] % 2 == 0 else 0)
+            pad = (b["dilation"] * k) // 2 - 1 if b["dilation"] > 1 else k // 2
+            for _ in range(b["repeat"]):
+                t = torch.div(t + (2 * pad - b["dilation"] * (k - 1) - 1), b["stride"], rounding_mode="floor") + 1
+        return t.to(torch.int32)
+
+    def forward(self, wav, length, want_logp=False, want_pred=True, row_independent=False, trim_silence=False,
+                _trim_buffers=None):
         """wav [B, L] f32 cuda (rows zero padded) -- or int16 PCM as it sits in a wav file: the front end scales it by 2^-15 as
         it reads it (vasr_transcribe_greedy_pcm16; the same bits as converting first) --, length [B] i64 cuda.
 
@@ -223,11 +236,22 @@ class QuartzNetCTC:
         padding at the padded end, padded frames decoded).  True makes ids / id_len of every row what a batch-1 call on
         that row alone returns, bit for bit (vasr_set_row_independent in include/vasr.h); every length must then
         exceed n_fft / 2, which the caller checks (the lengths live on the device here).
+
+        trim_silence=True cuts every row's leading and trailing silence on the device first, as ``AudioSegment(trim=True)``
+        does in front of the reference's front end (segment.py:24-28; ``audio.trim_silence``, int16 stays int16): three more
+        launches and no synchronisation -- the padded width stays L, so every frame count taken from L stays an upper
+        bound.  The dict then also carries "trim_start" [B] i64 (the first kept sample of each row) and "length" [B] i64 (the
+        trimmed lengths); ``frames_of(length)`` are the rows' own encoded frames.  With librosa's defaults a trimmed row keeps
+        at least 512 samples of a longer one, so the n_fft / 2 rule checked on the untrimmed lengths still holds.
         """
         if wav.device.type != "cuda" or wav.dtype not in (torch.float32, torch.int16) or not wav.is_contiguous():
             raise ValueError("wav must be a contiguous float32 (or int16 PCM) cuda tensor")
         if length.dtype != torch.int64 or length.device != wav.device:
             raise ValueError("length must be an int64 tensor on the same device")
+        trim_start = None
+        if trim_silence:
+            out, start = _trim_buffers if _trim_buffers is not None else (None, None)
+            wav, length, trim_start = trim_audio(wav, length, out=out, start=start)
         B, L = wav.shape
         _, t1 = self.frames(L)
         ws = self._workspace(B, L)
@@ -246,7 +270,10 @@ class QuartzNetCTC:
             pred.data_ptr() if pred is not None else None, ids.data_ptr(), id_len.data_ptr(),
             logp.data_ptr() if logp is not None else None, enc_len.data_ptr(),
             ws.data_ptr(), ws.numel(), _stream_ptr()))
-        return dict(ids=ids, id_len=id_len, pred=pred, enc_len=enc_len, logp=logp)
+        r = dict(ids=ids, id_len=id_len, pred=pred, enc_len=enc_len, logp=logp)
+        if trim_start is not None:
+            r["trim_start"], r["length"] = trim_start, length
+        return r
 
     def texts(self, ids, id_len):
         """Host side of helpers.py:32 -- ''.join(labels[c]) over the collapsed ids."""
@@ -256,15 +283,16 @@ class QuartzNetCTC:
             raise _lib.VasrError("beam search reported an internal overflow (id_len = -1) for rows %s" % (n < 0).nonzero()[0].tolist())
         return ["".join(self.labels[c] for c in ids[b, : n[b]]) for b in range(ids.shape[0])]
 
-    def transcribe(self, signals, row_independent=False):
+    def transcribe(self, signals, row_independent=False, trim_silence=False):
         """List of 1-D arrays (model sample rate; float, or int16 PCM) -> list of strings; zero-pad-to-max collate
-        (parts/dataset.py:14-53).  row_independent: see forward()."""
-        return self.launch(signals, row_independent).texts()
+        (parts/dataset.py:14-53).  row_independent, trim_silence: see forward()."""
+        return self.launch(signals, row_independent, trim_silence=trim_silence).texts()
 
-    def transcribe_beam(self, signals, beam_decoder, beam_width, row_independent=True):
+    def transcribe_beam(self, signals, beam_decoder, beam_width, row_independent=True, trim_silence=False):
         """Batched counterpart of the reference's beam wiring (infer.py:132-139, 159-160; batch 1 there): one forward
         pass for the log-probs, then viet_asr_amd.beam.BeamSearchDecoder over every row.  row_independent=True searches
-        each row over its own frames (and reflects it at its own end): the transcripts of batch-1 calls."""
+        each row over its own frames (and reflects it at its own end): the transcripts of batch-1 calls.  trim_silence: see
+        forward(); the rows' own frames then come from the trimmed lengths, on the device."""
         lens = [len(s) for s in signals]
         if row_independent and min(lens) <= self.frontend["n_fft"] // 2:
             raise ValueError(f"row-independent batching needs more than n_fft/2 = {self.frontend['n_fft'] // 2} samples "
@@ -273,8 +301,10 @@ class QuartzNetCTC:
         for i, s in enumerate(signals):
             batch[i, : lens[i]] = _pcm_to_float(s)
         r = self.forward(torch.from_numpy(batch).to(self.device), torch.tensor(lens, device=self.device),
-                         want_logp=True, want_pred=False, row_independent=row_independent)
+                         want_logp=True, want_pred=False, row_independent=row_independent, trim_silence=trim_silence)
         own = [self.frames(n)[1] for n in lens] if row_independent else None
+        if row_independent and trim_silence:
+            own = self.frames_of(r["length"])
         return beam_decoder.decode_batch(r["logp"], beam_width, frames=own)
 
     def forward_beam(self, wav, length, beam_decoder, beam_width, frames=None, overlap=True):
@@ -403,7 +433,7 @@ class QuartzNetCTC:
         return lf
 
     # -- pipelined host path: pinned staging, copies on their own stream, two batches in flight
-    def launch(self, signals, row_independent=False, after_forward=None):
+    def launch(self, signals, row_independent=False, after_forward=None, trim_silence=False):
         """Enqueue one batch and return at once; ``.texts()`` of the returned PendingBatch waits for it.
 
         Two staging slots alternate: while batch k computes, batch k+1 is collated into pinned memory and its
@@ -414,6 +444,8 @@ class QuartzNetCTC:
         after_forward(out): called with ``forward``'s result dict on the compute stream, right after the forward pass is
         enqueued and before its results are copied out -- device-side consumers of the ids (``metrics.ErrorRate.update``)
         hook in here; it must not synchronise.
+
+        trim_silence: see forward(); the slot keeps a second device buffer for the trimmed batch and one for the starts.
         """
         if len(signals) == 0:
             raise ValueError("empty batch")
@@ -422,7 +454,7 @@ class QuartzNetCTC:
             self._copy_stream = torch.cuda.Stream(self.device)
         slot = self._slots[self._launched % 2]
         self._launched += 1
-        return slot.launch(signals, row_independent, after_forward)
+        return slot.launch(signals, row_independent, after_forward, trim_silence)
 
 
 class QuartzNetClassifier:
@@ -470,7 +502,7 @@ class QuartzNetClassifier:
         self._ws = None
         self._row_independent = False
 
-    def forward(self, wav, length, offsets=None, softmax=False, row_independent=False, want_mel=False):
+    def forward(self, wav, length, offsets=None, softmax=False, row_independent=False, want_mel=False, trim_silence=False):
         """wav [B, L] f32 cuda (rows zero padded), length [B] i64 cuda -> logits [B, num_classes] f32, or probabilities
         (softmax=True: F.softmax(logits, -1)).  Enqueued on the current stream; nothing synchronises.
 
@@ -479,11 +511,14 @@ class QuartzNetClassifier:
         torch.manual_seed); an explicit array makes the crop reproducible without the generator.  row_independent: as
         QuartzNetCTC.forward -- every row is reflected, cut (its offset clamped into its own width) or centred as a batch-1
         call on it alone would be, and its output is that call's, bit for bit; every length must then exceed n_fft / 2.
-        want_mel: return (out, mel [B, n_mels, audio_length]), the encoder's input."""
+        want_mel: return (out, mel [B, n_mels, audio_length]), the encoder's input.  trim_silence: as QuartzNetCTC.forward --
+        every row's leading and trailing silence is cut on the device in front of the front end, the padded width stays L."""
         if wav.device.type != "cuda" or wav.dtype != torch.float32 or not wav.is_contiguous():
             raise ValueError("wav must be a contiguous float32 cuda tensor")
         if length.dtype != torch.int64 or length.device != wav.device:
             raise ValueError("length must be an int64 tensor on the same device")
+        if trim_silence:
+            wav, length, _ = trim_audio(wav, length)
         B, L = wav.shape
         T = self.handle.mel_frames(L)
         if offsets is None and T > self.audio_length:
@@ -508,11 +543,13 @@ class QuartzNetClassifier:
             self._ws.numel(), _stream_ptr()))
         return (out, mel) if want_mel else out
 
-    def classify(self, signals, offsets=None, row_independent=False):
+    def classify(self, signals, offsets=None, row_independent=False, trim_silence=False):
         """List of 1-D arrays (model sample rate; float, or integer PCM) -> the arg-max class index per signal, or its label
         where ``labels`` was given; zero-pad-to-max collate (parts/dataset.py:14-53).  Short inputs follow QuartzNetCTC's
-        rules: no empty batch or signal, and more than n_fft / 2 samples per signal with row_independent."""
-        out = self.forward(*self._collate(signals, row_independent), offsets=offsets, row_independent=row_independent)
+        rules: no empty batch or signal, and more than n_fft / 2 samples per signal with row_independent.  trim_silence: see
+        forward()."""
+        out = self.forward(*self._collate(signals, row_independent), offsets=offsets, row_independent=row_independent,
+                           trim_silence=trim_silence)
         idx = out.argmax(-1).cpu().tolist()
         return [self.labels[i] for i in idx] if self.labels is not None else idx
 
@@ -531,7 +568,7 @@ class QuartzNetClassifier:
             batch[i, : lens[i]] = _pcm_to_float(np.asarray(s))
         return torch.from_numpy(batch).to(self.device), torch.tensor(lens, device=self.device)
 
-    def classify_topk(self, signals, k, offsets=None, row_independent=False):
+    def classify_topk(self, signals, k, offsets=None, row_independent=False, trim_silence=False):
         """``classify``'s input -> per signal the list of its k best (label or index, softmax probability) pairs, best first:
         larger logit first, the lower class index first among equal ones (``stages.classification_scores``).  The same
         collate and forward pass as ``classify``; one device-to-host copy at the end."""
@@ -539,14 +576,16 @@ class QuartzNetClassifier:
         k = int(k)
         if not 1 <= k <= min(16, self.num_classes):
             raise ValueError(f"k must be in 1..{min(16, self.num_classes)}, got {k}")
-        out = self.forward(*self._collate(signals, row_independent), offsets=offsets, row_independent=row_independent)
+        out = self.forward(*self._collate(signals, row_independent), offsets=offsets, row_independent=row_independent,
+                           trim_silence=trim_silence)
         top = stages.classification_scores(out, k=k, want_prob=True)
         # one copy: the indices (exact in float32, below 2^24) next to the probabilities
         both = torch.cat([top["indices"].to(torch.float32), top["probs"]], dim=1).cpu().tolist()
         name = (lambda i: self.labels[i]) if self.labels is not None else (lambda i: i)
         return [[(name(int(r[j])), r[k + j]) for j in range(k)] for r in both]
 
-    def evaluate_manifest(self, manifest_filepath, batch_size=64, top_k=(1,), offsets=None, row_independent=False):
+    def evaluate_manifest(self, manifest_filepath, batch_size=64, top_k=(1,), offsets=None, row_independent=False,
+                          trim_silence=False):
         """Top-k accuracy and evaluation loss over a labelled manifest: -> (predictions, ``TopKAccuracy.compute()``), the
         dict {"accuracy": {k: float}, "correct": {k: int}, "samples": int, "eval_loss": float}; predictions: the top-1 class
         (label, or index without ``labels``) per kept manifest entry, in manifest order.
@@ -559,7 +598,8 @@ class QuartzNetClassifier:
         batch crosses from pinned memory, and its scoring (one vasr_class_scores_f32 launch: top-1, rank and loss) is
         enqueued right behind its forward pass; the only synchronisation before the final ``compute`` is the copy of the
         predictions after the last batch.  offsets: None (drawn per batch as ``forward`` draws them) or one crop offset per
-        kept manifest entry, in manifest order."""
+        kept manifest entry, in manifest order.  trim_silence: see forward() -- the data layer hands out untrimmed host
+        tensors (its own ``trim_silence`` is not implemented); the trim happens here, on the device, per batch."""
         from . import stages
         from .data_layer import AudioToSpeechLabelDataLayer
         from .metrics import TopKAccuracy
@@ -585,7 +625,8 @@ class QuartzNetClassifier:
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(self.device))
             staged = [(e, h) for e, h in staged if not e.query()] + [(done, host)]
-            out = self.forward(dev[0], dev[1], offsets=dev[3] if off is not None else None, row_independent=row_independent)
+            out = self.forward(dev[0], dev[1], offsets=dev[3] if off is not None else None, row_independent=row_independent,
+                               trim_silence=trim_silence)
             scores = stages.classification_scores(out, dev[2], k=1)
             metric.add_scores(scores["rank"], scores["loss"])
             picks.append(scores["indices"].view(-1))
@@ -626,12 +667,20 @@ class _Slot:
     def __init__(self, eng):
         self.eng = eng
         self.pin = self.dev = None
+        self.dev_trim = self.dev_start = None     # trim_silence: the trimmed batch and the rows' starts
         self.pin_len = self.dev_len = None
         self.pin_ids = self.pin_idlen = None
         self.out = None               # device outputs of the batch in flight (kept alive until its results are read)
         self.pending = None
         self.ev_h2d = torch.cuda.Event()
         self.ev_out = torch.cuda.Event()
+
+    def _reserve_trim(self, B, nbytes):
+        dev = self.eng.device
+        if self.dev_trim is None or self.dev_trim.numel() < nbytes:
+            self.dev_trim = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        if self.dev_start is None or self.dev_start.numel() < B:
+            self.dev_start = torch.empty(B, dtype=torch.int64, device=dev)
 
     def _reserve(self, B, nbytes, t1, pcm16):
         dev = self.eng.device
@@ -645,7 +694,7 @@ class _Slot:
         if self.pin_ids is None or self.pin_ids.numel() < B * t1:
             self.pin_ids = torch.empty(B * t1, dtype=torch.int32, pin_memory=True)
 
-    def launch(self, signals, row_independent=False, after_forward=None):
+    def launch(self, signals, row_independent=False, after_forward=None, trim_silence=False):
         eng = self.eng
         if self.pending is not None:
             self.pending.texts()          # the slot's previous batch: fetch before its buffers are overwritten
@@ -664,6 +713,10 @@ class _Slot:
         with torch.cuda.device(eng.device):
             self.ev_out.synchronize()     # batch k-2 has left the device buffers
             self._reserve(B, nbytes, t1, pcm16)
+            trim_buffers = None
+            if trim_silence:
+                self._reserve_trim(B, nbytes)
+                trim_buffers = (self.dev_trim[:nbytes].view(dtype).view(B, L), self.dev_start[:B])
             host = self.pin[:nbytes].view(dtype).view(B, L).numpy()
             for i, s in enumerate(signals):
                 if not pcm16:
@@ -682,7 +735,8 @@ class _Slot:
             comp.wait_event(self.ev_h2d)
             wav = self.dev[:nbytes].view(dtype).view(B, L)
             # (int16 PCM goes into the front end as it is: scaled by 2^-15 in the STFT kernel's staging load)
-            self.out = eng.forward(wav, self.dev_len[:B], want_pred=False, row_independent=row_independent)
+            self.out = eng.forward(wav, self.dev_len[:B], want_pred=False, row_independent=row_independent,
+                                   trim_silence=trim_silence, _trim_buffers=trim_buffers)
             if after_forward is not None:
                 after_forward(self.out)
             self.pin_ids[: B * t1].copy_(self.out["ids"].view(-1), non_blocking=True)

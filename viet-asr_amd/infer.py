@@ -20,15 +20,30 @@ from .engine import QuartzNetCTC
 from .helpers import post_process_predictions
 
 
-def alignment_entries(chars, start, end, logp, frame_seconds):
+def resolve_trim_silence(trim_silence, model_definition):
+    """The ``trim_silence`` argument of VietASR's batch calls -> bool.  False | True | "config": "config" follows the model
+    definition's ``AudioToTextDataLayer.trim_silence`` (the shipped quartznet15x5.yaml sets it, the 12x1 ones do not), which is
+    what the reference's data layer would have done to every clip of an evaluation with that YAML."""
+    if isinstance(trim_silence, str):
+        if trim_silence != "config":
+            raise ValueError(f"trim_silence must be False, True or 'config', got {trim_silence!r}")
+        return bool((model_definition.get("AudioToTextDataLayer") or {}).get("trim_silence", False))
+    if trim_silence not in (False, True):
+        raise ValueError(f"trim_silence must be False, True or 'config', got {trim_silence!r}")
+    return bool(trim_silence)
+
+
+def alignment_entries(chars, start, end, logp, frame_seconds, offset=0.0):
     """The host side of ``VietASR.align`` for one row that has a path: chars (the row's labels, one per token) with their
     frame spans [start[j], end[j]) and log-probs logp[j] -> (chars, words): lists of {"char" | "word", "start", "end",
     "logp"}, times in seconds = frames * frame_seconds.  Words are the maximal runs of non-whitespace labels, as the error
     rates split them (metrics.space_ids); a word starts with its first character, ends with its last, and its "logp" is the
-    sum of its characters', in order.  Whitespace labels are characters and belong to no word."""
+    sum of its characters', in order.  Whitespace labels are characters and belong to no word.  offset (seconds) is added to
+    every time: where the row was cut out of a longer recording (trim_silence), the times are the recording's."""
     cs, ws, run = [], [], []
     for j, c in enumerate(chars):
-        cs.append({"char": c, "start": int(start[j]) * frame_seconds, "end": int(end[j]) * frame_seconds, "logp": float(logp[j])})
+        cs.append({"char": c, "start": int(start[j]) * frame_seconds + offset, "end": int(end[j]) * frame_seconds + offset,
+                   "logp": float(logp[j])})
         if not c.isspace():
             run.append(cs[-1])
         if run and (c.isspace() or j == len(chars) - 1):
@@ -117,17 +132,26 @@ class VietASR:
                 return signals                      # int16 PCM goes to the device as it is (scaled there)
         return [self._to_model_rate(s, sample_rate) for s in signals]
 
-    def transcribe_batch(self, signals, sample_rate=None, row_independent=False, decoder="greedy"):
+    def _trim(self, trim_silence):
+        return resolve_trim_silence(trim_silence, self.model_definition)
+
+    def transcribe_batch(self, signals, sample_rate=None, row_independent=False, decoder="greedy", trim_silence=False):
         """Transcripts of a list of 1-D signals through the fused one-call path.  row_independent=True: every
         transcript is what the signal alone would give (engine.QuartzNetCTC.forward); default: the reference's
         padded-batch semantics.  decoder="beam" (instances built with decoder="beam" only) runs this instance's beam
-        search + LM over the batch instead of the greedy collapse."""
+        search + LM over the batch instead of the greedy collapse.
+
+        trim_silence: False | True | "config" ("config": what the model definition's ``AudioToTextDataLayer.trim_silence`` says;
+        ``resolve_trim_silence``).  True cuts every signal's leading and trailing silence on the device, after any resampling
+        and in front of the front end, as ``AudioSegment(trim=True)`` does (segment.py:24-28; ``audio.trim_silence``)."""
+        trim = self._trim(trim_silence)
         if decoder == "greedy":
-            return self._fused_engine().transcribe(self._batch_signals(signals, sample_rate), row_independent)
+            return self._fused_engine().transcribe(self._batch_signals(signals, sample_rate), row_independent, trim_silence=trim)
         if decoder != "beam" or self.mode != "beam":
             raise ValueError("decoder must be 'greedy', or 'beam' on an instance constructed with decoder='beam'")
         sigs = [self._to_model_rate(s, sample_rate) for s in signals]
-        return self._fused_engine().transcribe_beam(sigs, self.beam.decoder, self.beam.beam_width, row_independent)
+        return self._fused_engine().transcribe_beam(sigs, self.beam.decoder, self.beam.beam_width, row_independent,
+                                                    trim_silence=trim)
 
     def _manifest_batches(self, manifest_filepath, batch_size):
         """-> (the entries of a NeMo JSON-lines manifest, or of several separated by commas; a generator of (idx, signals): the
@@ -150,7 +174,7 @@ class VietASR:
                 yield idx, sigs
         return entries, batches()
 
-    def _walk_manifest(self, manifest_filepath, batch_size, row_independent, after_forward=None):
+    def _walk_manifest(self, manifest_filepath, batch_size, row_independent, after_forward=None, trim_silence=False):
         """The entries of a NeMo JSON-lines manifest and their greedy transcripts, in manifest order: sorted by duration, cut
         into batches of ``batch_size``, two batches in flight (engine.QuartzNetCTC.launch).  after_forward(entries, idx) -> the
         ``launch`` hook of the batch holding entries ``idx`` (or None)."""
@@ -164,14 +188,14 @@ class VietASR:
 
         for idx, sigs in batches:
             hook = after_forward(entries, idx) if after_forward is not None else None
-            pending.append((idx, self._fused_engine().launch(sigs, row_independent, hook)))
+            pending.append((idx, self._fused_engine().launch(sigs, row_independent, hook, trim_silence=trim_silence)))
             if len(pending) == 2:
                 collect(pending.pop(0))
         for job in pending:
             collect(job)
         return entries, hyps
 
-    def transcribe_manifest(self, manifest_filepath, batch_size=64, row_independent=True):
+    def transcribe_manifest(self, manifest_filepath, batch_size=64, row_independent=True, trim_silence=False):
         """Greedy transcripts of every entry of a NeMo JSON-lines manifest (parts/manifest.py:21-94), in manifest order,
         plus the word error rate against the entries' ``text`` (None when no entry has one).
 
@@ -182,9 +206,9 @@ class VietASR:
 
         The rate is ``data_layer.word_error_rate`` on the RAW manifest text, computed on the host after the last batch.
         ``evaluate_manifest`` scores the parsed tokens on the device instead (WER and CER); the two word error rates
-        differ only where a reference contains characters outside the labels."""
+        differ only where a reference contains characters outside the labels.  trim_silence: as ``transcribe_batch``."""
         from .data_layer import word_error_rate
-        entries, hyps = self._walk_manifest(manifest_filepath, batch_size, row_independent)
+        entries, hyps = self._walk_manifest(manifest_filepath, batch_size, row_independent, trim_silence=self._trim(trim_silence))
         refs = [e.get("text") for e in entries]
         scored = [i for i, r in enumerate(refs) if r]
         wer = word_error_rate([hyps[i] for i in scored], [refs[i] for i in scored]) if scored else None
@@ -203,7 +227,7 @@ class VietASR:
         return ref, ref_len
 
     def evaluate_manifest(self, manifest_filepath, batch_size=64, row_independent=True, breakdown=False, nbest=None,
-                          eval_loss=False):
+                          eval_loss=False, trim_silence=False):
         """``transcribe_manifest``'s walk with WER and CER scored on the device: -> (hyps, ``ErrorRate.compute()``), the
         dict {"wer", "cer", "word_edits", "ref_words", "char_edits", "ref_chars"}.
 
@@ -231,15 +255,19 @@ class VietASR:
         "infeasible" per utterance: ``loss_sum / scored``, the mean over the utterances that have a path, does not depend
         on the batch size.  A reference with more tokens than its audio has frames for counts in "infeasible" and makes
         "eval_loss" inf, as the reference's mean would be.  Like the ``nbest`` form this is a plain batch loop with
-        ``forward(want_logp=True)``; it cannot be combined with ``nbest`` (ValueError)."""
+        ``forward(want_logp=True)``; it cannot be combined with ``nbest`` (ValueError).
+
+        trim_silence: as ``transcribe_batch``, in every form; "config" scores what the reference's evaluation with this model
+        definition would have scored (quartznet15x5.yaml trims every clip)."""
         from .metrics import ErrorBreakdown, ErrorRate
         metric = (ErrorBreakdown if breakdown else ErrorRate)(self.labels)
+        trim = self._trim(trim_silence)
         if eval_loss:
             if nbest is not None:
                 raise ValueError("eval_loss=True cannot be combined with nbest")
-            return self._evaluate_manifest_loss(manifest_filepath, batch_size, row_independent, metric)
+            return self._evaluate_manifest_loss(manifest_filepath, batch_size, row_independent, metric, trim)
         if nbest is not None:
-            return self._evaluate_manifest_nbest(manifest_filepath, batch_size, row_independent, metric, int(nbest))
+            return self._evaluate_manifest_nbest(manifest_filepath, batch_size, row_independent, metric, int(nbest), trim)
         keep = []                   # pinned reference batches, alive until the copies that read them have run
 
         def after_forward(entries, idx):
@@ -259,10 +287,10 @@ class VietASR:
                 metric.update(ids, id_len, ref.to(dev, non_blocking=True), ref_len.to(dev, non_blocking=True))
             return score
 
-        _, hyps = self._walk_manifest(manifest_filepath, batch_size, row_independent, after_forward)
+        _, hyps = self._walk_manifest(manifest_filepath, batch_size, row_independent, after_forward, trim_silence=trim)
         return hyps, metric.compute()
 
-    def _evaluate_manifest_nbest(self, manifest_filepath, batch_size, row_independent, metric, nbest):
+    def _evaluate_manifest_nbest(self, manifest_filepath, batch_size, row_independent, metric, nbest, trim_silence=False):
         from .engine import _pcm_to_float
         from .metrics import OracleErrorRate
         if self.mode != "beam":
@@ -279,8 +307,10 @@ class VietASR:
             for k, s in enumerate(sigs):
                 batch[k, : lens[k]] = _pcm_to_float(s)
             r = eng.forward(torch.from_numpy(batch).to(eng.device), torch.tensor(lens, device=eng.device), want_logp=True,
-                            want_pred=False, row_independent=row_independent)
+                            want_pred=False, row_independent=row_independent, trim_silence=trim_silence)
             own = [eng.frames(n)[1] for n in lens] if row_independent else None
+            if row_independent and trim_silence:
+                own = eng.frames_of(r["length"])
             ids, id_len, count, _, _ = dec.decode_beams_ids(r["logp"], self.beam.beam_width, nbest, frames=own)
             rows = [k for k, i in enumerate(idx) if entries[i].get("text")]
             if rows:
@@ -296,10 +326,11 @@ class VietASR:
         res["oracle_wer"], res["oracle_cer"] = best["oracle_wer"], best["oracle_cer"]
         return hyps, res
 
-    def _forward_logp(self, sigs, row_independent):
+    def _forward_logp(self, sigs, row_independent, trim_silence=False):
         """One zero-padded batch of signals at the model's rate through ``forward(want_logp=True)`` -> (its result dict, the
         frames of every row [B] on the device: the row's own encoded frames when row_independent, otherwise the encoder's
-        lengths of the padded batch)."""
+        lengths of the padded batch).  trim_silence: the rows are trimmed on the device first (the dict then has "trim_start"
+        and "length") and a row's own frames follow its trimmed length, computed there."""
         from .engine import _pcm_to_float
         eng = self._fused_engine()
         lens = [len(s) for s in sigs]
@@ -310,20 +341,22 @@ class VietASR:
         for k, s in enumerate(sigs):
             batch[k, : lens[k]] = _pcm_to_float(s)
         r = eng.forward(torch.from_numpy(batch).to(eng.device), torch.tensor(lens, device=eng.device), want_logp=True,
-                        row_independent=row_independent)
-        if row_independent:
+                        row_independent=row_independent, trim_silence=trim_silence)
+        if row_independent and trim_silence:
+            frames = eng.frames_of(r["length"])
+        elif row_independent:
             frames = torch.tensor([eng.frames(n)[1] for n in lens], dtype=torch.int32).to(eng.device)
         else:
             frames = r["enc_len"]
         return r, frames
 
-    def _evaluate_manifest_loss(self, manifest_filepath, batch_size, row_independent, metric):
+    def _evaluate_manifest_loss(self, manifest_filepath, batch_size, row_independent, metric, trim_silence=False):
         from .metrics import CTCEvalLoss
         eng, loss = self._fused_engine(), CTCEvalLoss(len(self.labels))
         entries, batches = self._manifest_batches(manifest_filepath, batch_size)
         hyps = [None] * len(entries)
         for idx, sigs in batches:
-            r, frames = self._forward_logp(sigs, row_independent)
+            r, frames = self._forward_logp(sigs, row_independent, trim_silence)
             rows = [k for k, i in enumerate(idx) if entries[i].get("text")]
             if rows:
                 ref, ref_len = self._reference_tokens(entries, [idx[k] for k in rows])
@@ -340,18 +373,20 @@ class VietASR:
         res.update(loss.compute())
         return hyps, res
 
-    def score(self, signals, texts, sample_rate=None, row_independent=True):
+    def score(self, signals, texts, sample_rate=None, row_independent=True, trim_silence=False):
         """log P(text | audio) of every (signal, text) pair -> a list of Python floats, minus the CTC loss of the row
         (``stages.ctc_loss`` on the batch's log-probs, over each row's own encoded frames): the forced score of ANY
         transcript -- a reference, or a greedy or beam hypothesis as a sequence confidence or for rescoring.  The texts go
         through the character parser the references go through (characters outside the labels are dropped).  A text that
         has no path through its audio (more tokens, counting one more per repeated character, than frames) scores -inf.
-        row_independent (default): every score is what the signal alone would give.  One synchronisation."""
+        row_independent (default): every score is what the signal alone would give.  One synchronisation.  trim_silence: as
+        ``transcribe_batch``."""
         signals, texts = list(signals), list(texts)
         if len(signals) != len(texts) or not signals:
             raise ValueError(f"score needs as many texts as signals, and at least one (got {len(signals)} and {len(texts)})")
         eng = self._fused_engine()
-        r, frames = self._forward_logp([self._to_model_rate(s, sample_rate) for s in signals], row_independent)
+        r, frames = self._forward_logp([self._to_model_rate(s, sample_rate) for s in signals], row_independent,
+                                       self._trim(trim_silence))
         ref, ref_len = self._reference_tokens([{"text": t} for t in texts], range(len(texts)))
         from . import stages
         loss = stages.ctc_loss(r["logp"], frames, ref.to(eng.device), ref_len.to(eng.device), len(self.labels))
@@ -360,7 +395,7 @@ class VietASR:
             raise RuntimeError("the CTC score came back NaN for rows %s" % [k for k, v in enumerate(host) if v != v])
         return [-v for v in host]
 
-    def align(self, signals, texts=None, sample_rate=None, row_independent=True):
+    def align(self, signals, texts=None, sample_rate=None, row_independent=True, trim_silence=False):
         """Character and word time spans of every (signal, text) pair: the forced (Viterbi) alignment of the text to the
         batch's log-probs (``stages.ctc_align``, over each row's own encoded frames) -> per row a dict {"text", "score",
         "chars", "words"} (``alignment_entries``): "score" is the log-probability of the best single path, at most
@@ -369,7 +404,10 @@ class VietASR:
         dropped); "text" is the parsed text.  texts=None aligns every row's own greedy transcript, from the same forward
         pass: the collapsed ids of the pass are the targets on the device, the spans are the runs of the per-frame argmax.
         A text with no path through its audio gets score -inf and empty lists.  row_independent (default): every row is what
-        the signal alone would give.  One synchronisation."""
+        the signal alone would give.  One synchronisation.
+
+        trim_silence: as ``transcribe_batch``.  The spans stay in the time of the recording that was given: every "start"
+        and "end" has the row's ``trim_start / sample_rate`` added, and the row reports it as "offset" (seconds)."""
         from . import stages
         signals = list(signals)
         if texts is not None:
@@ -378,7 +416,8 @@ class VietASR:
             raise ValueError(f"align needs at least one signal, and as many texts as signals (got {len(signals)} and "
                              f"{None if texts is None else len(texts)})")
         eng = self._fused_engine()
-        r, frames = self._forward_logp([self._to_model_rate(s, sample_rate) for s in signals], row_independent)
+        trim = self._trim(trim_silence)
+        r, frames = self._forward_logp([self._to_model_rate(s, sample_rate) for s in signals], row_independent, trim)
         if texts is None:
             tgt, tgt_len = r["ids"], r["id_len"]
         else:
@@ -386,11 +425,15 @@ class VietASR:
             tgt, tgt_len = ref.to(eng.device, non_blocking=True), ref_len.to(eng.device, non_blocking=True)
         out = stages.ctc_align(r["logp"], frames, tgt, tgt_len, len(self.labels))
         dev = [out["score"], out["start"], out["end"], out["token_logp"], tgt.to(torch.int32), tgt_len.to(torch.int32)]
+        if trim:
+            dev.append(r["trim_start"])
         host = [torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in dev]
         for h, d in zip(host, dev):
             h.copy_(d, non_blocking=True)
         torch.cuda.current_stream(eng.device).synchronize()
-        score, start, end, logp, ids, n = (h.numpy() for h in host)
+        score, start, end, logp, ids, n = (h.numpy() for h in host[:6])
+        rate = float(self.model_definition["AudioToMelSpectrogramPreprocessor"]["sample_rate"])
+        offsets = [int(v) / rate for v in host[6].numpy()] if trim else None
         if np.isnan(score).any():
             raise RuntimeError("the alignment score came back NaN for rows %s" % np.isnan(score).nonzero()[0].tolist())
         sec = eng.frame_seconds()
@@ -398,8 +441,10 @@ class VietASR:
         for b in range(len(signals)):
             chars = [self.labels[c] for c in ids[b, : n[b]]]
             row = {"text": "".join(chars), "score": float(score[b]), "chars": [], "words": []}
+            if trim:
+                row["offset"] = offsets[b]
             if score[b] != -np.inf:
-                row["chars"], row["words"] = alignment_entries(chars, start[b], end[b], logp[b], sec)
+                row["chars"], row["words"] = alignment_entries(chars, start[b], end[b], logp[b], sec, offsets[b] if trim else 0.0)
             rows.append(row)
         return rows
 
