@@ -88,6 +88,14 @@ VASR_API int vasr_bench_pointwise_bf16x3(const float* d_x, const uint16_t* d_w3,
 VASR_API int vasr_bench_groupnorm(const float* d_x, const int32_t* d_lens, int batch, int channels, int64_t frames,
                                   int norm_groups, int shuffle, const float* h_gamma, const float* h_beta, int relu, float* d_y,
                                   vasr_stream stream);
+/* The CTC head's epilogue alone (decode.hip launch_logsoftmax_argmax, as run_decoder calls it behind the head's GEMM):
+ * d_logits [B][num_classes][vasr_padded_frames(frames)] class-major, columns >= frames are never read ->
+ * d_logp [B][frames][num_classes] = log_softmax over the classes (or NULL) and d_pred [B][frames] int64 = the first index of
+ * the row's maximum (or NULL).  The product's entry point vasr_decoder_logsoftmax_f32 passes no d_pred; this is the fused
+ * arg-max without an engine around it.  VASR_ERR_INVALID, before any launch: num_classes outside 1..128 (the widest
+ * instantiation), frames < 1, batch < 1, no logits, or both outputs NULL. */
+VASR_API int vasr_bench_ctc_head(const float* d_logits, int batch, int64_t frames, int num_classes, float* d_logp,
+                                 int64_t* d_pred, vasr_stream stream);
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,7 @@ DEV_SIGNATURES = {
                                              C.c_int, _P]),
     "vasr_bench_pointwise": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P]),
     "vasr_bench_groupnorm": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
+    "vasr_bench_ctc_head": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _P, _P, _P]),
 }
 
 ABI_VERSION = 8          # VASR_ABI_VERSION of the include/vasr.h these signatures were written against

@@ -249,5 +249,15 @@ int vasr_bench_groupnorm(const float* d_x, const int32_t* d_lens, int batch, int
   return 0;
 }
 
+int vasr_bench_ctc_head(const float* d_logits, int batch, int64_t frames, int num_classes, float* d_logp, int64_t* d_pred,
+                        vasr_stream stream) {
+  if (!d_logits || batch < 1 || frames < 1 || frames > 0x7fffff00 || num_classes < 1 || num_classes > 128 || (!d_logp && !d_pred))
+    return fail(VASR_ERR_INVALID, "bench_ctc_head: batch %d, frames %lld, num_classes %d (1..128), logp %s, pred %s", batch,
+                (long long)frames, num_classes, d_logp ? "given" : "NULL", d_pred ? "given" : "NULL");
+  const int64_t ld = pad_frames(frames);
+  launch_logsoftmax_argmax(d_logits, ld, (int64_t)num_classes * ld, batch, (int)frames, num_classes, d_logp, d_pred,
+                           static_cast<hipStream_t>(stream));
+  return check_launch("bench_ctc_head");
+}
 
 }  // extern "C"
