@@ -510,14 +510,16 @@ VASR_API int vasr_get_gemm_mode(const vasr_handle* h);
 /* ---- audio ingest (callers of the path: infer.py:200 librosa.load(sr=16000); parts/segment.py:19-32,61-74) ---- */
 /* int16 PCM -> float32 scaled by 2^-15 (AudioSegment._convert_samples_to_float32). n = total samples. */
 VASR_API int vasr_pcm16_to_f32(const int16_t* d_pcm, int64_t n, float* d_out, vasr_stream stream);
-/* Band-limited sample-rate conversion of a zero-padded batch (interpolated windowed-sinc, the scheme of resampy's
+/* Band-limited sample-rate conversion of a padded batch (interpolated windowed-sinc, the scheme of resampy's
  * kaiser_best that librosa.load uses by default; third-party => parity unpinned).  d_table = [nwin][2] floats
  * (window value, delta to the next entry) with num_table entries per zero crossing, built on the host
  * (viet-asr_amd/audio.py::sinc_table); ratio = sr_out / sr_in.  Lengths as librosa.load -> librosa.resample(fix=True)
  * produces them: resampy computes int(d_len_in[b] * ratio) samples, librosa pads (with zeros) to
  * d_len_out[b] = ceil(d_len_in[b] * ratio), both products in double (11 025 -> 16 000 Hz: 5 000 samples give 7 256
  * computed samples and a length of 7 257; the reference's 8 -> 16 kHz: 2 n either way).  Rows of d_out are
- * zero from int(d_len_in[b] * ratio) on.  ld_out >= ceil(ld_in * ratio).  (ABI 6; ABI 5 reported int(len * ratio).) */
+ * zero from int(d_len_in[b] * ratio) on, up to ld_out.  ld_out >= ceil(ld_in * ratio).  A row's length is clamped to
+ * [0, ld_in] (a negative one gives an all-zero row of length 0); samples at or beyond it are never read: the caller's padding
+ * may hold anything, NaN included.  (ABI 6; ABI 5 reported int(len * ratio).) */
 VASR_API int vasr_resample_f32(const float* d_in, int64_t ld_in, const int64_t* d_len_in, int batch, const float* d_table,
                       int nwin, int num_table, double ratio, float* d_out, int64_t ld_out, int64_t* d_len_out,
                       vasr_stream stream);

@@ -24,6 +24,11 @@ VASR_API int vasr_fused_tile_choice(int64_t tiles128, int compute_units);
  * (dual != 0) or without the folded residual, on tiles of tile_cols = 128 | 64 frames: VASR_FUSED_WAVES where it is set and the
  * form exists (the 128-frame tile), else the library's default (csrc/encoder_fused.hip fused_waves_choice; pure host arithmetic). */
 VASR_API int vasr_fused_waves_choice(int kernel, int dual, int tile_cols);
+/* The kernel vasr_resample_f32 runs a ratio on (csrc/audio.hip resample_form, which launch_resample itself calls; pure host
+ * arithmetic): 2 = integer up-sampling (ratio p / 1, 2 <= p <= 16), 1 = the phase kernel (p / q with a denominator up to 1000
+ * found within 1e-12 and wing tables within 60 KB of LDS), 0 = the generic per-output gather.  *p / *q (either may be NULL) receive
+ * the ratio in lowest terms, 0 / 0 where none was found.  VASR_ERR_INVALID for the arguments vasr_resample_f32 refuses. */
+VASR_API int vasr_resample_form(double ratio, int nwin, int num_table, int* p, int* q);
 /* Run ONE encoder layer kind in isolation for benchmarking/roofline measurement:
  * kind 0 = depthwise (K, stride 1, dilation 1), 1 = pointwise GEMM (+BN+ReLU epilogue).
  * Buffers are caller provided [B][C][Tp] with Tp = vasr_padded_frames(T). */

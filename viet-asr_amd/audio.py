@@ -71,7 +71,8 @@ _tables = {}
 
 
 def resample(signal, length, sr_in, sr_out, filter="kaiser_best"):
-    """signal [B, L] float32 cuda (zero padded), length [B] int64 cuda -> (signal' [B, L'], length').
+    """signal [B, L] float32 cuda (padding: anything, it is never read), length [B] int64 cuda -> (signal' [B, L'], length'),
+    rows of signal' zero from int(n * ratio) on.
 
     Lengths follow ``librosa.load(sr=...)`` -> ``librosa.resample(fix=True)`` (infer.py:200): resampy computes
     ``int(n * ratio)`` samples, librosa pads them with zeros to ``ceil(n * ratio)`` (both in float64: 5 000 samples at

@@ -14,7 +14,9 @@
 //     input span of its 1024 outputs in LDS (zero outside [0, len): that replaces the per-sample bound checks) and
 //     every output is two LDS dot products.  Same arithmetic as the generic kernel (fp32 weight, fp32 product, fp64
 //     accumulation), 8x faster: the generic form chases two dependent global loads per tap.
+//   * resample_up_kernel: integer ratios p = 2 .. 16, described at the kernel.
 //   * resample_kernel: any ratio, one thread per output sample, table gathers from L2.
+// resample_form() picks among the three; every kernel clamps a row's length to [0, ld_in] and reads nothing behind it.
 #include <cstdlib>
 
 #include "vasr_internal.h"
@@ -22,6 +24,10 @@
 namespace vasr {
 
 namespace {
+
+// A row's sample count: the caller's length clamped to [0, ld_in], as crop_pad_kernel clamps its widths -- a length above the
+// pitch would read past the row, a negative one report a negative output length.
+__device__ __forceinline__ int64_t row_length(int64_t len, int64_t ld_in) { return len < 0 ? 0 : (len > ld_in ? ld_in : len); }
 
 // out[b][i] = in[b][i] / 32768   (segment.py:61-74: int -> float32 * 1/2^(bits-1))
 __global__ __launch_bounds__(256) void pcm16_to_f32_kernel(const short* __restrict__ in, int64_t n,
@@ -44,7 +50,7 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
                                                        int64_t* __restrict__ len_out) {
   const int b = blockIdx.y;
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t n_orig = len_in[b];
+  const int64_t n_orig = row_length(len_in[b], ld_in);
   const int64_t n_out = (int64_t)((double)n_orig * ratio);   // resampy: int(n_orig * ratio) samples are COMPUTED ...
   if (t == 0) len_out[b] = (int64_t)ceil((double)n_orig * ratio);   // ... librosa.resample(fix=True) pads them to ceil(n_orig * ratio)
   if (t >= ld_out) return;
@@ -90,7 +96,7 @@ constexpr int kPhaseTile = 1024;   // outputs per workgroup
 __global__ __launch_bounds__(256) void resample_phase_kernel(const float* __restrict__ x, int64_t ld_in,
                                                              const int64_t* __restrict__ len_in,
                                                              const float2* __restrict__ table, int nwin, int num_table,
-                                                             double ratio, int p, int wmax, int span,
+                                                             double ratio, int p, int q, int wmax, int span,
                                                              float* __restrict__ y, int64_t ld_out,
                                                              int64_t* __restrict__ len_out) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -101,19 +107,21 @@ __global__ __launch_bounds__(256) void resample_phase_kernel(const float* __rest
 
   const int b = blockIdx.y, tid = threadIdx.x;
   const int64_t t0 = (int64_t)blockIdx.x * kPhaseTile;
-  const int64_t n_orig = len_in[b];
+  const int64_t n_orig = row_length(len_in[b], ld_in);
   const int64_t n_out = (int64_t)((double)n_orig * ratio);   // resampy: int(n_orig * ratio) samples are COMPUTED ...
   if (blockIdx.x == 0 && tid == 0) len_out[b] = (int64_t)ceil((double)n_orig * ratio);   // ... librosa pads to ceil(n_orig * ratio)
   const float* xi = x + (int64_t)b * ld_in;
   const double scale = ratio < 1.0 ? ratio : 1.0;
   const int index_step = (int)(scale * num_table);
 
-  // ---- the p interpolated filters: phase of output t is t mod p (same expressions as the generic kernel) ----
+  // ---- the p interpolated filters: phase of output t is t mod p (the generic kernel's expressions from an exact fraction) ----
+  // Output t sits at input time t q / p = n + r / p with n = (t q) / p and r = (t q) % p in integers.  Both come from the
+  // integers here and below: (double)t / ratio can land one ulp under an integer t q / p (100 / 99 at t = 500, 7 / 3 at
+  // t = 9), and a filter built for r = 0 at one output then met an n floored to one less at another -- the whole filter one
+  // sample off.  The generic kernel takes filter and n from the same quotient, so there the interpolation's continuity covers it.
   for (int ph = 0; ph < p; ++ph) {
-    const int64_t t = t0 + ((ph - t0 % p) + p) % p;          // first output of this tile with that phase
-    const double time_register = (double)t / ratio;
-    const int64_t n = (int64_t)time_register;
-    const double fl = scale * (time_register - (double)n), fr = scale - fl;
+    const int r = (int)(((int64_t)ph * q) % p);
+    const double fl = scale * ((double)r / (double)p), fr = scale - fl;
     const double ifl = fl * num_table, ifr = fr * num_table;
     const int ol = (int)ifl, orr = (int)ifr;
     const float el = (float)(ifl - ol), er = (float)(ifr - orr);
@@ -128,7 +136,7 @@ __global__ __launch_bounds__(256) void resample_phase_kernel(const float* __rest
     }
   }
   // ---- input span of the tile; samples outside [0, n_orig) are zero, which is what the wing bounds amount to ----
-  const int64_t n_lo = (int64_t)((double)t0 / ratio) - wmax;
+  const int64_t n_lo = t0 * q / p - wmax;
   for (int j = tid; j < span; j += 256) {
     const int64_t g = n_lo + j;
     xs[j] = (g >= 0 && g < n_orig) ? xi[g] : 0.f;
@@ -142,7 +150,7 @@ __global__ __launch_bounds__(256) void resample_phase_kernel(const float* __rest
     float out = 0.f;
     if (t < n_out) {
       const int ph = (int)(t % p);
-      const int64_t n = (int64_t)((double)t / ratio);
+      const int64_t n = t * q / p;
       const int base = (int)(n - n_lo);
       const float* a = wl + ph * wmax;
       const float* c = wr + ph * wmax;
@@ -177,7 +185,7 @@ __global__ __launch_bounds__(256) void resample_up_kernel(const float* __restric
   float* xs = reinterpret_cast<float*>(h + (size_t)p * mpad);     // [span]
   const int b = blockIdx.y, tid = threadIdx.x;
   const int64_t t0 = (int64_t)blockIdx.x * tile;                  // a multiple of p: output t0 + ph has phase ph
-  const int64_t n_orig = len_in[b];
+  const int64_t n_orig = row_length(len_in[b], ld_in);
   const int64_t n_out = n_orig * p;                               // int(n_orig * ratio), ratio = p exactly
   if (blockIdx.x == 0 && tid == 0) len_out[b] = n_out;
   const float* xi = x + (int64_t)b * ld_in;
@@ -235,6 +243,18 @@ __global__ __launch_bounds__(256) void resample_up_kernel(const float* __restric
 
 int64_t gcd64(int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; }
 
+// resample_phase_kernel's wing width, staged input span and dynamic LDS bytes for a ratio of p phases
+struct PhaseShape { int wmax, span; size_t lds; };
+PhaseShape phase_shape(double ratio, int nwin, int num_table, int p) {
+  const double scale = ratio < 1.0 ? ratio : 1.0;
+  const int index_step = (int)(scale * num_table);
+  PhaseShape s;
+  s.wmax = nwin / index_step + 2;
+  s.span = (int)((double)kPhaseTile / ratio) + 2 * s.wmax + 8;
+  s.lds = sizeof(float) * ((size_t)2 * p * s.wmax + s.span) + sizeof(int) * 2 * p;
+  return s;
+}
+
 }  // namespace
 
 void launch_pcm16_to_f32(const short* in, int64_t n, float* out, hipStream_t st) {
@@ -242,8 +262,10 @@ void launch_pcm16_to_f32(const short* in, int64_t n, float* out, hipStream_t st)
   hipLaunchKernelGGL(pcm16_to_f32_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, in, n, out);
 }
 
-void launch_resample(const float* x, int64_t ld_in, const int64_t* len_in, int batch, const float* table, int nwin,
-                     int num_table, double ratio, float* y, int64_t ld_out, int64_t* len_out, hipStream_t st) {
+// Which kernel a ratio runs on: 2 = resample_up_kernel, 1 = resample_phase_kernel, 0 = resample_kernel; *p / *q = the ratio in
+// lowest terms (0 / 0 where no denominator up to 1000 reproduces it to 1e-12).  Pure host arithmetic; launch_resample goes by
+// nothing else, and the devtools build exports it (vasr_resample_form) so that the tests' restatement cannot drift from it.
+int resample_form(double ratio, int nwin, int num_table, int* p_out, int* q_out) {
   // ratio as p/q: sample rates are integers, so ratio * 48000 * 44100 / ... is overkill -- try denominators up to 1000
   int p = 0, q = 0;   // the reduced ratio p / q (p = the phase count); 0 = no small rational found
   for (int d = 1; d <= 1000 && !p; ++d) {
@@ -255,7 +277,21 @@ void launch_resample(const float* x, int64_t ld_in, const int64_t* len_in, int b
       q = (int)(d / g);
     }
   }
-  if (p >= 2 && p <= 16 && q == 1) {   // integer up-sampling: 8 -> 16 kHz
+  if (p_out) *p_out = p;
+  if (q_out) *q_out = q;
+  if (p >= 2 && p <= 16 && q == 1) return 2;   // integer up-sampling: 8 -> 16 kHz
+  if (p > 0) {
+    const PhaseShape s = phase_shape(ratio, nwin, num_table, p);
+    if (s.lds <= 60 * 1024) return 1;
+  }
+  return 0;
+}
+
+void launch_resample(const float* x, int64_t ld_in, const int64_t* len_in, int batch, const float* table, int nwin,
+                     int num_table, double ratio, float* y, int64_t ld_out, int64_t* len_out, hipStream_t st) {
+  int p = 0, q = 0;
+  const int form = resample_form(ratio, nwin, num_table, &p, &q);
+  if (form == 2) {
     const int wmax = nwin / num_table + 2;                              // >= taps of either wing
     const int mpad = (2 * wmax + kUpTB - 1) / kUpTB * kUpTB;
     const int tile = kUpR * p * (256 / p);
@@ -266,18 +302,12 @@ void launch_resample(const float* x, int64_t ld_in, const int64_t* len_in, int b
                        nwin, num_table, p, wmax, mpad, span, tile, y, ld_out, len_out);
     return;
   }
-  if (p > 0) {
-    const double scale = ratio < 1.0 ? ratio : 1.0;
-    const int index_step = (int)(scale * num_table);
-    const int wmax = nwin / index_step + 2;
-    const int span = (int)((double)kPhaseTile / ratio) + 2 * wmax + 8;
-    const size_t lds = sizeof(float) * ((size_t)2 * p * wmax + span) + sizeof(int) * 2 * p;
-    if (lds <= 60 * 1024) {
-      dim3 grid((unsigned)((ld_out + kPhaseTile - 1) / kPhaseTile), batch);
-      hipLaunchKernelGGL(resample_phase_kernel, grid, dim3(256), lds, st, x, ld_in, len_in,
-                         reinterpret_cast<const float2*>(table), nwin, num_table, ratio, p, wmax, span, y, ld_out, len_out);
-      return;
-    }
+  if (form == 1) {
+    const PhaseShape s = phase_shape(ratio, nwin, num_table, p);
+    dim3 grid((unsigned)((ld_out + kPhaseTile - 1) / kPhaseTile), batch);
+    hipLaunchKernelGGL(resample_phase_kernel, grid, dim3(256), s.lds, st, x, ld_in, len_in,
+                       reinterpret_cast<const float2*>(table), nwin, num_table, ratio, p, q, s.wmax, s.span, y, ld_out, len_out);
+    return;
   }
   dim3 grid((unsigned)((ld_out + 255) / 256), batch);
   hipLaunchKernelGGL(resample_kernel, grid, dim3(256), 0, st, x, ld_in, len_in, reinterpret_cast<const float2*>(table),

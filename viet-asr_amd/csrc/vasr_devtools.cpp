@@ -52,6 +52,11 @@ int vasr_fused_tile_choice(int64_t tiles128, int compute_units) { return vasr::f
 int vasr_fused_waves_choice(int kernel, int dual, int tile_cols) {
   return vasr::fused_waves_choice(kernel, dual != 0, tile_cols, vasr::dev_switches().fused_waves);
 }
+int vasr_resample_form(double ratio, int nwin, int num_table, int* p, int* q) {
+  if (!(ratio > 0.0) || nwin < 2 || num_table < 1 || (int)((ratio < 1.0 ? ratio : 1.0) * num_table) < 1)
+    return fail(VASR_ERR_INVALID, "invalid ratio / table for resampling");   // what vasr_resample_f32 refuses
+  return vasr::resample_form(ratio, nwin, num_table, p, q);
+}
 
 static __global__ void dev_noop_kernel() {}
 

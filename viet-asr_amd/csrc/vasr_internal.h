@@ -410,6 +410,8 @@ int launch_ctc_align(const float* logp, const int32_t* frames_in, int batch, int
 
 // ---- audio ingest (audio.hip) ----
 void launch_pcm16_to_f32(const short* in, int64_t n, float* out, hipStream_t st);
+// the kernel launch_resample runs a ratio on (host only): 2 up, 1 phase, 0 generic; *p / *q = the ratio in lowest terms or 0 / 0
+int resample_form(double ratio, int nwin, int num_table, int* p, int* q);
 void launch_resample(const float* x, int64_t ld_in, const int64_t* len_in, int batch, const float* table, int nwin,
                      int num_table, double ratio, float* y, int64_t ld_out, int64_t* len_out, hipStream_t st);
 
