@@ -568,6 +568,62 @@ VASR_API int vasr_trim_silence_pcm16(const int16_t* d_in, int64_t ld_in, const i
                                      int frame_length, int hop_length, int16_t* d_out, int64_t ld_out, int64_t* d_len_out,
                                      int64_t* d_start, void* d_workspace, size_t workspace_bytes, vasr_stream stream);
 
+/* Split at silences: the non-silent intervals of every row of a padded batch, for cutting a long recording at its pauses.
+ * With min_silence_frames = 1 and max_segment_frames = 0 this is librosa.effects.split(y, top_db, ref=np.max, frame_length,
+ * hop_length) of librosa < 0.10 -- the trim above with EVERY run of non-silent frames reported, not only the outer bounds.
+ * Third-party arithmetic restated from its published form, parity unpinned (librosa is not available to the tests;
+ * tests/split_reference.py is the float64 restatement they use).  Two rules of an ASR front end sit on top of it: short
+ * pauses are bridged, over-long runs are cut at their quietest frame.
+ * Per row of n = clamp(d_len[b], 0, ld_in) samples, with frame_length, hop_length, top_db as for the trim,
+ * m = min_silence_frames >= 1 and M = max_segment_frames (0: no limit, otherwise >= 2):
+ *   A. flags: exactly the trim's.  F = 1 + n / hop_length frames of the reflect-padded row; frame f is NON-SILENT iff
+ *      max(amin, mse[f]) > max(amin, ref) * 10^(-top_db / 10), ref the loudest frame's mse, amin = 1e-10, all in float64.  A row
+ *      with n == 0 has no segment; a row whose loudest frame is below amin has every frame non-silent (for top_db > 0);
+ *   B. runs: a run is a maximal stretch of frames that starts and ends on a non-silent frame and contains no m or more
+ *      consecutive silent frames: a silent gap of fewer than m frames between two non-silent frames is bridged; leading and
+ *      trailing silence never is.  With m = 1 the runs are librosa.effects.split's;
+ *   C. cuts (M > 0 only): a run [s, e) with e - s > M is cut at c, the frame with the smallest energy among s + ceil(M / 2) ..
+ *      s + M inclusive, the lowest index among equal energies -- the energy is the float64 frame sum the threshold uses --;
+ *      [s, c) is a segment and the rule is applied again to [c, e).  Every segment is then at most M frames long and the pieces
+ *      of a run are contiguous: no sample of a run is lost;
+ *   D. bounds: the segment of frames [f0, f1) is the samples [min(n, f0 hop), min(n, f1 hop)) (librosa's frames_to_samples and
+ *      np.minimum).  As in librosa, a run that starts on the last frame of a row whose n is a multiple of hop_length gives the
+ *      empty interval [n, n); it is reported, not filtered;
+ *   E. output: d_bounds[b][k] = (start, end), int64 pairs in ascending order for k < min(count, max_segments), the row pitch
+ *      is 2 max_segments; d_count[b] = the row's total number of segments, ALSO where it exceeds max_segments (the caller sees
+ *      the overflow).  Entries at and behind min(count, max_segments) are not written.  A row has at most F segments.
+ * int16 rows (the _pcm16 form): energies of value * 2^-15, as for the trim.  Samples at or beyond a row's length are never
+ * read as data.  A row's outputs do not depend on the other rows, on the batch size, on ld_in or on the row's alignment.
+ * Two launches, no atomics, no host synchronisation, no handle.
+ * The chunk sums and the runs go through d_workspace: vasr_split_silence_workspace_bytes(batch, ld_in, frame_length,
+ * hop_length) bytes of device memory at any address, contents undefined before and after (16 bytes per hop_length samples +
+ * 512); the function is host only and returns 0 for arguments the calls refuse.
+ * NULL d_in / d_len / d_bounds / d_count / d_workspace, batch <= 0, ld_in < 0, max_segments < 0, min_silence_frames < 1,
+ * max_segment_frames < 0 or == 1, a non-finite top_db and a workspace smaller than required return VASR_ERR_INVALID; the frame
+ * forms the trim refuses return VASR_ERR_UNSUPPORTED; an argument error wins over the limit -- all before a device is touched.
+ * DESIGN section 7g has the kernels.  (added within ABI 8) */
+VASR_API size_t vasr_split_silence_workspace_bytes(int batch, int64_t ld_in, int frame_length, int hop_length);
+VASR_API int vasr_split_silence_f32(const float* d_in, int64_t ld_in, const int64_t* d_len, int batch, float top_db,
+                                    int frame_length, int hop_length, int min_silence_frames, int max_segment_frames,
+                                    int64_t* d_bounds, int64_t max_segments, int64_t* d_count, void* d_workspace,
+                                    size_t workspace_bytes, vasr_stream stream);
+VASR_API int vasr_split_silence_pcm16(const int16_t* d_in, int64_t ld_in, const int64_t* d_len, int batch, float top_db,
+                                      int frame_length, int hop_length, int min_silence_frames, int max_segment_frames,
+                                      int64_t* d_bounds, int64_t max_segments, int64_t* d_count, void* d_workspace,
+                                      size_t workspace_bytes, vasr_stream stream);
+
+/* Gather segments of a padded batch into a padded batch: d_out[s][t] = d_in[d_row[s]][d_start[s] + t] for t < d_len[s], bit
+ * for bit, and zero up to ld_out, for s < segments.  EVERY element of every output row is written.  A segment whose row is
+ * outside [0, batch), whose start or length is negative, with start + len > ld_in, or with len > ld_out gives a row of zeros;
+ * nothing is read or written out of bounds.  One launch, no atomics, no host synchronisation, no handle; d_out must not alias
+ * d_in.  NULL pointers, batch <= 0, ld_in < 0, segments <= 0 and ld_out <= 0 return VASR_ERR_INVALID before a device is
+ * touched.  (added within ABI 8) */
+VASR_API int vasr_gather_segments_f32(const float* d_in, int64_t ld_in, int batch, const int32_t* d_row, const int64_t* d_start,
+                                      const int64_t* d_len, int64_t segments, float* d_out, int64_t ld_out, vasr_stream stream);
+VASR_API int vasr_gather_segments_pcm16(const int16_t* d_in, int64_t ld_in, int batch, const int32_t* d_row,
+                                        const int64_t* d_start, const int64_t* d_len, int64_t segments, int16_t* d_out,
+                                        int64_t ld_out, vasr_stream stream);
+
 /* The fused call can cut the batch into `slices` contiguous parts (1..4; default 1 = off, because on MI355X it
  * measured slower: 11.7 -> 13.5 ms at 2 slices) and run each on its own
  * internal HIP stream, forked from / joined to `stream` with events: one part's HBM-bound kernels (depthwise,

@@ -7,7 +7,7 @@ Run this script ONCE on a machine that has the packages -- e.g. `pip install "li
 kenlm` -- and commit what it writes: from then on `tests/test_thirdparty_pins.py` compares BOTH the CPU oracle and the
 device kernels with the packages' own outputs instead of skipping with "parity unpinned".
 
-    python tools/pin_third_party.py [--out tests/golden] [--only mel,resample,stftconv,beam,trim]
+    python tools/pin_third_party.py [--out tests/golden] [--only mel,resample,stftconv,beam,trim,split]
 
 fixture                                 produced by (reference call site)                              pins
 tests/golden/thirdparty_mel.npz         librosa.filters.mel(16000, 512, n_mels=64, fmin=0, fmax=8000)  oracle.slaney_mel_filterbank,
@@ -22,6 +22,8 @@ tests/golden/thirdparty_beam.npz        pyctcdecode.build_ctcdecoder(vocab, kenl
 tests/golden/thirdparty_trim.npz        librosa.effects.trim(samples, top_db) of librosa < 0.10         tests/trim_reference.trim_bounds,
                                         (parts/segment.py:24-28, AudioSegment(trim=True)), a fifth     vasr_trim_silence_f32 / _pcm16
                                         piece: every row of the case table of tests/trim_reference.py
+tests/golden/thirdparty_split.npz       librosa.effects.split(samples, top_db) of librosa < 0.10: every tests/split_reference.split at (m, M) = (1, 0),
+                                        row of the case table of tests/split_reference.py              vasr_split_silence_f32 / _pcm16
 
 Inputs are regenerated from seeds by the tests (viet_asr_amd.synth), except where the package output depends on an input
 file: those inputs are stored in the fixture.  Only numpy arrays are written -- data, no package source.
@@ -160,12 +162,39 @@ def pin_trim(out):
     print("trim", len(names), "rows | rows where the restatement differs from librosa:", int((got != want).any(axis=1).sum()))
 
 
+def pin_split(out):
+    """librosa's own intervals for every row of the split tests' case table, next to the restatement's at (m, M) = (1, 0): flat
+    (start, end) pairs with the number of intervals per row; the rows themselves are regenerated from the table's seeds by the
+    tests."""
+    import librosa
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import split_reference as R
+    names, counts, got, restated_counts, want, differ = [], [], [], [], [], 0
+    for i, row in enumerate(R.TABLE):
+        for dtype in R.DTYPES:
+            c = R.case(i, dtype)
+            if c["n"] == 0:
+                continue                                                                # np.pad refuses an empty row: librosa raises
+            x = R.T.as_float64(c["x"]).astype(np.float32)
+            iv = librosa.effects.split(x, top_db=c["top_db"], frame_length=c["frame_length"], hop_length=c["hop_length"])
+            mine = R.expected(i, dtype, 1, 0)
+            names.append(f"{row[0]}/{dtype}"), counts.append(len(iv)), restated_counts.append(len(mine))
+            got += [[int(a), int(b)] for a, b in iv]
+            want += [[int(a), int(b)] for a, b in mine]
+            differ += [[int(a), int(b)] for a, b in iv] != [[int(a), int(b)] for a, b in mine]
+    np.savez_compressed(os.path.join(out, "thirdparty_split.npz"), names=np.array(names), counts=np.array(counts, dtype=np.int64),
+                        bounds=np.array(got, dtype=np.int64).reshape(-1, 2), restated_counts=np.array(restated_counts, dtype=np.int64),
+                        restated=np.array(want, dtype=np.int64).reshape(-1, 2), versions=str(versions("librosa", "numpy")))
+    print("split", len(names), "rows | rows where the restatement differs from librosa:", differ)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
-    ap.add_argument("--only", default="mel,resample,stftconv,beam,trim")
+    ap.add_argument("--only", default="mel,resample,stftconv,beam,trim,split")
     a = ap.parse_args()
-    todo = {"mel": pin_mel, "resample": pin_resample, "stftconv": pin_stftconv, "beam": pin_beam, "trim": pin_trim}
+    todo = {"mel": pin_mel, "resample": pin_resample, "stftconv": pin_stftconv, "beam": pin_beam, "trim": pin_trim,
+            "split": pin_split}
     failed = []
     for name in a.only.split(","):
         try:

@@ -75,6 +75,13 @@ SIGNATURES = {
                                         C.c_size_t, _P]),
     "vasr_trim_silence_pcm16": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_float, C.c_int, C.c_int, _P, C.c_int64, _P, _P, _P,
                                           C.c_size_t, _P]),
+    "vasr_split_silence_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int, C.c_int]),
+    "vasr_split_silence_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64,
+                                         _P, _P, C.c_size_t, _P]),
+    "vasr_split_silence_pcm16": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64,
+                                           _P, _P, C.c_size_t, _P]),
+    "vasr_gather_segments_f32": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P]),
+    "vasr_gather_segments_pcm16": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P]),
     "vasr_set_gemm_mode": (C.c_int, [_P, C.c_int]),
     "vasr_get_gemm_mode": (C.c_int, [_P]),
     "vasr_set_slices": (C.c_int, [_P, C.c_int]),

@@ -134,6 +134,105 @@ def trim_silence(signal, length, top_db=60.0, frame_length=2048, hop_length=512,
     return out, ln_out, start
 
 
+def split_silence(signal, length, top_db=60.0, frame_length=2048, hop_length=512, min_silence_frames=1, max_segment_frames=0,
+                  max_segments=None, workspace=None):
+    """signal [B, L] float32 or int16 cuda (padding: anything), length [B] int64 cuda ->
+    (bounds [B, N, 2] int64: (start, end) in samples, ascending; count [B] int64), device tensors, no synchronisation.
+
+    The non-silent intervals of every row: ``librosa.effects.split(y, top_db, ref=np.max, frame_length, hop_length)`` (librosa
+    < 0.10, third-party arithmetic restated from its published form, parity unpinned) with two rules on top: a pause of fewer
+    than ``min_silence_frames`` frames is bridged, and a run longer than ``max_segment_frames`` frames (0: no limit) is cut at
+    its quietest frame; vasr_split_silence_f32 / _pcm16 in include/vasr.h have the semantics.  Entries of ``bounds`` at and
+    behind ``min(count, N)`` are not written; ``count`` is the row's total also where it exceeds N.  max_segments=None takes
+    N = 1 + L // hop_length, the most a row can have.  workspace: a uint8 buffer of the caller's of at least
+    vasr_split_silence_workspace_bytes."""
+    if signal.device.type != "cuda":
+        raise _lib.VasrError("viet-asr_amd kernels need HIP-resident tensors; there is no CPU fallback for this path")
+    if signal.dtype not in (torch.float32, torch.int16) or signal.dim() != 2:
+        raise ValueError("split_silence expects a [B, L] float32 or int16 cuda tensor")
+    x = signal.contiguous()
+    ln = length.to(device=x.device, dtype=torch.int64).contiguous()
+    B, L = x.shape
+    L_lib = _lib.lib()
+    N = 1 + L // max(int(hop_length), 1) if max_segments is None else int(max_segments)
+    bounds = torch.empty((B, max(N, 1), 2), dtype=torch.int64, device=x.device)      # never NULL, also for a count-only call
+    count = torch.empty((B,), dtype=torch.int64, device=x.device)
+    need = int(L_lib.vasr_split_silence_workspace_bytes(B, L, int(frame_length), int(hop_length)))
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+    entry = L_lib.vasr_split_silence_pcm16 if x.dtype == torch.int16 else L_lib.vasr_split_silence_f32
+    _lib.check(entry(x.data_ptr(), L, ln.data_ptr(), B, float(top_db), int(frame_length), int(hop_length), int(min_silence_frames),
+                     int(max_segment_frames), bounds.data_ptr(), N, count.data_ptr(),
+                     workspace.data_ptr(), workspace.numel(), torch.cuda.current_stream(x.device).cuda_stream))
+    return bounds[:, : max(N, 0)], count
+
+
+def gather_segments(signal, rows, starts, lengths, width=None):
+    """signal [B, L] float32 or int16 cuda; rows [S] (int32), starts [S], lengths [S] (int64): tensors or sequences ->
+    out [S, width] of signal's dtype: out[s] = signal[rows[s], starts[s] : starts[s] + lengths[s]] and zeros behind it
+    (vasr_gather_segments_f32 / _pcm16; a descriptor that does not lie inside its row, or is longer than ``width``, gives a row
+    of zeros).  width=None takes the longest length, which reads ``lengths`` on the host when it is a device tensor."""
+    if signal.device.type != "cuda":
+        raise _lib.VasrError("viet-asr_amd kernels need HIP-resident tensors; there is no CPU fallback for this path")
+    if signal.dtype not in (torch.float32, torch.int16) or signal.dim() != 2:
+        raise ValueError("gather_segments expects a [B, L] float32 or int16 cuda tensor")
+    x = signal.contiguous()
+    B, L = x.shape
+    r = torch.as_tensor(rows).to(device=x.device, dtype=torch.int32).contiguous()
+    s = torch.as_tensor(starts).to(device=x.device, dtype=torch.int64).contiguous()
+    n = torch.as_tensor(lengths)
+    S = int(r.numel())
+    if int(s.numel()) != S or int(n.numel()) != S:
+        raise ValueError("rows, starts and lengths must have one entry per segment")
+    if width is None:
+        width = int(n.max()) if S else 0
+    width = max(int(width), 1)
+    n = n.to(device=x.device, dtype=torch.int64).contiguous()
+    out = torch.empty((S, width), dtype=x.dtype, device=x.device)
+    if S == 0:
+        return out
+    entry = _lib.lib().vasr_gather_segments_pcm16 if x.dtype == torch.int16 else _lib.lib().vasr_gather_segments_f32
+    _lib.check(entry(x.data_ptr(), L, B, r.data_ptr(), s.data_ptr(), n.data_ptr(), S, out.data_ptr(), width,
+                     torch.cuda.current_stream(x.device).cuda_stream))
+    return out
+
+
+def plan_segments(bounds, count, lengths, pad=0, min_samples=0):
+    """The host side between ``split_silence`` and ``gather_segments``: bounds [B, N, 2], count [B], lengths [B] (tensors on any
+    device, arrays or lists) -> (segments, dropped): the flat list of (row, start, length) in row order, ascending inside a row,
+    and the number of segments dropped per row (a list of B integers).  Integers only.  Reading ``count`` is the one
+    synchronisation of the long-recording path: the shape of the batches depends on it.
+
+    Every segment is widened by ``pad`` samples on both sides, then clamped to its row [0, lengths[b]) and to the midpoint of
+    the gap to its neighbour -- the midpoint (start of the next + end of this) // 2 belongs to the next one --, so segments
+    never overlap; a segment of ``min_samples`` or fewer samples after that is dropped.  A count beyond N (the device table
+    overflowed) raises ValueError."""
+    def host(t):
+        return t.cpu().tolist() if isinstance(t, torch.Tensor) else np.asarray(t).tolist()
+    c_host, n_host = host(count), host(lengths)
+    held = int(bounds.shape[1]) if isinstance(bounds, torch.Tensor) else len(bounds[0]) if len(bounds) else 0
+    used = min(held, max([int(c) for c in c_host], default=0))
+    b_host = host(bounds[:, :used]) if isinstance(bounds, torch.Tensor) else bounds     # only the entries that were written
+    pad, min_samples = int(pad), int(min_samples)
+    segments, dropped = [], []
+    for b, c in enumerate(c_host):
+        c, n = int(c), max(int(n_host[b]), 0)
+        if c > held:
+            raise ValueError(f"row {b} has {c} segments, the table holds {held}: pass a larger max_segments")
+        segs = [(int(s), int(e)) for s, e in b_host[b][:c]]
+        lost = 0
+        for k, (s, e) in enumerate(segs):
+            lo = (segs[k - 1][1] + s) // 2 if k > 0 else 0
+            hi = (e + segs[k + 1][0]) // 2 if k + 1 < c else n
+            s2, e2 = max(s - pad, lo, 0), min(e + pad, hi, n)
+            if e2 - s2 > min_samples:
+                segments.append((b, s2, e2 - s2))
+            else:
+                lost += 1
+        dropped.append(lost)
+    return segments, dropped
+
+
 def pcm16_to_float(pcm):
     """int16 cuda tensor -> float32 / 32768 on the device (halves the host->device bytes of a batch)."""
     if pcm.device.type != "cuda" or pcm.dtype != torch.int16:

@@ -2057,6 +2057,76 @@ int vasr_trim_silence_pcm16(const int16_t* d_in, int64_t ld_in, const int64_t* d
                              d_workspace, workspace_bytes, stream);
 }
 
+size_t vasr_split_silence_workspace_bytes(int batch, int64_t ld_in, int frame_length, int hop_length) {
+  if (batch <= 0 || ld_in < 0 || !trim_shape_supported(frame_length, hop_length)) return 0;
+  return split_workspace_bytes(batch, ld_in, frame_length, hop_length);
+}
+
+extern "C++" {
+template <typename T>
+static int split_silence(const T* d_in, int64_t ld_in, const int64_t* d_len, int batch, float top_db, int frame_length,
+                         int hop_length, int min_silence_frames, int max_segment_frames, int64_t* d_bounds, int64_t max_segments,
+                         int64_t* d_count, void* d_workspace, size_t workspace_bytes, vasr_stream stream) {
+  // every refusal comes before a device is touched
+  if (!d_in || !d_len || !d_bounds || !d_count) return fail(VASR_ERR_INVALID, "split_silence: NULL pointer");
+  if (batch <= 0 || ld_in < 0 || max_segments < 0)
+    return fail(VASR_ERR_INVALID, "split_silence: batch %d, ld_in %lld, max_segments %lld (batch >= 1, ld_in >= 0, max_segments >= 0)",
+                batch, (long long)ld_in, (long long)max_segments);
+  if (min_silence_frames < 1 || max_segment_frames < 0 || max_segment_frames == 1)
+    return fail(VASR_ERR_INVALID, "split_silence: min_silence_frames %d (>= 1), max_segment_frames %d (0 = no limit, or >= 2)",
+                min_silence_frames, max_segment_frames);
+  if (!std::isfinite(top_db)) return fail(VASR_ERR_INVALID, "split_silence: top_db is not finite");
+  if (!d_workspace) return fail(VASR_ERR_INVALID, "split_silence: NULL workspace");
+  if (!trim_shape_supported(frame_length, hop_length))
+    return fail(VASR_ERR_UNSUPPORTED, "split_silence: frame_length %d, hop_length %d: hop_length >= 1 and frame_length a multiple of "
+                "it, at most %d", frame_length, hop_length, kTrimMaxFrame);
+  const size_t need = split_workspace_bytes(batch, ld_in, frame_length, hop_length);
+  if (workspace_bytes < need)
+    return fail(VASR_ERR_INVALID, "split_silence: workspace of %zu bytes, %zu needed (vasr_split_silence_workspace_bytes)",
+                workspace_bytes, need);
+  const double factor = std::pow(10.0, -(double)top_db / 10.0);
+  launch_split_silence<T>(d_in, ld_in, d_len, batch, factor, frame_length, hop_length, min_silence_frames, max_segment_frames,
+                          d_bounds, max_segments, d_count, d_workspace, static_cast<hipStream_t>(stream));
+  return check_launch("split_silence");
+}
+
+template <typename T>
+static int gather_segments(const T* d_in, int64_t ld_in, int batch, const int32_t* d_row, const int64_t* d_start,
+                           const int64_t* d_len, int64_t segments, T* d_out, int64_t ld_out, vasr_stream stream) {
+  if (!d_in || !d_row || !d_start || !d_len || !d_out) return fail(VASR_ERR_INVALID, "gather_segments: NULL pointer");
+  if (d_in == d_out) return fail(VASR_ERR_INVALID, "gather_segments: d_out must not alias d_in");
+  if (batch <= 0 || ld_in < 0 || segments <= 0 || ld_out <= 0)
+    return fail(VASR_ERR_INVALID, "gather_segments: batch %d, ld_in %lld, segments %lld, ld_out %lld (batch, segments, ld_out >= 1, "
+                "ld_in >= 0)", batch, (long long)ld_in, (long long)segments, (long long)ld_out);
+  launch_gather_segments<T>(d_in, ld_in, batch, d_row, d_start, d_len, segments, d_out, ld_out, static_cast<hipStream_t>(stream));
+  return check_launch("gather_segments");
+}
+}  // extern "C++"
+
+int vasr_split_silence_f32(const float* d_in, int64_t ld_in, const int64_t* d_len, int batch, float top_db, int frame_length,
+                           int hop_length, int min_silence_frames, int max_segment_frames, int64_t* d_bounds, int64_t max_segments,
+                           int64_t* d_count, void* d_workspace, size_t workspace_bytes, vasr_stream stream) {
+  return split_silence<float>(d_in, ld_in, d_len, batch, top_db, frame_length, hop_length, min_silence_frames, max_segment_frames,
+                              d_bounds, max_segments, d_count, d_workspace, workspace_bytes, stream);
+}
+
+int vasr_split_silence_pcm16(const int16_t* d_in, int64_t ld_in, const int64_t* d_len, int batch, float top_db, int frame_length,
+                             int hop_length, int min_silence_frames, int max_segment_frames, int64_t* d_bounds, int64_t max_segments,
+                             int64_t* d_count, void* d_workspace, size_t workspace_bytes, vasr_stream stream) {
+  return split_silence<short>(d_in, ld_in, d_len, batch, top_db, frame_length, hop_length, min_silence_frames, max_segment_frames,
+                              d_bounds, max_segments, d_count, d_workspace, workspace_bytes, stream);
+}
+
+int vasr_gather_segments_f32(const float* d_in, int64_t ld_in, int batch, const int32_t* d_row, const int64_t* d_start,
+                             const int64_t* d_len, int64_t segments, float* d_out, int64_t ld_out, vasr_stream stream) {
+  return gather_segments<float>(d_in, ld_in, batch, d_row, d_start, d_len, segments, d_out, ld_out, stream);
+}
+
+int vasr_gather_segments_pcm16(const int16_t* d_in, int64_t ld_in, int batch, const int32_t* d_row, const int64_t* d_start,
+                               const int64_t* d_len, int64_t segments, int16_t* d_out, int64_t ld_out, vasr_stream stream) {
+  return gather_segments<short>(d_in, ld_in, batch, d_row, d_start, d_len, segments, d_out, ld_out, stream);
+}
+
 int vasr_set_gemm_mode(vasr_handle* h, int mode) {
   if (!h || mode < 0 || mode > 3)
     return fail(VASR_ERR_INVALID, "gemm mode must be 0 (fp32 MFMA), 1 (3 x bf16 split), 2 (2 x bf16 split, reduced) or "

@@ -424,6 +424,18 @@ size_t trim_workspace_bytes(int batch, int64_t ld_in, int frame_length, int hop)
 template <typename T>
 void launch_trim_silence(const T* in, int64_t ld_in, const int64_t* len, int batch, double factor, int frame_length, int hop,
                          T* out, int64_t ld_out, int64_t* len_out, int64_t* start, void* workspace, hipStream_t st);
+// split at silences (vasr_split_silence_f32): the trim's chunk sums, then one workgroup per row; the runs (frames) and the chunk
+// sums go through `workspace` (split_workspace_bytes, any address).  The caller checks the trim's frame forms, min_silence >= 1,
+// max_frames == 0 or >= 2, max_segments >= 0; two launches, no host sync.
+size_t split_workspace_bytes(int batch, int64_t ld_in, int frame_length, int hop);  // host only; SIZE_MAX where it does not fit
+template <typename T>
+void launch_split_silence(const T* in, int64_t ld_in, const int64_t* len, int batch, double factor, int frame_length, int hop,
+                          int min_silence, int max_frames, int64_t* bounds, int64_t max_segments, int64_t* count,
+                          void* workspace, hipStream_t st);
+// out[s][t] = in[row[s]][start[s] + t] for t < len[s], zero up to ld_out; a descriptor outside its row gives zeros.  One launch.
+template <typename T>
+void launch_gather_segments(const T* in, int64_t ld_in, int batch, const int32_t* row, const int64_t* start, const int64_t* len,
+                            int64_t segments, T* out, int64_t ld_out, hipStream_t st);
 
 // ---- beam search (beam_wave.hip, beam_group.hip) ----
 struct BeamLm {  // device-resident hashed back-off n-gram model

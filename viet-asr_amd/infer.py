@@ -448,6 +448,102 @@ class VietASR:
             rows.append(row)
         return rows
 
+    def transcribe_long(self, signals, sample_rate=None, top_db=60.0, min_silence=0.3, max_seconds=None, pad=None,
+                        batch_size=64, decoder="greedy", align=False):
+        """Recordings of any length: cut at their pauses on the device, transcribed as ordinary batches, every piece's text
+        returned with its time.  One 1-D signal (float, or int16 PCM) -> a dict; a list of signals -> a list of dicts:
+        {"text", "segments": [{"start", "end", "text"}, ...], "dropped"}.  "start" / "end" are seconds of the recording as
+        given, "text" is the non-empty segment texts joined by a space, "dropped" the number of segments too short for the
+        front end (n_fft / 2 samples or fewer after padding), which are not transcribed.  This replaces the reference CLI's
+        "audio file too long, skipped" (infer.py:201-203).
+
+        The recordings are uploaded once (int16 stays int16; a list is zero-padded to its longest member), resampled on the
+        device when ``sample_rate`` differs from the model's, and split by ``audio.split_silence`` (include/vasr.h:
+        librosa.effects.split's frames, frame_length 2048 and hop_length 512, pauses shorter than ``min_silence`` seconds
+        bridged, runs longer than ``max_seconds`` cut at their quietest frame; both converted to frames with floor, at least
+        1 and 2).  ``audio.plan_segments`` widens every segment by ``pad`` samples, without overlap -- the one host
+        synchronisation --, and ``audio.gather_segments`` builds batches of at most ``batch_size`` segments, sorted by length;
+        no audio goes back to the host.  Every batch runs with row_independent=True: a segment's text is what
+        ``transcribe_batch([that slice], row_independent=True)`` gives, whatever it was batched with.  Nothing here depends on
+        a receptive field: squeeze-and-excitation and group-normalised models run, which ``forward_long`` refuses.
+
+        max_seconds=None: the model definition's ``AudioToTextDataLayer.max_duration`` -- the longest utterance the model was
+        trained on --, 16.7 where that is absent or null.  pad=None: frame_length // 2 = 1024 samples, the half frame that
+        librosa's centred framing can hide in front of the first non-silent frame.  top_db=60 (librosa's default) and
+        min_silence=0.3 s (a common pause length) are CONVENTIONS, not values measured on speech.
+        decoder="beam" (instances built with decoder="beam" only) runs this instance's beam search + LM on every batch.
+        align=True adds "chars" and "words" to every segment (``align``'s entries: the forced alignment of the segment's text to
+        its log-probs, times shifted by the segment's start)."""
+        from . import audio, stages
+        from .engine import _pcm_to_float
+        if decoder not in ("greedy", "beam") or (decoder == "beam" and self.mode != "beam"):
+            raise ValueError("decoder must be 'greedy', or 'beam' on an instance constructed with decoder='beam'")
+        single = not isinstance(signals, (list, tuple))
+        sigs = [np.asarray(s) for s in ([signals] if single else signals)]
+        if not sigs or any(s.ndim != 1 for s in sigs):
+            raise ValueError("transcribe_long needs one 1-D signal or a non-empty list of them")
+        eng = self._fused_engine()
+        rate = int(self.model_definition["AudioToMelSpectrogramPreprocessor"]["sample_rate"])
+        frame_length, hop = 2048, 512
+        if max_seconds is None:
+            max_seconds = (self.model_definition.get("AudioToTextDataLayer") or {}).get("max_duration") or 16.7
+        m = max(1, int(np.floor(float(min_silence) * rate / hop)))
+        M = max(2, int(np.floor(float(max_seconds) * rate / hop)))
+        pad = frame_length // 2 if pad is None else int(pad)
+        min_samples = eng.frontend["n_fft"] // 2
+        # upload once: int16 as it is where every recording is, float32 otherwise
+        pcm = all(s.dtype == np.int16 for s in sigs)
+        lens = [len(s) for s in sigs]
+        host = np.zeros((len(sigs), max(max(lens), 1)), dtype=np.int16 if pcm else np.float32)
+        for b, s in enumerate(sigs):
+            host[b, : lens[b]] = s if pcm else np.asarray(_pcm_to_float(s), dtype=np.float32)
+        x = torch.from_numpy(host).to(eng.device)
+        length = torch.tensor(lens, dtype=torch.int64, device=eng.device)
+        if sample_rate is not None and int(sample_rate) != rate:
+            x, length = audio.resample(audio.pcm16_to_float(x) if pcm else x, length, sample_rate, rate)
+        bounds, count = audio.split_silence(x, length, top_db, frame_length, hop, m, M)
+        plan, dropped = audio.plan_segments(bounds, count, length, pad, min_samples)
+        results = [None] * len(plan)
+        order = sorted(range(len(plan)), key=lambda i: plan[i][2])
+        for lo in range(0, len(order), max(1, int(batch_size))):
+            idx = order[lo : lo + max(1, int(batch_size))]
+            seg_len = torch.tensor([plan[i][2] for i in idx], dtype=torch.int64, device=eng.device)
+            wav = audio.gather_segments(x, [plan[i][0] for i in idx], [plan[i][1] for i in idx], seg_len, plan[idx[-1]][2])
+            r = eng.forward(wav, seg_len, want_logp=align or decoder == "beam", want_pred=False, row_independent=True)
+            frames = eng.frames_of(seg_len)
+            if decoder == "beam":
+                texts = self.beam.decoder.decode_batch(r["logp"], self.beam.beam_width, frames=frames)
+            else:
+                texts = eng.texts(r["ids"], r["id_len"])
+            entries = [{"start": plan[i][1] / float(rate), "end": (plan[i][1] + plan[i][2]) / float(rate), "text": t}
+                       for i, t in zip(idx, texts)]
+            if align:
+                if decoder == "beam":
+                    ref, ref_len = self._reference_tokens([{"text": t} for t in texts], range(len(texts)))
+                    tgt, tgt_len = ref.to(eng.device), ref_len.to(eng.device)
+                else:
+                    tgt, tgt_len = r["ids"], r["id_len"]
+                out = stages.ctc_align(r["logp"], frames, tgt, tgt_len, len(self.labels))
+                score, start, end, logp, ids, n = (t.cpu().numpy() for t in (out["score"], out["start"], out["end"],
+                                                                             out["token_logp"], tgt.to(torch.int32),
+                                                                             tgt_len.to(torch.int32)))
+                if np.isnan(score).any():
+                    raise RuntimeError("the alignment score came back NaN for segments %s" % np.isnan(score).nonzero()[0].tolist())
+                sec = eng.frame_seconds()
+                for k, e in enumerate(entries):
+                    e["chars"], e["words"] = [], []
+                    if score[k] != -np.inf:
+                        chars = [self.labels[c] for c in ids[k, : n[k]]]
+                        e["chars"], e["words"] = alignment_entries(chars, start[k], end[k], logp[k], sec, e["start"])
+            for i, e in zip(idx, entries):
+                results[i] = e
+        out = [{"text": "", "segments": [], "dropped": int(d)} for d in dropped]
+        for (b, _, _), e in zip(plan, results):
+            out[b]["segments"].append(e)
+        for o in out:
+            o["text"] = " ".join(e["text"] for e in o["segments"] if e["text"])
+        return out[0] if single else out
+
     def launch_batch(self, signals, sample_rate=None, row_independent=False):
         """Asynchronous ``transcribe_batch``: returns a handle at once, ``.texts()`` waits (engine.QuartzNetCTC.launch)."""
         return self._fused_engine().launch(self._batch_signals(signals, sample_rate), row_independent)
