@@ -24,6 +24,16 @@ VASR_API int vasr_fused_tile_choice(int64_t tiles128, int compute_units);
  * (dual != 0) or without the folded residual, on tiles of tile_cols = 128 | 64 frames: VASR_FUSED_WAVES where it is set and the
  * form exists (the 128-frame tile), else the library's default (csrc/encoder_fused.hip fused_waves_choice; pure host arithmetic). */
 VASR_API int vasr_fused_waves_choice(int kernel, int dual, int tile_cols);
+/* Where one encoder pass puts its tensors (csrc/vasr_host.h BufRotation, through run_encoder's dry form; pure host arithmetic, no
+ * device is touched).  h: a handle with its weights loaded, finalized or not (not finalized: the plan of a device of 256
+ * compute units).  samples > 0: the pass of vasr_transcribe_greedy_*
+ * on `batch` clips of that many samples (every slice of vasr_set_slices in turn); else the pass of vasr_encoder_f32 on
+ * mel_frames frames.  Returns the number of launches (negative: a VASR_ERR_* code) and fills out[5 * i ...] of the first `cap`
+ * with (kind, dst, src, src2, res): kind 0 = copy of a block input into the dense-residual pane buffer, 1 = depthwise -> D,
+ * 2 = a sub-block's GEMM, 3 = fused depthwise + pointwise, 4 = a residual-branch GEMM, 5 = squeeze-and-excitation,
+ * 6 = GroupNorm (5, 6 and a max-mode 4 work in place); buffers 0-3 = the rotation buffers, 4 = D, 5 = the pane buffer,
+ * 6 = the encoder's input, 7 = its output, -1 = none.  VASR_BUF_ROTATE=pingpong|inplace picks the rotation. */
+VASR_API int vasr_plan_buffers(vasr_handle* h, int batch, int64_t samples, int64_t mel_frames, int32_t* out, int cap);
 /* The kernel vasr_resample_f32 runs a ratio on (csrc/audio.hip resample_form, which launch_resample itself calls; pure host
  * arithmetic): 2 = integer up-sampling (ratio p / 1, 2 <= p <= 16), 1 = the phase kernel (p / q with a denominator up to 1000
  * found within 1e-12 and wing tables within 60 KB of LDS), 0 = the generic per-output gather.  *p / *q (either may be NULL) receive

@@ -129,6 +129,7 @@ DEV_SIGNATURES = {
     "vasr_profile_bracket_overhead": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double)]),
     "vasr_fused_tile_choice": (C.c_int, [C.c_int64, C.c_int]),
     "vasr_fused_waves_choice": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "vasr_plan_buffers": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int]),
     "vasr_resample_form": (C.c_int, [C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vasr_pack_pointwise": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "vasr_conv_gemm_weights": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),

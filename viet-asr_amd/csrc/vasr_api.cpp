@@ -14,6 +14,9 @@
 #include <vector>
 
 #include "vasr.h"
+#ifdef VASR_DEVTOOLS
+#include "vasr_devtools.h"   // vasr_plan_buffers: the one devtools entry point that needs the handle's insides
+#endif
 #include "vasr_host.h"
 #include "vasr_internal.h"
 
@@ -203,6 +206,7 @@ struct vasr_handle {
   // useful way (one workgroup per CU each), so slicing is OFF by default
   int slices = getenv("VASR_SLICES") ? atoi(getenv("VASR_SLICES")) : 1;
   bool slice_ready = false;
+  bool plan_only = false;         // vasr_plan_buffers' host-side shadow of an unfinalized handle: upload() allocates nothing
   bool row_independent = false;   // vasr_set_row_independent
   int busy_cus = 0;               // vasr_set_busy_cus
   DevSwitches sw = dev_switches();   // kernel-selection switches of the devtools build (vasr_internal.h); defaults in the product
@@ -229,6 +233,11 @@ namespace {
 
 template <class T>
 int upload(vasr_handle* h, const std::vector<T>& v, T** out) {
+  if (h->plan_only) {   // a host-side shadow: the pointer only says "this table exists", nothing ever reads through it
+    alignas(16) static char no_table[16];
+    *out = reinterpret_cast<T*>(no_table);
+    return 0;
+  }
   void* p = nullptr;
   HIP_TRY(hipMalloc(&p, std::max<size_t>(v.size() * sizeof(T), 16)));
   h->dev_allocs.push_back(p);
@@ -947,7 +956,9 @@ enum { kProfFrontend = 0, kProfDepthwise = 1, kProfPointwise = 2, kProfHead = 3,
 
 // GEMM dispatch: exact-fp32 MFMA kernel, or the 3 x bf16 split kernel when selected and the layer has that pack.
 // Returns 1 when the launch published a.amax_y (only the split kernel does), 0 when not, < 0 on error.
-int run_pointwise(vasr_handle* h, PwArgs& a, const ConvLayer& W, hipStream_t st) {
+// dry (vasr_plan_buffers): nothing is launched, the return value is the one the launch would give.
+int run_pointwise(vasr_handle* h, PwArgs& a, const ConvLayer& W, hipStream_t st, bool dry = false) {
+  if (dry) return h->gemm_mode >= 1 && W.d_w3 && a.amax_y.p != nullptr ? 1 : 0;
   if (h->gemm_mode >= 1 && W.d_w3) {
     int arith = h->gemm_mode == 2 ? 1 : 0;
     a.wt = reinterpret_cast<const float*>(W.d_w3);
@@ -1012,10 +1023,14 @@ int fused_tile_cols(const vasr_handle* h, int batch, int64_t ld) {
 // Encoder over an input [B][feat_in][x_ld]; writes [B][c_last][out_ld] (T1 valid frames).
 // enc_amax (optional): receives the maxima table of the encoder output when one was published (fp16-split mode, padded
 // output pitch), for the CTC head of the fused path; the table lives in the workspace until the next encoder pass.
+// rec (vasr_plan_buffers): a dry pass -- nothing is launched and no device memory is touched, every launch the pass would
+// make is recorded as (kind, dst, src, src2, res) in buffer numbers (vasr_host.h); ws is then any base address.
+struct PlanRec { std::vector<int32_t> v; };
 int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const int64_t* seq, int batch,
                 float* out, int64_t out_ld, float* enc_len, char* ws, const WsPlan& p, hipStream_t st,
                 AmaxTab* enc_amax = nullptr, const int64_t* wav_len = nullptr, const int32_t** own_frames = nullptr,
-                bool chain_done = false) {
+                bool chain_done = false, PlanRec* rec = nullptr) {
+  const bool dry = rec != nullptr;
   int32_t* lens_tab = reinterpret_cast<int32_t*>(ws + p.lens_tab);
   auto lens = [&](int step) { return lens_tab + (size_t)step * batch; };
   // row-independent mode (fused path): everything the CTC head sees of a row must depend on that row alone, also the
@@ -1023,7 +1038,7 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
   // would produce, and the head zeroes the columns behind them (they are not decoded in this mode)
   const bool own = h->row_independent && wav_len != nullptr;
   // (the fused path has run the chain as extra workgroups of its normalisation launch: launch_normalize_chain)
-  if (!chain_done)
+  if (!chain_done && !dry)
     launch_len_chain(seq, batch, h->d_steps, (int)h->steps.size(), lens_tab, enc_len, st, own ? wav_len : nullptr,
                      h->fe.hop_length, (int)p.T1);
   const int32_t* own_tab = own ? lens((int)h->steps.size() + 1) : nullptr;
@@ -1031,6 +1046,41 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
   float* bufs[4] = {reinterpret_cast<float*>(ws + p.bufP), reinterpret_cast<float*>(ws + p.bufQ),
                     reinterpret_cast<float*>(ws + p.bufR), reinterpret_cast<float*>(ws + p.bufS)};
   float* D = reinterpret_cast<float*>(ws + p.bufD);
+  // Where the sub-block outputs go (vasr_host.h BufRotation), and the check every launch passes before it is made: its
+  // destination is none of its own sources, not the live block input, not the live R, not the pane buffer
+  BufRotation rot;
+  rot.inplace = h->sw.buf_inplace;
+  const float* pane_lo = reinterpret_cast<const float*>(ws + p.pane);
+  const float* pane_hi = reinterpret_cast<const float*>(ws + p.encp);
+  auto buf_of = [&](const float* q) -> int {
+    if (!q) return kBufNone;
+    for (int i = 0; i < kBufRot; ++i) if (q == bufs[i]) return i;
+    if (q == D) return kBufD;
+    if (q == out) return kBufOut;
+    if (q == x) return kBufIn;
+    return h->pane_c_max && q >= pane_lo && q < pane_hi ? kBufPane : kBufNone;
+  };
+  auto check_dst = [&](int kind, const float* dst, const float* sx, const float* sx2, const float* sr) -> int {
+    const int d = buf_of(dst), a = buf_of(sx), b = buf_of(sx2), r = buf_of(sr);
+    if (const char* why = rot.refuse(kind, d, a, b, r))
+      return fail(VASR_ERR_STATE, "encoder buffers: %s (launch kind %d: dst %d, src %d, src2 %d, res %d)", why, kind, d, a, b, r);
+    return 0;
+  };
+  auto commit = [&](int kind, const float* dst, const float* sx, const float* sx2, const float* sr) {
+    const int d = buf_of(dst), a = buf_of(sx), b = buf_of(sx2), r = buf_of(sr);
+    rot.launched(d, a, b, r);
+    if (rec) rec->v.insert(rec->v.end(), {kind, d, a, b, r});
+  };
+  auto note = [&](int kind, const float* dst, const float* sx, const float* sx2, const float* sr) -> int {
+    if (int rc = check_dst(kind, dst, sx, sx2, sr)) return rc;
+    commit(kind, dst, sx, sx2, sr);
+    return 0;
+  };
+  // the rotation buffer the next sub-block output goes to (over_cur: the launch does not read the current tensor)
+  auto next_dst = [&](bool over_cur) -> float* {
+    const int d = rot.pick(over_cur);
+    return d >= 0 ? bufs[d] : nullptr;   // (nullptr: no dead buffer -- check_dst refuses it)
+  };
   const float* cur = x;
   int64_t cur_ld = x_ld, cur_T = T;
   // fp16-split GEMMs: maxima rows, indexed by the length-chain step of the conv that produced the tensor
@@ -1058,6 +1108,8 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
     a.frames = (int)frames; a.store_cols = store_cols; a.lens = pool_lens; a.w1 = L.d_w1; a.w2 = L.d_w2;
     a.sums = se_sums; a.scale = se_scale; a.zero_lens = zero_lens; a.relu = relu; a.act = h->act; a.accumulate = acc;
     a.amax_y = am; a.lens_y = lens_y;
+    if (int rc = note(kPlanSe, sy, sx, nullptr, nullptr)) return rc;
+    if (dry) return 0;
     ProfScope ps(h, kProfDepthwise, st, 4.0 * L.c * L.hidden * (double)batch,
                  4.0 * (acc ? 4.0 : 3.0) * L.c * (double)store_cols * batch);
     const int e = launch_se(a, st);
@@ -1077,6 +1129,8 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
     a.row_mean = nrm_ws; a.row_m2 = nrm_ws + (size_t)batch * h->norm_c_max;
     a.g_mean = nrm_ws + (size_t)2 * batch * h->norm_c_max; a.g_rstd = a.g_mean + (size_t)batch * h->norm_g_max;
     a.zero_lens = zero_lens; a.relu = relu; a.act = h->act; a.amax_y = am; a.lens_y = lens_y;
+    if (int rc = note(kPlanNorm, ny, nx, nullptr, add)) return rc;
+    if (dry) return 0;
     // (counted with the depthwise class, as the SE passes are: statistics and affine, ~5 flops per element; two reads for
     // the statistics, a read and a write to apply)
     ProfScope ps(h, kProfDepthwise, st, 5.0 * L.c * (double)frames * batch,
@@ -1091,12 +1145,11 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
     const float* blk_in = cur;
     const int64_t blk_ld = cur_ld;
     blk_amax = cur_amax;
-    // scratch buffers that are not the block input (the fused residual reads it until the block's last GEMM):
-    // sub-block outputs ping-pong between the first two, an unfused residual result takes the third
-    float* free3[3];
-    int nf = 0;
-    for (float* q : bufs) if (q != blk_in && nf < 3) free3[nf++] = q;
-    float* R = free3[2];
+    // the block input stays where it is (the fused residual reads it until the block's last GEMM), an unfused residual result
+    // takes the third rotation buffer that is not the block input, the sub-block outputs go where the rotation sends them
+    const int blk_buf = buf_of(blk_in);
+    rot.begin_block(blk_buf < kBufRot ? blk_buf : kBufNone, B.has_res && !B.fused_res);
+    float* R = bufs[rot.pp[2]];
     float* panes = reinterpret_cast<float*>(ws + p.pane);
     const int64_t pane_bs = (int64_t)h->pane_c_max * cur_ld;   // batch stride of the pane buffer, elements
     if (B.keep_input && B.pane == 0) pane_ld = cur_ld;
@@ -1106,8 +1159,10 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
                   (long long)cur_ld);
     if (B.keep_input) {
       // this block's input is pane B.pane of its dense run (parts/jasper.py:446-447: xs + [out])
-      HIP_TRY(hipMemcpy2DAsync(panes + (int64_t)B.pane_off * cur_ld, (size_t)pane_bs * 4, cur, (size_t)B.pane_c * cur_ld * 4,
-                               (size_t)B.pane_c * cur_ld * 4, batch, hipMemcpyDeviceToDevice, st));
+      if (int rc = note(kPlanPaneCopy, panes + (int64_t)B.pane_off * cur_ld, cur, nullptr, nullptr)) return rc;
+      if (!dry)
+        HIP_TRY(hipMemcpy2DAsync(panes + (int64_t)B.pane_off * cur_ld, (size_t)pane_bs * 4, cur, (size_t)B.pane_c * cur_ld * 4,
+                                 (size_t)B.pane_c * cur_ld * 4, batch, hipMemcpyDeviceToDevice, st));
     }
     // residual panes' masks: the block input lengths; a last block's residual keeps its padding columns (the encoder output's)
     const int32_t* res_zero = last_block ? nullptr : lens(B.first_step);
@@ -1132,13 +1187,14 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
         a.bsx = pane_bs;
         if (want_amax) {   // fp16 split: one scale from the maxima of all the channels the GEMM reads
           a.amax_x = free_tab(AmaxTab{});
-          launch_amax(px, cur_ld, W.cin, (int)cur_T, lens(B.first_step), batch, &a.amax_x, st, pane_bs);
+          if (!dry) launch_amax(px, cur_ld, W.cin, (int)cur_T, lens(B.first_step), batch, &a.amax_x, st, pane_bs);
         }
       }
+      if (int rc = note(kPlanResGemm, Rq, px, nullptr, a.res)) return rc;
       {
         ProfScope ps(h, kProfPointwise, st, 2.0 * W.cin * W.cout * (double)cur_T * batch,
                      4.0 * W.m_pad * (double)cur_ld * batch);   // bytes of class 2 = what the GEMM STORES (its epilogue's share of the time)
-        if (run_pointwise(h, a, W, st) < 0) return VASR_ERR_HIP;
+        if (run_pointwise(h, a, W, st, dry) < 0) return VASR_ERR_HIP;
       }
       // GroupNorm, then the residual branch's SqueezeExcite (parts/jasper.py:275-280)
       if (G.norm.d_gamma && run_norm(G.norm, Rq, G.se.d_w1 ? Rq : R, (!G.se.d_w1 && q > 0) ? R : nullptr, cur_ld, cur_ld, cur_T,
@@ -1148,7 +1204,6 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
                               q > 0 ? (h->res_max ? 2 : 1) : 0, nullptr, nullptr))
         return VASR_ERR_HIP;
     }
-    int flip = 0;
     for (size_t r = 0; r < B.subs.size(); ++r) {
       SubBlock& S = B.subs[r];
       const bool last_sub = r + 1 == B.subs.size();
@@ -1170,8 +1225,8 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
           // a folded residual must come from a 256-channel block input (K = 256 + 256): the kernel's second K range is 4 chunks
           (fuse_res ? (blk_amax.p && blk_ld == cur_ld && WF.cin == 2 * S.dw.cin && B.fused_k1 == S.dw.cin) : WF.cin == S.dw.cin) &&
           cur_ld % kTimeTile == 0 && !enc_out && (f_cols = fused_tile_cols(h, batch, cur_ld)) != 0) {
-        float* dst = free3[flip];
-        flip ^= 1;
+        float* dst = next_dst(false);   // (the kernel reads cur)
+        if (int rc = check_dst(kPlanFused, dst, cur, fuse_res ? blk_in : nullptr, nullptr)) return rc;
         FusedLaunch f{};
         f.x = cur; f.ldx = cur_ld; f.lens_in = lens(S.dw.step); f.lens_out = lens(S.dw.step + 1);
         f.taps = S.dw.d_ftaps; f.dw_l1 = S.dw.f_l1; f.amax_x = cur_amax;
@@ -1182,19 +1237,21 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
         f.batch = batch; f.kernel = S.dw.kernel;
         f.tile_cols = f_cols;
         f.waves = h->sw.fused_waves;
-        int e;
-        {
+        int e = 0;   // (a dry pass: every shape that reaches this point has an instantiation)
+        if (!dry) {
           ProfScope ps(h, kProfFused, st, 2.0 * WF.cin * WF.cout * (double)cur_T * batch,
                        4.0 * (2.0 + (fuse_res ? 1.0 : 0.0)) * S.dw.cin * (double)cur_T * batch);
           e = launch_fused_dwpw(f, st, &f.amax_y.n);
         }
         if (e > 0) return fail(VASR_ERR_HIP, "fused dw -> pw: %s", hipGetErrorString((hipError_t)e));
         if (e == 0) {
+          commit(kPlanFused, dst, cur, f.x2, nullptr);
+          rot.wrote(buf_of(dst));
           cur = dst;
           cur_amax = f.amax_y;
           continue;
         }
-        flip ^= 1;   // shape not covered after all: the two-kernel path below
+        // shape not covered after all: the two-kernel path below (nothing was committed)
       }
       if (S.separable) {
         const int64_t t_out = conv_out_frames(cur_T, S.dw);
@@ -1207,8 +1264,9 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
         // of packed FMAs; 256 channels, K = 33 / 39: 12.8 / 12.6 against 13.3 / 13.4), else packed FMAs.
         // VASR_DW_MFMA=0 keeps the packed-FMA kernels.
         const bool dw_mfma = h->sw.dw_mfma;
-        int e = -1;
-        if (want_amax && dw_mfma && cur_amax.p && S.dw.d_taps)
+        if (int rc = note(kPlanDepthwise, D, cur, nullptr, nullptr)) return rc;
+        int e = dry ? 0 : -1;
+        if (!dry && want_amax && dw_mfma && cur_amax.p && S.dw.d_taps)
           e = launch_depthwise_mfma(cur, cur_ld, S.dw.d_taps, S.dw.d_tap_inv, lens(S.dw.step), lens(S.dw.step + 1), cur_amax,
                                     batch, S.dw.cin, S.dw.kernel, S.dw.dilation, D, ld_out, am.p ? &am : nullptr, st);
         if (e > 0) return fail(VASR_ERR_HIP, "depthwise (MFMA): %s", hipGetErrorString((hipError_t)e));
@@ -1224,12 +1282,12 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
           // channels (a grouped conv's conv_cin is one group's)
           if (want_amax && !gx_amax.p) {
             gx_amax = free_tab(AmaxTab{});
-            launch_amax(cur, cur_ld, S.pw.conv_cin * S.pw.groups, (int)cur_T, g_lens, batch, &gx_amax, st);
+            if (!dry) launch_amax(cur, cur_ld, S.pw.conv_cin * S.pw.groups, (int)cur_T, g_lens, batch, &gx_amax, st);
           }
         }
       }
-      float* dst = free3[flip];
-      flip ^= 1;
+      // (the GEMM of the two-kernel separable path reads D: it may store over the current tensor)
+      float* dst = next_dst(S.separable);
       // (a K-tap conv's output has its own pitch: stride 2 halves the frames)
       int64_t dst_ld = S.pw.conv_cin ? pad_frames(g_T) : gx_ld;
       if (enc_out) { dst = out; dst_ld = out_ld; }
@@ -1265,12 +1323,14 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
         a.amax_y = free_tab(gx_amax);
         a.lens_y = enc_out ? own_tab : lens(S.pw.step + 1);
       }
+      if (int rc = note(kPlanGemm, dst, gx, a.x2, a.res)) return rc;
       int published;
       {
         ProfScope ps(h, kProfPointwise, st, 2.0 * W.cin * W.cout * (double)g_T * batch, 4.0 * W.m_pad * (double)dst_ld * batch);
-        published = run_pointwise(h, a, W, st);
+        published = run_pointwise(h, a, W, st, dry);
       }
       if (published < 0) return VASR_ERR_HIP;
+      rot.wrote(buf_of(dst));
       // GroupNorm of the conv's output over its own lengths, then the activation (the last sub-layer's: after the residual
       // sum, or after its SE); the normalized tensor's maxima replace the ones the GEMM published
       if (nrm) {
@@ -1291,7 +1351,7 @@ int run_encoder(vasr_handle* h, const float* x, int64_t x_ld, int64_t T, const i
     }
   }
   if (enc_amax) *enc_amax = cur_amax;
-  return check_launch("encoder");
+  return dry ? 0 : check_launch("encoder");
 }
 
 int run_decoder(vasr_handle* h, const float* encp, int64_t ld, int64_t T1, int batch, float* logits, float* logp,
@@ -1501,17 +1561,22 @@ int vasr_set_classifier(vasr_handle* h, int feat_in, int num_classes, int poolin
   return 0;
 }
 
+// vasr_finalize's checks of the encoder, before anything touches the device
+static int check_encoder(vasr_handle* h) {
+  int rc;
+  if (h->res_max)
+    for (size_t i = 0; i < h->blocks.size(); ++i)
+      if (h->blocks[i].norm_g)
+        return fail(VASR_ERR_UNSUPPORTED, "block %zu: residual_mode max with group, instance or layer normalization", i);
+  if ((rc = check_groups(h)) || (rc = check_se(h))) return rc;
+  return check_norm(h);
+}
+
 int vasr_finalize(vasr_handle* h) {
   if (!h) return fail(VASR_ERR_INVALID, "null handle");
   if (h->finalized) return 0;
   int rc;
-  if (h->has_encoder && h->res_max)
-    for (size_t i = 0; i < h->blocks.size(); ++i)
-      if (h->blocks[i].norm_g)
-        return fail(VASR_ERR_UNSUPPORTED, "block %zu: residual_mode max with group, instance or layer normalization", i);
-  if (h->has_encoder && (rc = check_groups(h))) return rc;
-  if (h->has_encoder && (rc = check_se(h))) return rc;
-  if (h->has_encoder && (rc = check_norm(h))) return rc;
+  if (h->has_encoder && (rc = check_encoder(h))) return rc;
   if (h->has_classifier && (rc = check_classifier(h))) return rc;
   if (h->has_frontend && (rc = build_frontend(h))) return rc;
   if (h->has_encoder && (rc = build_encoder(h))) return rc;
@@ -2154,6 +2219,57 @@ int vasr_set_slices(vasr_handle* h, int slices) {
   h->slices = slices;
   return 0;
 }
+
+#ifdef VASR_DEVTOOLS
+// include/vasr_devtools.h.  An unfinalized handle is planned on a host-side shadow: the same checks and build_encoder, with
+// upload() allocating nothing; the pass itself is run_encoder's dry form, so the plan is made by the code that runs.
+int vasr_plan_buffers(vasr_handle* h, int batch, int64_t samples, int64_t mel_frames, int32_t* out, int cap) {
+  if (!h || !h->has_encoder || batch <= 0 || (samples <= 0 && mel_frames <= 0) || cap < 0 || (cap > 0 && !out))
+    return fail(VASR_ERR_INVALID, "bad argument");
+  if (samples > 0 && !(h->has_frontend && h->has_decoder))
+    return fail(VASR_ERR_STATE, "a plan by samples is the transcribe path's: the handle needs a front end and a CTC head");
+  if (h->profiling) return fail(VASR_ERR_STATE, "profiling is active");
+  std::unique_ptr<vasr_handle> shadow;
+  vasr_handle* e = h;
+  if (!h->finalized) {
+    shadow.reset(new vasr_handle(*h));
+    e = shadow.get();
+    e->plan_only = true;
+    int rc;
+    if ((rc = check_encoder(e)) || (rc = build_encoder(e))) return rc;
+    e->weights.clear();
+  }
+  PlanRec rec;
+  char* base = reinterpret_cast<char*>(uintptr_t{1} << 40);   // (no memory behind it: a dry pass only compares addresses)
+  const int64_t T = samples > 0 ? vasr_mel_frames(e, samples) : mel_frames;
+  if (samples > 0) {   // transcribe_any: every slice of the batch through transcribe_part
+    const int n = n_slices(e, batch);
+    for (int i = 0; i < n; ++i) {
+      const int nb = (int)((int64_t)batch * (i + 1) / n) - (int)((int64_t)batch * i / n);
+      const WsPlan p = plan_ws(e, nb, T);
+      AmaxTab enc_amax{};
+      const int32_t* own_frames = nullptr;
+      if (int rc = run_encoder(e, reinterpret_cast<float*>(base + p.melp), p.Tp0, T, reinterpret_cast<int64_t*>(base + p.seq), nb,
+                               reinterpret_cast<float*>(base + p.encp), p.Tp1, nullptr, base, p, nullptr, &enc_amax,
+                               reinterpret_cast<const int64_t*>(base), &own_frames, true, &rec))
+        return rc;
+    }
+  } else {             // vasr_encoder_f32: port tensors outside the workspace
+    const WsPlan p = plan_ws(e, batch, T);
+    const Block& b0 = e->blocks[0];
+    const bool in_place = b0.subs[0].separable && !b0.has_res;
+    float* port_in = reinterpret_cast<float*>(base + p.total + 256);
+    float* port_out = reinterpret_cast<float*>(base + p.total + 512);
+    if (int rc = run_encoder(e, in_place ? port_in : reinterpret_cast<float*>(base + p.melp), in_place ? T : p.Tp0, T,
+                             reinterpret_cast<int64_t*>(base + p.seq), batch, port_out, p.T1, nullptr, base, p, nullptr, nullptr,
+                             nullptr, nullptr, false, &rec))
+      return rc;
+  }
+  const int n = (int)(rec.v.size() / 5);
+  if (out) std::copy_n(rec.v.begin(), (size_t)std::min(n, cap) * 5, out);
+  return n;
+}
+#endif
 
 size_t vasr_beam_workspace_bytes(int batch, int64_t frames) {
   // back-pointer rows [B][T][128] u32, then the LM-cache key log [B][T * 128] u64 (beam_wave.hip: eoslog)

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <initializer_list>
+#include <string>
 #include <vector>
 
 #include "vasr.h"
@@ -41,6 +42,14 @@ const vasr::DevSwitches& vasr::dev_switches() {
     s.fused_residual = num("VASR_NO_FUSED_RESIDUAL", 0, {0, 1}) == 0;
     s.beam_group = num("VASR_BEAM_GROUP", -1, {-1, 0, 1, 4});
     s.no_grouped = num("VASR_NO_GROUPED", 0, {0, 1}) != 0;
+    if (const char* e = getenv("VASR_BUF_ROTATE")) {
+      const std::string v(e);
+      if (v != "pingpong" && v != "inplace") {
+        fprintf(stderr, "vasr (devtools build): VASR_BUF_ROTATE=%s is not a documented value -- refusing to guess\n", e);
+        abort();
+      }
+      s.buf_inplace = v == "inplace";
+    }
     return s;
   }();
   return sw;

@@ -29,6 +29,7 @@ struct DevSwitches {
   bool fused_residual = true;   // VASR_NO_FUSED_RESIDUAL=1: a block's residual branch as its own GEMM, not as a second K range
   int beam_group = -1;          // VASR_BEAM_GROUP=0|1: always one wavefront per utterance, 4: always four
   bool no_grouped = false;      // VASR_NO_GROUPED=1: every grouped layer as its block-diagonal dense form (no grouped GEMM)
+  bool buf_inplace = true;      // VASR_BUF_ROTATE=pingpong|inplace: where run_encoder's sub-block outputs go (vasr_host.h BufRotation)
 };
 #ifdef VASR_DEVTOOLS
 const DevSwitches& dev_switches();
