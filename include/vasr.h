@@ -624,6 +624,87 @@ VASR_API int vasr_gather_segments_pcm16(const int16_t* d_in, int64_t ld_in, int 
                                         const int64_t* d_start, const int64_t* d_len, int64_t segments, int16_t* d_out,
                                         int64_t ld_out, vasr_stream stream);
 
+/* ---- audio perturbation: the arithmetic of AudioAugmentor (parts/perturb.py) on a padded float32 batch -------------------
+ * Gain, shift, noise at an SNR, white noise and convolution with a room impulse response, for robustness sweeps without a
+ * round trip through the host.  The host draws the random parameters (viet-asr_amd/perturb.py consumes the generators as the
+ * reference's per-utterance calls do) and uploads them as small per-row arrays; these entry points are the arithmetic.  An
+ * int16 batch goes through vasr_pcm16_to_f32 first.  Common to all of them: no handle, no atomics, no host synchronisation;
+ * a row's length is n = clamp(d_len[b], 0, ld_in); samples at or behind it are never read as data (the caller's padding may
+ * hold NaN); EVERY element of every non-NULL output is written, zeros behind a row's length up to ld_out; a row's bits do
+ * not depend on the other rows, on the batch size, on ld_in or on the row's alignment; every argument is checked before a
+ * device is touched, VASR_ERR_INVALID wins over VASR_ERR_UNSUPPORTED, limits are reported in vasr_last_error().  tests/
+ * perturb_reference.py is the float64 restatement; DESIGN section 7h has the kernels.  (added within ABI 8)
+ *
+ * vasr_mean_square_f32: d_ms[b] = mean(x^2) of row b in float64, the argument of AudioSegment.rms_db (parts/segment.py:
+ * 136-139; the reference takes the mean in float32).  A float32 square is exact in float64; the sums run over chunks of 4096
+ * samples counted from the row's first one (thread t of 256 adds positions 4 t + 1024 i + {0 .. 3} in ascending order, the
+ * threads are added in a binary tree), the chunk sums are added in the same fixed order, the total is divided by n: within
+ * n 2^-53 of the exact sum.  n == 0 gives 0.0.  Two launches.  The chunk sums go through d_workspace:
+ * vasr_mean_square_workspace_bytes(batch, ld_in) bytes at any address (8 per 4096 samples + 256), contents undefined before
+ * and after; the function is host only and returns 0 for arguments the call refuses.  NULL d_in / d_len / d_ms /
+ * d_workspace, batch <= 0, ld_in < 0 and a workspace smaller than required return VASR_ERR_INVALID. */
+VASR_API size_t vasr_mean_square_workspace_bytes(int batch, int64_t ld_in);
+VASR_API int vasr_mean_square_f32(const float* d_in, int64_t ld_in, const int64_t* d_len, int batch, double* d_ms,
+                                  void* d_workspace, size_t workspace_bytes, vasr_stream stream);
+
+/* vasr_noise_plan_f64: NoisePerturbation.perturb (parts/perturb.py:94-107) restated in float64 and product form, one launch.
+ * Per row b: n = max(d_len[b], 0), ms_x = d_ms_x[b], the noise row r = d_row[b] with N = max(d_noise_len[r], 0) samples and
+ * mean square ms_v = d_ms_v[r], snr_db = d_snr_db[b], u = d_u[b] in [0, 1) (the one random() that uniform(0.0, .) consumes):
+ *   d_scale[b] = (float) min(sqrt(ms_x / ms_v) * 10^(-snr_db / 20), 10^(max_gain_db / 20)), which is 10^(gain / 20) of the
+ *                reference's noise_gain_db = min(rms_db(x) - rms_db(v) - snr_db, max_gain_db); the cap is at most FLT_MAX.
+ *                ms_x == 0 gives 0 (the reference: 0 or NaN); ms_v == 0 with ms_x > 0 gives the cap;
+ *   d_start[b]:  for N > n, rint(((N / sr - n / sr) * u) * sr) in doubles, each operation rounded once, half to even -- the
+ *                reference's start_time = uniform(0.0, noise.duration - data.duration) and int(round(start_time * sr)) --
+ *                clamped to [0, N - n]; for N <= n it is 0 and vasr_mix_f32 wraps the noise modulo N (a stated deviation:
+ *                the reference raises there).
+ * r < 0 or r >= noise_rows gives scale 0 and start 0: nothing is added.  NULL pointers, batch / noise_rows / sample_rate <= 0
+ * and a NaN max_gain_db return VASR_ERR_INVALID. */
+VASR_API int vasr_noise_plan_f64(const int64_t* d_len, const double* d_ms_x, const int32_t* d_row, const double* d_snr_db,
+                                 const double* d_u, int batch, const int64_t* d_noise_len, const double* d_ms_v, int noise_rows,
+                                 double max_gain_db, int sample_rate, float* d_scale, int64_t* d_start, vasr_stream stream);
+
+/* vasr_mix_f32: gain, shift and an additive signal in one memory-bound pass; the length does not change.  Per row, with
+ * g = d_gain[b], s = d_shift[b] (samples), c = d_scale[b], r = d_add_row[b], v = row r of d_add [add_rows][ld_add] with
+ * N = clamp(d_add_len[r], 0, ld_add) samples, st = d_start[b] mod N:
+ *   d_out[b][t] = g * x[t + s] + c * v[(st + t) mod N]     for t < n, zero from n up to ld_out,
+ * in float32 as fmaf(c, v, fl(g * x)).  The x term is 0 where t + s falls outside [0, n): ShiftPerturbation's copy in place
+ * with zero fill, for both signs (perturb.py:69-81; s = int(shift_ms * sr // 1000)); a shift with |s| > n is ignored, the
+ * reference's duration rule in samples.  g is GainPerturbation's 10^(gain_db / 20).  d_gain, d_shift and d_add may each be
+ * NULL (1, 0, nothing added); d_start may be NULL (0).  With c == 0, r outside [0, add_rows) or N == 0 the addend is NOT
+ * read: a NaN there changes nothing.  With g == 1, s == 0 and nothing added the row is a bit-for-bit copy.  White noise is
+ * an addend the caller draws on the device (one row per utterance, r = b).  One launch, 16-byte loads and stores where the
+ * addresses allow (the same arithmetic either way).  d_out must not alias d_in or d_add; ld_out >= ld_in >= 0.
+ * NULL d_in / d_len / d_out, an addend without d_add_len / d_add_row / d_scale, ld_add < 0 or add_rows <= 0 with an addend,
+ * batch <= 0, a negative ld and ld_out < ld_in return VASR_ERR_INVALID. */
+VASR_API int vasr_mix_f32(const float* d_in, int64_t ld_in, const int64_t* d_len, int batch, const float* d_gain,
+                          const int64_t* d_shift, const float* d_add, int64_t ld_add, int add_rows, const int64_t* d_add_len,
+                          const int32_t* d_add_row, const float* d_scale, const int64_t* d_start, float* d_out, int64_t ld_out,
+                          vasr_stream stream);
+
+/* Convolution with a bank of impulse responses: ImpulsePerturbation (perturb.py:56-60), scipy.signal.fftconvolve(x, h,
+ * "full"), length n + m - 1.  d_ir [R][ld_ir] holds the responses, m = clamp(d_ir_len[r], 1, ld_ir) taps each.
+ * vasr_convolve_prepare_f32 runs once per bank: it writes the spectra of the zero-padded partitions of every response into
+ * d_spectra (vasr_convolve_spectra_bytes(R, ld_ir) bytes, 8-byte aligned: 16 KiB per 2048 taps and response + 8 KiB; host only,
+ * 0 for arguments the calls refuse), behind the transform's twiddle factors, which it builds on the host (float64 rounded to
+ * float32) and copies there with one hipMemcpyAsync from host memory -- the one call of this group that is not launches only.  The buffer is opaque and belongs to this version of the library.
+ * vasr_convolve_f32 runs per batch: with r = d_ir_row[b],
+ *   d_out[b][t] = sum_k h_r[k] x[t - k]   for t < n + m - 1, zero up to ld_out; d_len_out[b] = n + m - 1;
+ *   r < 0 (or r >= R) copies the row bit for bit, d_len_out[b] = n;   n == 0 gives d_len_out[b] = 0.
+ * Uniformly partitioned overlap-save in ONE kernel, transform length 2048, partitions of 1024 taps, one workgroup per row and
+ * block of 1024 outputs: it stages the input segments it needs and transforms them in LDS, multiplies by the partition spectra
+ * and accumulates in registers across partitions, runs one inverse transform and stores; no spectrum of x goes through
+ * memory.  Two partitions share one complex transform (the spectrum stored for a pair is that of h_even - i h_odd).  The error is normwise: |error| <= c 2^-24 |h|_2
+ * |x|_2 per row (tests/perturb_reference.py has c).  d_ir_len passed here must be the array the spectra were prepared from.
+ * d_out must not alias d_in.  NULL pointers, batch <= 0, R <= 0, ld_in < 0, ld_ir < 1, ld_out < 1, ld_out < ld_in + ld_ir
+ * - 1, a misaligned or too small spectra buffer return VASR_ERR_INVALID; ld_ir > 32768 or R > 65535 return
+ * VASR_ERR_UNSUPPORTED with the limit in vasr_last_error(); an argument error wins over the limit. */
+VASR_API size_t vasr_convolve_spectra_bytes(int R, int64_t ld_ir);
+VASR_API int vasr_convolve_prepare_f32(const float* d_ir, int64_t ld_ir, const int64_t* d_ir_len, int R, void* d_spectra,
+                                       size_t spectra_bytes, vasr_stream stream);
+VASR_API int vasr_convolve_f32(const float* d_in, int64_t ld_in, const int64_t* d_len, int batch, const int32_t* d_ir_row,
+                               const int64_t* d_ir_len, const void* d_spectra, int R, int64_t ld_ir, float* d_out,
+                               int64_t ld_out, int64_t* d_len_out, vasr_stream stream);
+
 /* The fused call can cut the batch into `slices` contiguous parts (1..4; default 1 = off, because on MI355X it
  * measured slower: 11.7 -> 13.5 ms at 2 slices) and run each on its own
  * internal HIP stream, forked from / joined to `stream` with events: one part's HBM-bound kernels (depthwise,

@@ -82,6 +82,13 @@ SIGNATURES = {
                                            _P, _P, C.c_size_t, _P]),
     "vasr_gather_segments_f32": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P]),
     "vasr_gather_segments_pcm16": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P]),
+    "vasr_mean_square_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
+    "vasr_mean_square_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P, C.c_size_t, _P]),
+    "vasr_noise_plan_f64": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_double, C.c_int, _P, _P, _P]),
+    "vasr_mix_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P, _P, C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "vasr_convolve_spectra_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
+    "vasr_convolve_prepare_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
+    "vasr_convolve_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int64, _P, C.c_int64, _P, _P]),
     "vasr_set_gemm_mode": (C.c_int, [_P, C.c_int]),
     "vasr_get_gemm_mode": (C.c_int, [_P]),
     "vasr_set_slices": (C.c_int, [_P, C.c_int]),

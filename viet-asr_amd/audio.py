@@ -233,6 +233,120 @@ def plan_segments(bounds, count, lengths, pad=0, min_samples=0):
     return segments, dropped
 
 
+def _f32_batch(signal, length, what):
+    if signal.device.type != "cuda":
+        raise _lib.VasrError("viet-asr_amd kernels need HIP-resident tensors; there is no CPU fallback for this path")
+    if signal.dtype != torch.float32 or signal.dim() != 2:
+        raise ValueError(f"{what} expects a [B, L] float32 cuda tensor (int16 PCM: pcm16_to_float first)")
+    x = signal.contiguous()
+    return x, length.to(device=x.device, dtype=torch.int64).contiguous()
+
+
+def _opt(t, device, dtype):
+    return None if t is None else torch.as_tensor(t).to(device=device, dtype=dtype).contiguous()
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def mean_square(signal, length, workspace=None):
+    """signal [B, L] float32 cuda (padding: anything), length [B] int64 -> mean(x^2) per row, [B] float64 on the device: the
+    argument of ``AudioSegment.rms_db`` (vasr_mean_square_f32: float64 sums in a fixed order; an empty row gives 0).  Two launches,
+    no synchronisation."""
+    x, ln = _f32_batch(signal, length, "mean_square")
+    B, L = x.shape
+    ms = torch.empty((B,), dtype=torch.float64, device=x.device)
+    need = int(_lib.lib().vasr_mean_square_workspace_bytes(B, L))
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.lib().vasr_mean_square_f32(x.data_ptr(), L, ln.data_ptr(), B, ms.data_ptr(), workspace.data_ptr(),
+                                               workspace.numel(), torch.cuda.current_stream(x.device).cuda_stream))
+    return ms
+
+
+def noise_plan(length, ms_x, rows, snr_db, u, noise_len, ms_v, max_gain_db, sample_rate):
+    """NoisePerturbation's gain and start per row on the device (vasr_noise_plan_f64): length [B] i64, ms_x [B] f64, rows [B]
+    i32 (-1: no noise), snr_db [B] f64, u [B] f64 in [0, 1), noise_len [R] i64, ms_v [R] f64 -> (scale [B] f32, start [B] i64)."""
+    dev = ms_x.device
+    ln, mx = _opt(length, dev, torch.int64), _opt(ms_x, dev, torch.float64)
+    r, s, uu = _opt(rows, dev, torch.int32), _opt(snr_db, dev, torch.float64), _opt(u, dev, torch.float64)
+    nl, mv = _opt(noise_len, dev, torch.int64), _opt(ms_v, dev, torch.float64)
+    B = int(ln.numel())
+    if any(int(t.numel()) != B for t in (mx, r, s, uu)) or int(nl.numel()) != int(mv.numel()):
+        raise ValueError("noise_plan: one entry per row (length, ms_x, rows, snr_db, u) and per noise (noise_len, ms_v)")
+    scale = torch.empty((B,), dtype=torch.float32, device=dev)
+    start = torch.empty((B,), dtype=torch.int64, device=dev)
+    _lib.check(_lib.lib().vasr_noise_plan_f64(ln.data_ptr(), mx.data_ptr(), r.data_ptr(), s.data_ptr(), uu.data_ptr(), B,
+                                              nl.data_ptr(), mv.data_ptr(), int(nl.numel()), float(max_gain_db), int(sample_rate),
+                                              scale.data_ptr(), start.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    return scale, start
+
+
+def mix(signal, length, gain=None, shift=None, add=None, add_len=None, add_row=None, scale=None, start=None, out=None):
+    """out[b][t] = gain[b] * x[b][t + shift[b]] + scale[b] * add[add_row[b]][(start[b] + t) mod add_len] for t < length[b], zeros
+    behind; the lengths do not change (vasr_mix_f32: GainPerturbation, ShiftPerturbation, NoisePerturbation's and
+    WhiteNoisePerturbation's sum in one pass).  gain [B] f32, shift [B] i64 (samples), add [R, La] f32 with add_len [R] i64,
+    add_row [B] i32, scale [B] f32, start [B] i64; gain, shift, add and start may be None (1, 0, nothing, 0).  out: a
+    contiguous float32 [B, >= L] tensor of the caller's."""
+    x, ln = _f32_batch(signal, length, "mix")
+    B, L = x.shape
+    dev = x.device
+    if out is None:
+        out = torch.empty((B, L), dtype=torch.float32, device=dev)
+    if out.dtype != torch.float32 or out.device != dev or out.dim() != 2 or out.shape[0] != B or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 [B, >= L] tensor on signal's device")
+    g, sh = _opt(gain, dev, torch.float32), _opt(shift, dev, torch.int64)
+    a = al = ar = sc = st = None
+    ld_add = rows = 0
+    if add is not None:
+        if add.dim() != 2 or add.dtype != torch.float32 or add.device != dev:
+            raise ValueError("add must be a [R, La] float32 tensor on signal's device")
+        a = add.contiguous()
+        rows, ld_add = a.shape
+        al, ar = _opt(add_len, dev, torch.int64), _opt(add_row, dev, torch.int32)
+        sc, st = _opt(scale, dev, torch.float32), _opt(start, dev, torch.int64)
+    _lib.check(_lib.lib().vasr_mix_f32(x.data_ptr(), L, ln.data_ptr(), B, _ptr(g), _ptr(sh), _ptr(a), ld_add, rows, _ptr(al),
+                                       _ptr(ar), _ptr(sc), _ptr(st), out.data_ptr(), out.shape[1],
+                                       torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
+class ImpulseBank:
+    """Impulse responses [R, Lh] float32 cuda with their lengths, and their partition spectra computed once
+    (vasr_convolve_prepare_f32)."""
+
+    def __init__(self, responses, lengths):
+        h, ln = _f32_batch(responses, lengths, "ImpulseBank")
+        self.responses, self.lengths = h, ln
+        self.R, self.ld = int(h.shape[0]), int(h.shape[1])
+        L = _lib.lib()
+        # the refusals (too many taps: NotImplementedError) come from the call itself
+        need = int(L.vasr_convolve_spectra_bytes(self.R, self.ld))
+        self.spectra = torch.empty(max(need, 8), dtype=torch.uint8, device=h.device)
+        _lib.check(L.vasr_convolve_prepare_f32(h.data_ptr(), self.ld, ln.data_ptr(), self.R, self.spectra.data_ptr(),
+                                               self.spectra.numel(), torch.cuda.current_stream(h.device).cuda_stream))
+
+
+def convolve(signal, length, bank, rows, out=None):
+    """signal [B, L] float32 cuda, length [B] i64, bank: an ImpulseBank, rows [B] i32 (-1: the row is copied) ->
+    (out [B, L + bank.ld - 1], length' [B] i64): ``scipy.signal.fftconvolve(x, h, "full")`` per row, length n + m - 1
+    (vasr_convolve_f32: partitioned overlap-save in one kernel).  One launch, no synchronisation."""
+    x, ln = _f32_batch(signal, length, "convolve")
+    B, L = x.shape
+    r = _opt(rows, x.device, torch.int32)
+    width = max(L + bank.ld - 1, 1)
+    if out is None:
+        out = torch.empty((B, width), dtype=torch.float32, device=x.device)
+    if out.dtype != torch.float32 or out.device != x.device or out.dim() != 2 or out.shape[0] != B or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 [B, >= L + bank.ld - 1] tensor on signal's device")
+    ln_out = torch.empty((B,), dtype=torch.int64, device=x.device)
+    _lib.check(_lib.lib().vasr_convolve_f32(x.data_ptr(), L, ln.data_ptr(), B, r.data_ptr(), bank.lengths.data_ptr(),
+                                            bank.spectra.data_ptr(), bank.R, bank.ld, out.data_ptr(), out.shape[1],
+                                            ln_out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream))
+    return out, ln_out
+
+
 def pcm16_to_float(pcm):
     """int16 cuda tensor -> float32 / 32768 on the device (halves the host->device bytes of a batch)."""
     if pcm.device.type != "cuda" or pcm.dtype != torch.int16:

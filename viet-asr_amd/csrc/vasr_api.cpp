@@ -2,6 +2,7 @@
 // workspace planning and the launch sequences for each stage of the path.
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -2190,6 +2191,109 @@ int vasr_gather_segments_f32(const float* d_in, int64_t ld_in, int batch, const 
 int vasr_gather_segments_pcm16(const int16_t* d_in, int64_t ld_in, int batch, const int32_t* d_row, const int64_t* d_start,
                                const int64_t* d_len, int64_t segments, int16_t* d_out, int64_t ld_out, vasr_stream stream) {
   return gather_segments<short>(d_in, ld_in, batch, d_row, d_start, d_len, segments, d_out, ld_out, stream);
+}
+
+size_t vasr_mean_square_workspace_bytes(int batch, int64_t ld_in) {
+  if (batch <= 0 || ld_in < 0) return 0;
+  return mean_square_workspace_bytes(batch, ld_in);
+}
+
+int vasr_mean_square_f32(const float* d_in, int64_t ld_in, const int64_t* d_len, int batch, double* d_ms, void* d_workspace,
+                         size_t workspace_bytes, vasr_stream stream) {
+  // every refusal comes before a device is touched
+  if (!d_in || !d_len || !d_ms) return fail(VASR_ERR_INVALID, "mean_square: NULL pointer");
+  if (batch <= 0 || ld_in < 0) return fail(VASR_ERR_INVALID, "mean_square: batch %d, ld_in %lld (batch >= 1, ld_in >= 0)", batch,
+                                           (long long)ld_in);
+  if (!d_workspace) return fail(VASR_ERR_INVALID, "mean_square: NULL workspace");
+  const size_t need = mean_square_workspace_bytes(batch, ld_in);
+  if (workspace_bytes < need)
+    return fail(VASR_ERR_INVALID, "mean_square: workspace of %zu bytes, %zu needed (vasr_mean_square_workspace_bytes)",
+                workspace_bytes, need);
+  launch_mean_square(d_in, ld_in, d_len, batch, d_ms, d_workspace, static_cast<hipStream_t>(stream));
+  return check_launch("mean_square");
+}
+
+int vasr_noise_plan_f64(const int64_t* d_len, const double* d_ms_x, const int32_t* d_row, const double* d_snr_db, const double* d_u,
+                        int batch, const int64_t* d_noise_len, const double* d_ms_v, int noise_rows, double max_gain_db,
+                        int sample_rate, float* d_scale, int64_t* d_start, vasr_stream stream) {
+  if (!d_len || !d_ms_x || !d_row || !d_snr_db || !d_u || !d_noise_len || !d_ms_v || !d_scale || !d_start)
+    return fail(VASR_ERR_INVALID, "noise_plan: NULL pointer");
+  if (batch <= 0 || noise_rows <= 0 || sample_rate <= 0)
+    return fail(VASR_ERR_INVALID, "noise_plan: batch %d, noise_rows %d, sample_rate %d (all >= 1)", batch, noise_rows, sample_rate);
+  if (std::isnan(max_gain_db)) return fail(VASR_ERR_INVALID, "noise_plan: max_gain_db is not a number");
+  double cap = std::pow(10.0, max_gain_db / 20.0);
+  cap = cap > (double)FLT_MAX ? (double)FLT_MAX : cap;
+  launch_noise_plan(d_len, d_ms_x, d_row, d_snr_db, d_u, batch, d_noise_len, d_ms_v, noise_rows, cap, sample_rate, d_scale, d_start,
+                    static_cast<hipStream_t>(stream));
+  return check_launch("noise_plan");
+}
+
+int vasr_mix_f32(const float* d_in, int64_t ld_in, const int64_t* d_len, int batch, const float* d_gain, const int64_t* d_shift,
+                 const float* d_add, int64_t ld_add, int add_rows, const int64_t* d_add_len, const int32_t* d_add_row,
+                 const float* d_scale, const int64_t* d_start, float* d_out, int64_t ld_out, vasr_stream stream) {
+  if (!d_in || !d_len || !d_out) return fail(VASR_ERR_INVALID, "mix: NULL pointer");
+  if (d_in == d_out) return fail(VASR_ERR_INVALID, "mix: d_out must not alias d_in");
+  if (batch <= 0 || ld_in < 0 || ld_out < ld_in)
+    return fail(VASR_ERR_INVALID, "mix: batch %d, ld_in %lld, ld_out %lld (ld_out >= ld_in >= 0)", batch, (long long)ld_in,
+                (long long)ld_out);
+  if (d_add && (!d_add_len || !d_add_row || !d_scale))
+    return fail(VASR_ERR_INVALID, "mix: an addend needs d_add_len, d_add_row and d_scale");
+  if (d_add && (ld_add < 0 || add_rows <= 0))
+    return fail(VASR_ERR_INVALID, "mix: ld_add %lld, add_rows %d (ld_add >= 0, add_rows >= 1)", (long long)ld_add, add_rows);
+  if (d_add == d_out) return fail(VASR_ERR_INVALID, "mix: d_out must not alias d_add");
+  launch_mix(d_in, ld_in, d_len, batch, d_gain, d_shift, d_add, ld_add, add_rows, d_add_len, d_add_row, d_scale, d_start, d_out,
+             ld_out, static_cast<hipStream_t>(stream));
+  return check_launch("mix");
+}
+
+static const char* convolve_bank_error(int R, int64_t ld_ir) {
+  if (R <= 0 || ld_ir < 1) return "R >= 1 and ld_ir >= 1";
+  return nullptr;
+}
+
+size_t vasr_convolve_spectra_bytes(int R, int64_t ld_ir) {
+  if (convolve_bank_error(R, ld_ir) || ld_ir > kConvMaxTaps || R > 65535) return 0;
+  return convolve_spectra_bytes(R, ld_ir);
+}
+
+int vasr_convolve_prepare_f32(const float* d_ir, int64_t ld_ir, const int64_t* d_ir_len, int R, void* d_spectra,
+                              size_t spectra_bytes, vasr_stream stream) {
+  if (!d_ir || !d_ir_len || !d_spectra) return fail(VASR_ERR_INVALID, "convolve_prepare: NULL pointer");
+  if (convolve_bank_error(R, ld_ir))
+    return fail(VASR_ERR_INVALID, "convolve_prepare: R %d, ld_ir %lld (%s)", R, (long long)ld_ir, convolve_bank_error(R, ld_ir));
+  if (reinterpret_cast<uintptr_t>(d_spectra) % 8) return fail(VASR_ERR_INVALID, "convolve_prepare: d_spectra must be 8-byte aligned");
+  if (ld_ir > kConvMaxTaps || R > 65535)
+    return fail(VASR_ERR_UNSUPPORTED, "convolve_prepare: ld_ir %lld, R %d: at most %lld taps and 65535 responses", (long long)ld_ir, R,
+                (long long)kConvMaxTaps);
+  const size_t need = convolve_spectra_bytes(R, ld_ir);
+  if (spectra_bytes < need)
+    return fail(VASR_ERR_INVALID, "convolve_prepare: spectra buffer of %zu bytes, %zu needed (vasr_convolve_spectra_bytes)",
+                spectra_bytes, need);
+  const int e = launch_convolve_prepare(d_ir, ld_ir, d_ir_len, R, d_spectra, static_cast<hipStream_t>(stream));
+  if (e) return fail(VASR_ERR_HIP, "convolve_prepare: twiddle table copy: %s", hipGetErrorString((hipError_t)e));
+  return check_launch("convolve_prepare");
+}
+
+int vasr_convolve_f32(const float* d_in, int64_t ld_in, const int64_t* d_len, int batch, const int32_t* d_ir_row,
+                      const int64_t* d_ir_len, const void* d_spectra, int R, int64_t ld_ir, float* d_out, int64_t ld_out,
+                      int64_t* d_len_out, vasr_stream stream) {
+  if (!d_in || !d_len || !d_ir_row || !d_ir_len || !d_spectra || !d_out || !d_len_out)
+    return fail(VASR_ERR_INVALID, "convolve: NULL pointer");
+  if (d_in == d_out) return fail(VASR_ERR_INVALID, "convolve: d_out must not alias d_in");
+  if (batch <= 0 || ld_in < 0) return fail(VASR_ERR_INVALID, "convolve: batch %d, ld_in %lld (batch >= 1, ld_in >= 0)", batch,
+                                           (long long)ld_in);
+  if (convolve_bank_error(R, ld_ir))
+    return fail(VASR_ERR_INVALID, "convolve: R %d, ld_ir %lld (%s)", R, (long long)ld_ir, convolve_bank_error(R, ld_ir));
+  if (ld_out < 1 || ld_out - ld_ir + 1 < ld_in)
+    return fail(VASR_ERR_INVALID, "convolve: ld_out %lld (>= 1 and >= ld_in + ld_ir - 1 = %lld)", (long long)ld_out,
+                (long long)(ld_in + ld_ir - 1));
+  if (reinterpret_cast<uintptr_t>(d_spectra) % 8) return fail(VASR_ERR_INVALID, "convolve: d_spectra must be 8-byte aligned");
+  if (ld_ir > kConvMaxTaps || R > 65535)
+    return fail(VASR_ERR_UNSUPPORTED, "convolve: ld_ir %lld, R %d: at most %lld taps and 65535 responses", (long long)ld_ir, R,
+                (long long)kConvMaxTaps);
+  launch_convolve(d_in, ld_in, d_len, batch, d_ir_row, d_ir_len, d_spectra, R, ld_ir, d_out, ld_out, d_len_out,
+                  static_cast<hipStream_t>(stream));
+  return check_launch("convolve");
 }
 
 int vasr_set_gemm_mode(vasr_handle* h, int mode) {

@@ -438,6 +438,29 @@ template <typename T>
 void launch_gather_segments(const T* in, int64_t ld_in, int batch, const int32_t* row, const int64_t* start, const int64_t* len,
                             int64_t segments, T* out, int64_t ld_out, hipStream_t st);
 
+// ---- audio perturbation (perturb.hip): gain / shift / noise mix and convolution with impulse responses; include/vasr.h has
+// the semantics.  The callers check every argument; none of these synchronises with the host. ----
+constexpr int kMsChunk = 4096;          // samples per partial sum of the mean square
+constexpr int kConvN = 2048;            // transform length of the overlap-save convolution
+constexpr int kConvTaps = 1024;         // taps per partition (Lp)
+constexpr int kConvOut = 1024;          // outputs per workgroup (L); L + Lp - 1 <= N
+constexpr int64_t kConvMaxTaps = 32768;
+size_t mean_square_workspace_bytes(int batch, int64_t ld_in);   // host only; SIZE_MAX where it does not fit
+void launch_mean_square(const float* in, int64_t ld_in, const int64_t* len, int batch, double* ms, void* workspace,
+                        hipStream_t st);
+// cap = 10^(max_gain_db / 20), at most FLT_MAX
+void launch_noise_plan(const int64_t* len, const double* ms_x, const int32_t* row, const double* snr_db, const double* u,
+                       int batch, const int64_t* noise_len, const double* ms_v, int noise_rows, double cap, int sample_rate,
+                       float* scale, int64_t* start, hipStream_t st);
+void launch_mix(const float* in, int64_t ld_in, const int64_t* len, int batch, const float* gain, const int64_t* shift,
+                const float* add, int64_t ld_add, int add_rows, const int64_t* add_len, const int32_t* add_row,
+                const float* scale, const int64_t* start, float* out, int64_t ld_out, hipStream_t st);
+size_t convolve_spectra_bytes(int R, int64_t ld_ir);             // host only
+// also copies the host-built twiddle table to the head of `spectra`; returns 0 or a hipError_t
+int launch_convolve_prepare(const float* ir, int64_t ld_ir, const int64_t* ir_len, int R, void* spectra, hipStream_t st);
+void launch_convolve(const float* in, int64_t ld_in, const int64_t* len, int batch, const int32_t* ir_row, const int64_t* ir_len,
+                     const void* spectra, int R, int64_t ld_ir, float* out, int64_t ld_out, int64_t* len_out, hipStream_t st);
+
 // ---- beam search (beam_wave.hip, beam_group.hip) ----
 struct BeamLm {  // device-resident hashed back-off n-gram model
   const void* vocab; int vcap;    // [vcap] 16-byte entries {u64 word hash | 1, i32 word id, u32 flags}, vcap a power of two

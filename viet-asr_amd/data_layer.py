@@ -130,7 +130,8 @@ class AudioToSpeechLabelDataLayer(_ManifestBatches, DataLayerNM):
     Batches: signals zero padded to the batch maximum (seq_collate_fn), ``label`` [B] int64, ``label_length`` [B] int64, all
     ones.  PCM WAV only; ``trim_silence`` and ``augmentor`` are not implemented HERE: the layer hands out host tensors, and the
     trim (librosa.effects.trim) runs on the device, in the engine call that consumes them
-    (``engine.QuartzNetClassifier.evaluate_manifest(..., trim_silence=True)``, ``audio.trim_silence``).  Sharding, length buckets and
+    (``engine.QuartzNetClassifier.evaluate_manifest(..., trim_silence=True)``, ``audio.trim_silence``), as the perturbations do
+    (``perturb.AudioAugmentor``, the ``augmentor`` argument of ``engine.QuartzNetCTC`` and ``VietASR``'s batch calls).  Sharding, length buckets and
     ``utterance_order`` as in ``AudioToTextDataLayer``, whose defaults (no shuffle) it shares."""
 
     @property
@@ -147,7 +148,8 @@ class AudioToSpeechLabelDataLayer(_ManifestBatches, DataLayerNM):
         if trim_silence:
             raise NotImplementedError("trim_silence=True (librosa.effects.trim) is not implemented")
         if augmentor is not None:
-            raise NotImplementedError("audio augmentors are not implemented")
+            raise NotImplementedError("audio augmentors are not applied in the data layer: pass the perturb.AudioAugmentor to the "
+                                      "engine call that consumes the batches (augmentor=...)")
         if not load_audio:
             raise NotImplementedError("load_audio=False is not implemented")
         self._sample_rate, self._batch_size, self._shuffle = sample_rate, batch_size, shuffle

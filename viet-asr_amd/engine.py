@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .audio import trim_silence as trim_audio
+from .audio import pcm16_to_float, trim_silence as trim_audio
 from .frontend_tables import frontend_description
 
 
@@ -225,7 +225,7 @@ class QuartzNetCTC:
         return t.to(torch.int32)
 
     def forward(self, wav, length, want_logp=False, want_pred=True, row_independent=False, trim_silence=False,
-                _trim_buffers=None):
+                _trim_buffers=None, augmentor=None, _lengths_host=None):
         """wav [B, L] f32 cuda (rows zero padded) -- or int16 PCM as it sits in a wav file: the front end scales it by 2^-15 as
         it reads it (vasr_transcribe_greedy_pcm16; the same bits as converting first) --, length [B] i64 cuda.
 
@@ -243,6 +243,12 @@ class QuartzNetCTC:
         bound.  The dict then also carries "trim_start" [B] i64 (the first kept sample of each row) and "length" [B] i64 (the
         trimmed lengths); ``frames_of(length)`` are the rows' own encoded frames.  With librosa's defaults a trimmed row keeps
         at least 512 samples of a longer one, so the n_fft / 2 rule checked on the untrimmed lengths still holds.
+
+        augmentor: a ``perturb.AudioAugmentor`` (None: nothing changes).  The batch is perturbed on the device after the trim and in
+        front of the front end, the reference's order in ``WaveformFeaturizer.process``; int16 PCM is scaled to float32 first.
+        The parameters are drawn on the host from the rows' lengths (with trim_silence they are read back from the device: one
+        synchronisation).  An impulse response makes the batch wider: every frame count then follows the new width, and the dict
+        carries "length" [B] i64, the perturbed lengths.
         """
         if wav.device.type != "cuda" or wav.dtype not in (torch.float32, torch.int16) or not wav.is_contiguous():
             raise ValueError("wav must be a contiguous float32 (or int16 PCM) cuda tensor")
@@ -252,6 +258,11 @@ class QuartzNetCTC:
         if trim_silence:
             out, start = _trim_buffers if _trim_buffers is not None else (None, None)
             wav, length, trim_start = trim_audio(wav, length, out=out, start=start)
+        if augmentor is not None:
+            if wav.dtype == torch.int16:
+                wav = pcm16_to_float(wav)
+            wav, length = augmentor.perturb_batch(wav, length, self.frontend["sample_rate"],
+                                                  lengths_host=None if trim_silence else _lengths_host)
         B, L = wav.shape
         _, t1 = self.frames(L)
         ws = self._workspace(B, L)
@@ -273,6 +284,8 @@ class QuartzNetCTC:
         r = dict(ids=ids, id_len=id_len, pred=pred, enc_len=enc_len, logp=logp)
         if trim_start is not None:
             r["trim_start"], r["length"] = trim_start, length
+        if augmentor is not None:
+            r["length"] = length
         return r
 
     def texts(self, ids, id_len):
@@ -283,16 +296,17 @@ class QuartzNetCTC:
             raise _lib.VasrError("beam search reported an internal overflow (id_len = -1) for rows %s" % (n < 0).nonzero()[0].tolist())
         return ["".join(self.labels[c] for c in ids[b, : n[b]]) for b in range(ids.shape[0])]
 
-    def transcribe(self, signals, row_independent=False, trim_silence=False):
+    def transcribe(self, signals, row_independent=False, trim_silence=False, augmentor=None):
         """List of 1-D arrays (model sample rate; float, or int16 PCM) -> list of strings; zero-pad-to-max collate
-        (parts/dataset.py:14-53).  row_independent, trim_silence: see forward()."""
-        return self.launch(signals, row_independent, trim_silence=trim_silence).texts()
+        (parts/dataset.py:14-53).  row_independent, trim_silence, augmentor: see forward()."""
+        return self.launch(signals, row_independent, trim_silence=trim_silence, augmentor=augmentor).texts()
 
-    def transcribe_beam(self, signals, beam_decoder, beam_width, row_independent=True, trim_silence=False):
+    def transcribe_beam(self, signals, beam_decoder, beam_width, row_independent=True, trim_silence=False, augmentor=None):
         """Batched counterpart of the reference's beam wiring (infer.py:132-139, 159-160; batch 1 there): one forward
         pass for the log-probs, then viet_asr_amd.beam.BeamSearchDecoder over every row.  row_independent=True searches
         each row over its own frames (and reflects it at its own end): the transcripts of batch-1 calls.  trim_silence: see
-        forward(); the rows' own frames then come from the trimmed lengths, on the device."""
+        forward(); the rows' own frames then come from the trimmed lengths, on the device.  augmentor: see forward(); the
+        rows' own frames come from the perturbed lengths."""
         lens = [len(s) for s in signals]
         if row_independent and min(lens) <= self.frontend["n_fft"] // 2:
             raise ValueError(f"row-independent batching needs more than n_fft/2 = {self.frontend['n_fft'] // 2} samples "
@@ -301,9 +315,10 @@ class QuartzNetCTC:
         for i, s in enumerate(signals):
             batch[i, : lens[i]] = _pcm_to_float(s)
         r = self.forward(torch.from_numpy(batch).to(self.device), torch.tensor(lens, device=self.device),
-                         want_logp=True, want_pred=False, row_independent=row_independent, trim_silence=trim_silence)
+                         want_logp=True, want_pred=False, row_independent=row_independent, trim_silence=trim_silence,
+                         augmentor=augmentor, _lengths_host=lens)
         own = [self.frames(n)[1] for n in lens] if row_independent else None
-        if row_independent and trim_silence:
+        if row_independent and (trim_silence or augmentor is not None):
             own = self.frames_of(r["length"])
         return beam_decoder.decode_batch(r["logp"], beam_width, frames=own)
 
@@ -433,7 +448,7 @@ class QuartzNetCTC:
         return lf
 
     # -- pipelined host path: pinned staging, copies on their own stream, two batches in flight
-    def launch(self, signals, row_independent=False, after_forward=None, trim_silence=False):
+    def launch(self, signals, row_independent=False, after_forward=None, trim_silence=False, augmentor=None):
         """Enqueue one batch and return at once; ``.texts()`` of the returned PendingBatch waits for it.
 
         Two staging slots alternate: while batch k computes, batch k+1 is collated into pinned memory and its
@@ -446,6 +461,7 @@ class QuartzNetCTC:
         hook in here; it must not synchronise.
 
         trim_silence: see forward(); the slot keeps a second device buffer for the trimmed batch and one for the starts.
+        augmentor: see forward(); the staging for the ids is sized by ``augmentor.max_augmentation_length``.
         """
         if len(signals) == 0:
             raise ValueError("empty batch")
@@ -454,7 +470,7 @@ class QuartzNetCTC:
             self._copy_stream = torch.cuda.Stream(self.device)
         slot = self._slots[self._launched % 2]
         self._launched += 1
-        return slot.launch(signals, row_independent, after_forward, trim_silence)
+        return slot.launch(signals, row_independent, after_forward, trim_silence, augmentor)
 
 
 class QuartzNetClassifier:
@@ -694,7 +710,7 @@ class _Slot:
         if self.pin_ids is None or self.pin_ids.numel() < B * t1:
             self.pin_ids = torch.empty(B * t1, dtype=torch.int32, pin_memory=True)
 
-    def launch(self, signals, row_independent=False, after_forward=None, trim_silence=False):
+    def launch(self, signals, row_independent=False, after_forward=None, trim_silence=False, augmentor=None):
         eng = self.eng
         if self.pending is not None:
             self.pending.texts()          # the slot's previous batch: fetch before its buffers are overwritten
@@ -710,6 +726,8 @@ class _Slot:
         dtype, item = (torch.int16, 2) if pcm16 else (torch.float32, 4)
         nbytes = B * L * item
         _, t1 = eng.frames(L)
+        if augmentor is not None:         # the widest the batch can become: the staging for the ids holds that many frames
+            t1 = eng.frames(int(augmentor.max_augmentation_length(L, eng.frontend["sample_rate"])))[1]
         with torch.cuda.device(eng.device):
             self.ev_out.synchronize()     # batch k-2 has left the device buffers
             self._reserve(B, nbytes, t1, pcm16)
@@ -736,7 +754,9 @@ class _Slot:
             wav = self.dev[:nbytes].view(dtype).view(B, L)
             # (int16 PCM goes into the front end as it is: scaled by 2^-15 in the STFT kernel's staging load)
             self.out = eng.forward(wav, self.dev_len[:B], want_pred=False, row_independent=row_independent,
-                                   trim_silence=trim_silence, _trim_buffers=trim_buffers)
+                                   trim_silence=trim_silence, _trim_buffers=trim_buffers, augmentor=augmentor,
+                                   _lengths_host=lens)
+            t1 = self.out["ids"].shape[1]  # the width the batch got (an impulse response widens it)
             if after_forward is not None:
                 after_forward(self.out)
             self.pin_ids[: B * t1].copy_(self.out["ids"].view(-1), non_blocking=True)

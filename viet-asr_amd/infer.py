@@ -135,7 +135,8 @@ class VietASR:
     def _trim(self, trim_silence):
         return resolve_trim_silence(trim_silence, self.model_definition)
 
-    def transcribe_batch(self, signals, sample_rate=None, row_independent=False, decoder="greedy", trim_silence=False):
+    def transcribe_batch(self, signals, sample_rate=None, row_independent=False, decoder="greedy", trim_silence=False,
+                         augmentor=None):
         """Transcripts of a list of 1-D signals through the fused one-call path.  row_independent=True: every
         transcript is what the signal alone would give (engine.QuartzNetCTC.forward); default: the reference's
         padded-batch semantics.  decoder="beam" (instances built with decoder="beam" only) runs this instance's beam
@@ -143,15 +144,19 @@ class VietASR:
 
         trim_silence: False | True | "config" ("config": what the model definition's ``AudioToTextDataLayer.trim_silence`` says;
         ``resolve_trim_silence``).  True cuts every signal's leading and trailing silence on the device, after any resampling
-        and in front of the front end, as ``AudioSegment(trim=True)`` does (segment.py:24-28; ``audio.trim_silence``)."""
+        and in front of the front end, as ``AudioSegment(trim=True)`` does (segment.py:24-28; ``audio.trim_silence``).
+
+        augmentor: a ``perturb.AudioAugmentor`` (None: nothing changes), applied on the device after the trim and in front of
+        the front end (``engine.QuartzNetCTC.forward``)."""
         trim = self._trim(trim_silence)
         if decoder == "greedy":
-            return self._fused_engine().transcribe(self._batch_signals(signals, sample_rate), row_independent, trim_silence=trim)
+            return self._fused_engine().transcribe(self._batch_signals(signals, sample_rate), row_independent, trim_silence=trim,
+                                                   augmentor=augmentor)
         if decoder != "beam" or self.mode != "beam":
             raise ValueError("decoder must be 'greedy', or 'beam' on an instance constructed with decoder='beam'")
         sigs = [self._to_model_rate(s, sample_rate) for s in signals]
         return self._fused_engine().transcribe_beam(sigs, self.beam.decoder, self.beam.beam_width, row_independent,
-                                                    trim_silence=trim)
+                                                    trim_silence=trim, augmentor=augmentor)
 
     def _manifest_batches(self, manifest_filepath, batch_size):
         """-> (the entries of a NeMo JSON-lines manifest, or of several separated by commas; a generator of (idx, signals): the
@@ -174,7 +179,8 @@ class VietASR:
                 yield idx, sigs
         return entries, batches()
 
-    def _walk_manifest(self, manifest_filepath, batch_size, row_independent, after_forward=None, trim_silence=False):
+    def _walk_manifest(self, manifest_filepath, batch_size, row_independent, after_forward=None, trim_silence=False,
+                       augmentor=None):
         """The entries of a NeMo JSON-lines manifest and their greedy transcripts, in manifest order: sorted by duration, cut
         into batches of ``batch_size``, two batches in flight (engine.QuartzNetCTC.launch).  after_forward(entries, idx) -> the
         ``launch`` hook of the batch holding entries ``idx`` (or None)."""
@@ -188,14 +194,15 @@ class VietASR:
 
         for idx, sigs in batches:
             hook = after_forward(entries, idx) if after_forward is not None else None
-            pending.append((idx, self._fused_engine().launch(sigs, row_independent, hook, trim_silence=trim_silence)))
+            pending.append((idx, self._fused_engine().launch(sigs, row_independent, hook, trim_silence=trim_silence,
+                                                             augmentor=augmentor)))
             if len(pending) == 2:
                 collect(pending.pop(0))
         for job in pending:
             collect(job)
         return entries, hyps
 
-    def transcribe_manifest(self, manifest_filepath, batch_size=64, row_independent=True, trim_silence=False):
+    def transcribe_manifest(self, manifest_filepath, batch_size=64, row_independent=True, trim_silence=False, augmentor=None):
         """Greedy transcripts of every entry of a NeMo JSON-lines manifest (parts/manifest.py:21-94), in manifest order,
         plus the word error rate against the entries' ``text`` (None when no entry has one).
 
@@ -206,9 +213,11 @@ class VietASR:
 
         The rate is ``data_layer.word_error_rate`` on the RAW manifest text, computed on the host after the last batch.
         ``evaluate_manifest`` scores the parsed tokens on the device instead (WER and CER); the two word error rates
-        differ only where a reference contains characters outside the labels.  trim_silence: as ``transcribe_batch``."""
+        differ only where a reference contains characters outside the labels.  trim_silence, augmentor: as
+        ``transcribe_batch``; the rows draw their perturbations in batch order (sorted by duration)."""
         from .data_layer import word_error_rate
-        entries, hyps = self._walk_manifest(manifest_filepath, batch_size, row_independent, trim_silence=self._trim(trim_silence))
+        entries, hyps = self._walk_manifest(manifest_filepath, batch_size, row_independent, trim_silence=self._trim(trim_silence),
+                                            augmentor=augmentor)
         refs = [e.get("text") for e in entries]
         scored = [i for i, r in enumerate(refs) if r]
         wer = word_error_rate([hyps[i] for i in scored], [refs[i] for i in scored]) if scored else None
@@ -227,7 +236,7 @@ class VietASR:
         return ref, ref_len
 
     def evaluate_manifest(self, manifest_filepath, batch_size=64, row_independent=True, breakdown=False, nbest=None,
-                          eval_loss=False, trim_silence=False):
+                          eval_loss=False, trim_silence=False, augmentor=None):
         """``transcribe_manifest``'s walk with WER and CER scored on the device: -> (hyps, ``ErrorRate.compute()``), the
         dict {"wer", "cer", "word_edits", "ref_words", "char_edits", "ref_chars"}.
 
@@ -258,16 +267,17 @@ class VietASR:
         ``forward(want_logp=True)``; it cannot be combined with ``nbest`` (ValueError).
 
         trim_silence: as ``transcribe_batch``, in every form; "config" scores what the reference's evaluation with this model
-        definition would have scored (quartznet15x5.yaml trims every clip)."""
+        definition would have scored (quartznet15x5.yaml trims every clip).  augmentor: as ``transcribe_manifest``, in every form."""
         from .metrics import ErrorBreakdown, ErrorRate
         metric = (ErrorBreakdown if breakdown else ErrorRate)(self.labels)
         trim = self._trim(trim_silence)
         if eval_loss:
             if nbest is not None:
                 raise ValueError("eval_loss=True cannot be combined with nbest")
-            return self._evaluate_manifest_loss(manifest_filepath, batch_size, row_independent, metric, trim)
+            return self._evaluate_manifest_loss(manifest_filepath, batch_size, row_independent, metric, trim, augmentor)
         if nbest is not None:
-            return self._evaluate_manifest_nbest(manifest_filepath, batch_size, row_independent, metric, int(nbest), trim)
+            return self._evaluate_manifest_nbest(manifest_filepath, batch_size, row_independent, metric, int(nbest), trim,
+                                                 augmentor)
         keep = []                   # pinned reference batches, alive until the copies that read them have run
 
         def after_forward(entries, idx):
@@ -287,10 +297,12 @@ class VietASR:
                 metric.update(ids, id_len, ref.to(dev, non_blocking=True), ref_len.to(dev, non_blocking=True))
             return score
 
-        _, hyps = self._walk_manifest(manifest_filepath, batch_size, row_independent, after_forward, trim_silence=trim)
+        _, hyps = self._walk_manifest(manifest_filepath, batch_size, row_independent, after_forward, trim_silence=trim,
+                                      augmentor=augmentor)
         return hyps, metric.compute()
 
-    def _evaluate_manifest_nbest(self, manifest_filepath, batch_size, row_independent, metric, nbest, trim_silence=False):
+    def _evaluate_manifest_nbest(self, manifest_filepath, batch_size, row_independent, metric, nbest, trim_silence=False,
+                                 augmentor=None):
         from .engine import _pcm_to_float
         from .metrics import OracleErrorRate
         if self.mode != "beam":
@@ -307,9 +319,10 @@ class VietASR:
             for k, s in enumerate(sigs):
                 batch[k, : lens[k]] = _pcm_to_float(s)
             r = eng.forward(torch.from_numpy(batch).to(eng.device), torch.tensor(lens, device=eng.device), want_logp=True,
-                            want_pred=False, row_independent=row_independent, trim_silence=trim_silence)
+                            want_pred=False, row_independent=row_independent, trim_silence=trim_silence, augmentor=augmentor,
+                            _lengths_host=lens)
             own = [eng.frames(n)[1] for n in lens] if row_independent else None
-            if row_independent and trim_silence:
+            if row_independent and (trim_silence or augmentor is not None):
                 own = eng.frames_of(r["length"])
             ids, id_len, count, _, _ = dec.decode_beams_ids(r["logp"], self.beam.beam_width, nbest, frames=own)
             rows = [k for k, i in enumerate(idx) if entries[i].get("text")]
@@ -326,11 +339,11 @@ class VietASR:
         res["oracle_wer"], res["oracle_cer"] = best["oracle_wer"], best["oracle_cer"]
         return hyps, res
 
-    def _forward_logp(self, sigs, row_independent, trim_silence=False):
+    def _forward_logp(self, sigs, row_independent, trim_silence=False, augmentor=None):
         """One zero-padded batch of signals at the model's rate through ``forward(want_logp=True)`` -> (its result dict, the
         frames of every row [B] on the device: the row's own encoded frames when row_independent, otherwise the encoder's
         lengths of the padded batch).  trim_silence: the rows are trimmed on the device first (the dict then has "trim_start"
-        and "length") and a row's own frames follow its trimmed length, computed there."""
+        and "length") and a row's own frames follow its trimmed length, computed there.  augmentor: likewise, behind the trim."""
         from .engine import _pcm_to_float
         eng = self._fused_engine()
         lens = [len(s) for s in sigs]
@@ -341,8 +354,8 @@ class VietASR:
         for k, s in enumerate(sigs):
             batch[k, : lens[k]] = _pcm_to_float(s)
         r = eng.forward(torch.from_numpy(batch).to(eng.device), torch.tensor(lens, device=eng.device), want_logp=True,
-                        row_independent=row_independent, trim_silence=trim_silence)
-        if row_independent and trim_silence:
+                        row_independent=row_independent, trim_silence=trim_silence, augmentor=augmentor, _lengths_host=lens)
+        if row_independent and (trim_silence or augmentor is not None):
             frames = eng.frames_of(r["length"])
         elif row_independent:
             frames = torch.tensor([eng.frames(n)[1] for n in lens], dtype=torch.int32).to(eng.device)
@@ -350,13 +363,14 @@ class VietASR:
             frames = r["enc_len"]
         return r, frames
 
-    def _evaluate_manifest_loss(self, manifest_filepath, batch_size, row_independent, metric, trim_silence=False):
+    def _evaluate_manifest_loss(self, manifest_filepath, batch_size, row_independent, metric, trim_silence=False,
+                                augmentor=None):
         from .metrics import CTCEvalLoss
         eng, loss = self._fused_engine(), CTCEvalLoss(len(self.labels))
         entries, batches = self._manifest_batches(manifest_filepath, batch_size)
         hyps = [None] * len(entries)
         for idx, sigs in batches:
-            r, frames = self._forward_logp(sigs, row_independent, trim_silence)
+            r, frames = self._forward_logp(sigs, row_independent, trim_silence, augmentor)
             rows = [k for k, i in enumerate(idx) if entries[i].get("text")]
             if rows:
                 ref, ref_len = self._reference_tokens(entries, [idx[k] for k in rows])
@@ -373,20 +387,20 @@ class VietASR:
         res.update(loss.compute())
         return hyps, res
 
-    def score(self, signals, texts, sample_rate=None, row_independent=True, trim_silence=False):
+    def score(self, signals, texts, sample_rate=None, row_independent=True, trim_silence=False, augmentor=None):
         """log P(text | audio) of every (signal, text) pair -> a list of Python floats, minus the CTC loss of the row
         (``stages.ctc_loss`` on the batch's log-probs, over each row's own encoded frames): the forced score of ANY
         transcript -- a reference, or a greedy or beam hypothesis as a sequence confidence or for rescoring.  The texts go
         through the character parser the references go through (characters outside the labels are dropped).  A text that
         has no path through its audio (more tokens, counting one more per repeated character, than frames) scores -inf.
         row_independent (default): every score is what the signal alone would give.  One synchronisation.  trim_silence: as
-        ``transcribe_batch``."""
+        ``transcribe_batch``.  augmentor: as ``transcribe_batch``."""
         signals, texts = list(signals), list(texts)
         if len(signals) != len(texts) or not signals:
             raise ValueError(f"score needs as many texts as signals, and at least one (got {len(signals)} and {len(texts)})")
         eng = self._fused_engine()
         r, frames = self._forward_logp([self._to_model_rate(s, sample_rate) for s in signals], row_independent,
-                                       self._trim(trim_silence))
+                                       self._trim(trim_silence), augmentor)
         ref, ref_len = self._reference_tokens([{"text": t} for t in texts], range(len(texts)))
         from . import stages
         loss = stages.ctc_loss(r["logp"], frames, ref.to(eng.device), ref_len.to(eng.device), len(self.labels))
@@ -395,7 +409,7 @@ class VietASR:
             raise RuntimeError("the CTC score came back NaN for rows %s" % [k for k, v in enumerate(host) if v != v])
         return [-v for v in host]
 
-    def align(self, signals, texts=None, sample_rate=None, row_independent=True, trim_silence=False):
+    def align(self, signals, texts=None, sample_rate=None, row_independent=True, trim_silence=False, augmentor=None):
         """Character and word time spans of every (signal, text) pair: the forced (Viterbi) alignment of the text to the
         batch's log-probs (``stages.ctc_align``, over each row's own encoded frames) -> per row a dict {"text", "score",
         "chars", "words"} (``alignment_entries``): "score" is the log-probability of the best single path, at most
@@ -407,7 +421,8 @@ class VietASR:
         the signal alone would give.  One synchronisation.
 
         trim_silence: as ``transcribe_batch``.  The spans stay in the time of the recording that was given: every "start"
-        and "end" has the row's ``trim_start / sample_rate`` added, and the row reports it as "offset" (seconds)."""
+        and "end" has the row's ``trim_start / sample_rate`` added, and the row reports it as "offset" (seconds).  augmentor: as
+        ``transcribe_batch``; the spans are those of the perturbed audio (a shift or an impulse response is not undone)."""
         from . import stages
         signals = list(signals)
         if texts is not None:
@@ -417,7 +432,7 @@ class VietASR:
                              f"{None if texts is None else len(texts)})")
         eng = self._fused_engine()
         trim = self._trim(trim_silence)
-        r, frames = self._forward_logp([self._to_model_rate(s, sample_rate) for s in signals], row_independent, trim)
+        r, frames = self._forward_logp([self._to_model_rate(s, sample_rate) for s in signals], row_independent, trim, augmentor)
         if texts is None:
             tgt, tgt_len = r["ids"], r["id_len"]
         else:
