@@ -244,9 +244,16 @@ def squeeze_excite(x, lens, sd, prefix, se_mean="rows"):
     return x * s[:, :, None]
 
 
-def jasper_block_forward(x, lens, sd, i, lcfg, panes=None, se_mean="rows"):
+def activation_fn(name):
+    """jasper_activations (parts/jasper.py:21-25): nn.ReLU, nn.Hardtanh() = clamp to [-1, 1], nn.SELU (torch's constants)."""
+    return {"relu": F.relu, "hardtanh": F.hardtanh, "selu": F.selu}[name]
+
+
+def jasper_block_forward(x, lens, sd, i, lcfg, panes=None, se_mean="rows", activation="relu", residual_mode="add"):
     """JasperBlock.forward (parts/jasper.py:408-448) for the layouts the shipped configs and the Jasper-DR layouts use:
-    residual_mode='add', groups=1, heads=-1, activation ReLU, dropout = identity (eval).
+    groups=1, heads=-1, dropout = identity (eval).  activation: "relu" | "hardtanh" | "selu", one module for every block
+    (jasper.py:150); residual_mode "add" | "max": each residual pane is added to the branch output or combined with it by
+    torch.max (parts/jasper.py:438-441), before the block's output activation.
 
     SE (lcfg["se"], parts/jasper.py:223-253): without residual, after every sub-layer -- after its activation, except the
     last one's, which comes after its BN and before the block's output activation; with residual, on every residual pane
@@ -267,6 +274,9 @@ def jasper_block_forward(x, lens, sd, i, lcfg, panes=None, se_mean="rows"):
     pad = get_same_padding(k, stride, dil)
     rep, sep = lcfg["repeat"], lcfg.get("separable", False)
     se = bool(lcfg.get("se", False))
+    if residual_mode not in ("add", "max"):
+        raise ValueError("residual_mode: 'add' or 'max'")
+    act = activation_fn(activation)
     lens_orig = lens
     out, j = x, 0
     for r in range(rep):
@@ -282,7 +292,7 @@ def jasper_block_forward(x, lens, sd, i, lcfg, panes=None, se_mean="rows"):
             out = _bn_eval(out, sd, f"{p}.{j + 1}")
             j += 2
         if r != rep - 1:
-            out = F.relu(out)
+            out = act(out)
             j += 2
         if se and not lcfg["residual"]:
             out = squeeze_excite(out, lens, sd, f"{p}.{j}", se_mean)
@@ -295,11 +305,11 @@ def jasper_block_forward(x, lens, sd, i, lcfg, panes=None, se_mean="rows"):
             res = _bn_eval(res, sd, f"{p}.1")
             if se:
                 res = squeeze_excite(res, lens_orig, sd, f"{p}.2", se_mean)
-            out = out + res                                                    # :438-439
-    return F.relu(out), lens                                                   # :444 mout
+            out = out + res if residual_mode == "add" else torch.max(out, res)    # :438-441
+    return act(out), lens                                                      # :444 mout
 
 
-def encoder_forward(mel, length, sd, jasper_cfg, dtype=torch.float32, se_mean="rows"):
+def encoder_forward(mel, length, sd, jasper_cfg, dtype=torch.float32, se_mean="rows", activation="relu", residual_mode="add"):
     """JasperEncoder.forward (jasper.py:198-204): Sequential of JasperBlocks passing a LIST of tensors.
     A block with residual_dense and a residual appends its output to the list it received (parts/jasper.py:446-447: the
     list grows by one pane per dense block); every other block passes on a list of its output alone.  The encoder returns
@@ -308,13 +318,15 @@ def encoder_forward(mel, length, sd, jasper_cfg, dtype=torch.float32, se_mean="r
     dtype=torch.float64 runs the SAME graph in double precision: not the reference's arithmetic (that is float32, the
     default) but the reference's function without its rounding -- the tests use it to tell a frame on which two float32
     computations may legitimately disagree (a top-2 tie inside float32 rounding) from a wrong answer.
-    se_mean: the time mean of squeeze-and-excitation blocks, see squeeze_excite."""
+    se_mean: the time mean of squeeze-and-excitation blocks, see squeeze_excite.  activation, residual_mode: the encoder's
+    (jasper.py:142-150), handed to every block."""
     x = torch.as_tensor(mel).to(dtype)
     lens = torch.as_tensor(length)
     xs = [x]
     with torch.no_grad():
         for i, l in enumerate(jasper_cfg):
-            out, lens = jasper_block_forward(xs[-1], lens, sd, i, l, panes=xs, se_mean=se_mean)
+            out, lens = jasper_block_forward(xs[-1], lens, sd, i, l, panes=xs, se_mean=se_mean, activation=activation,
+                                             residual_mode=residual_mode)
             xs = xs + [out] if (l["residual"] and l.get("residual_dense", False)) else [out]
     return xs[-1], lens
 

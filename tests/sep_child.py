@@ -1,6 +1,7 @@
-"""Child process of tests/test_gpu_sep.py, one per environment setting (the VASR_* switches are read once per process, by
-the devtools build VASR_LIB_PATH names): the cases of tests/sep_reference.py named on the command line, in f16x2 and bf16x3
--> their outputs and launch counts in the .npz given first."""
+"""Child process of tests/test_gpu_sep.py and tests/test_gpu_act_f64.py, one per environment setting (the VASR_* switches are
+read once per process, by the devtools build VASR_LIB_PATH names): the cases of tests/sep_reference.py named on the command
+line (each with its own activation and residual mode), in f16x2 and bf16x3 -> their outputs and launch counts in the .npz
+given first."""
 import os
 import sys
 

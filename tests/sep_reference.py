@@ -1,4 +1,4 @@
-"""What the separable-block tests share (tests/test_gpu_sep.py, tests/test_sep_host.py): a float64 restatement of a short chain
+"""What the separable-block tests share (tests/test_gpu_sep.py, tests/test_gpu_act_f64.py, tests/test_sep_host.py): a float64 restatement of a short chain
 of JasperBlocks with an ELEMENTWISE error bound per arithmetic, the restatement of the product's kernel choice (which form
 every sub-layer takes), the case table and its inputs, a device-like float32 evaluation with switchable defects, and the
 runner that puts one case through asr.JasperEncoder (vasr_encoder_f32) and lists what it finds wrong.
@@ -57,6 +57,28 @@ test_sep_host.py would then sit at 5e-5 of it.)  With u = 2^-24 (EPS), per layer
 
 The bound is the sum over the chain, + 2^-126 so that exact zeros compare.  Every element of the stored tensor is judged, the
 columns past a row's length too: the reference computes them from the masked inputs (relu(shift (+ residual))).
+
+HARDTANH, SELU AND MAX RESIDUALS (vasr_set_activation; Case.activation / Case.residual_mode, the encoder's: every block of a case
+runs them; ACT_CASES, PROBES, tests/test_gpu_act_f64.py).  With activation "relu" and residual_mode "add" everything above is
+computed exactly as before, same bits.  Otherwise, behind a layer's pre-activation y with bound E_in:
+  hardtanh = min(max(y, -1), 1): 1-Lipschitz, and min and max round nothing:                        E_out = E_in
+  SELU = lambda y (y > 0), lambda alpha expm1(y) (y <= 0), torch's constants:       E_out = L E_in + S u |selu(y)|
+    L = the supremum of |selu'| over [y - E_in, y + E_in]: selu' is lambda on x > 0 and lambda alpha e^x on x <= 0, so L = lambda
+    where y - E_in > 0 and lambda alpha exp(min(y + E_in, 0)) elsewhere -- at most lambda alpha = 1.7581, and small for deeply
+    negative y (this L is a true Lipschitz constant over the interval, not a first-order one).  S = 4 (SELU_OWN): expm1f within
+    1 ulp (ROCm's published device-math accuracy), the float32 rounding of the constant lambda alpha, one multiply, one spare.
+    S is a constant of the bound, not a knob: an element that exceeds it on the identity probes is a finding.
+  max residual, y = max(a, r) before the activation (RES epilogue with res_max; never folded, so no DUAL and no fused kernel
+    with a folded residual; the residual GEMM itself is Epilogue<0> with the relu flag clear, as under add: no clamp):
+    |max(a, r) - max(a', r')| <= max(E_a, E_r), and the "1 u (A_y + A_res)" term of the add disappears with the add (max rounds
+    nothing); A = max(A_y, A_res).
+The columns past a row's length then hold selu(shift (+ residual shift)) resp. act(max(shift, residual shift)), and are judged.
+An ACT_CASE's block under test has the gamma and beta of its BNs scaled per channel by 2^-14 ... 2^6 (spread_scales; under max
+beta of the two max arguments one unit lower), so that its pre-activations lie on both sides of, at and far beyond every point
+where an activation changes behaviour -- test_sep_host.py asserts the shares --, and its trailing block is not the identity but
+alpha = 1/2, beta = 1/4 (weights() says why).  An identity PROBE (_probe) is a first block whose conv and BN are the identity:
+its pre-activation is the input itself, a sweep (probe_values), and with `sparse` its GEMMs' accumulation terms count the one
+non-zero weight of a row, so that the probe's bound is ~ 12 u |act(x)|: the affine's 7, SELU's 4, one product.
 """
 import numpy as np
 import torch
@@ -141,10 +163,11 @@ def latency_supported(M, K, K1):
     return M % 128 == 0 and K in (256, 512, 1024) and (K1 == 0 or K1 % 256 == 0)
 
 
-def residual_folds(cfg, cin):
-    """vasr_api.cpp build_encoder: the residual 1x1 conv becomes a second K range of the block's last GEMM."""
+def residual_folds(cfg, cin, residual_mode="add"):
+    """vasr_api.cpp build_encoder: the residual 1x1 conv becomes a second K range of the block's last GEMM (the fold sums:
+    add mode only)."""
     k, stride, _ = _geo(cfg)
-    if not cfg["residual"] or stride != 1 or not (cfg["separable"] or k == 1):
+    if not cfg["residual"] or stride != 1 or not (cfg["separable"] or k == 1) or residual_mode == "max":
         return False
     f = cfg["filters"]
     k1 = f if cfg["repeat"] > 1 else cin
@@ -152,12 +175,17 @@ def residual_folds(cfg, cin):
     return k1 % chunk == 0 and cin % chunk == 0
 
 
-def plan(case, arith, cus):
+def plan(case, arith, cus, fused=True):
     """-> list (one entry per block) of lists of launches, in run_encoder's order.  A launch is a dict: kind = "fused" (cols 64
     / 128, dual), "dw" (form toeplitz / fma / generic) or "gemm" (tile = 1 .. 5 or "lat" or "fp32", arith = the arithmetic that
     runs -- a GEMM whose source has no published maxima keeps 3 x bf16 in f16x2 mode --, epi = plain / masked / RES / DUAL,
-    port = it writes the unpadded encoder output, mx = whose maximum scales the activations: "in", "dw", "l1")."""
+    port = it writes the unpadded encoder output, mx = whose maximum scales the activations: "in", "dw", "l1").
+    Under residual_mode "max" (build_encoder / run_encoder) the residual is never folded: no DUAL GEMM, no fused kernel with a
+    folded residual, the last sub-layer of a residual block is not fused and ends in the RES epilogue (with res_max).  The
+    activation changes no choice: under hardtanh or SELU in add mode the residual folds as under ReLU.  fused=False: the
+    two-kernel form of every sub-layer (VASR_FUSED=0 on the devtools build)."""
     B, T = case.B, case.T
+    mode = getattr(case, "residual_mode", "add")
     split = arith != "fp32"
     f16 = arith == "f16x2"
     cin = case.feat_in
@@ -170,7 +198,7 @@ def plan(case, arith, cus):
         last_block = i + 1 == len(case.blocks)
         k, stride, dil = _geo(cfg)
         f, rep, sep, res = cfg["filters"], cfg["repeat"], cfg["separable"], cfg["residual"]
-        fold = residual_folds(cfg, cin)
+        fold = residual_folds(cfg, cin, mode)
         blk_amax, blk_ld, blk_cin = has_amax, ld, cin
         L = []
 
@@ -188,7 +216,7 @@ def plan(case, arith, cus):
             last_sub = r + 1 == rep
             enc_out = last_block and last_sub
             fuse_res = last_sub and fold
-            if (f16 and sep and c == 256 and f == 256 and stride == 1 and dil == 1 and k in (33, 39) and has_amax
+            if (fused and f16 and sep and c == 256 and f == 256 and stride == 1 and dil == 1 and k in (33, 39) and has_amax
                     and not (last_sub and res and not fold) and (not fuse_res or (blk_amax and blk_ld == ld and blk_cin == 256))
                     and ld % 128 == 0 and not enc_out):
                 cols = fused_tile_choice(B * (ld // 128), cus)
@@ -233,14 +261,59 @@ def form_names(p_block):
     return names
 
 
+def epilogue_kind(relu, activation, res_max):
+    """vasr_internal.h epilogue_kind: the EPI template argument of a GEMM or fused launch."""
+    if relu and activation == "selu":
+        return 2
+    return 1 if (relu and activation != "relu") or res_max else 0
+
+
+def act_forms(case, arith, cus):
+    """The launches of the block under test as (kernel, form, EPI, max, arithmetic, port): kernel = a tile "512x128" ..., "lat",
+    "fp32", "fused64" / "fused128"; form = plain / masked / RES / DUAL, a fused kernel's "plain" or "+res"; max = the launch
+    combines a residual by max (a RES epilogue in max mode).  The launchers hand epilogue_kind the launch's OWN max, not the
+    encoder's mode: RES && a.res_max (encoder_pw_split.hip, encoder_pw_lat.hip), a.res && a.res_max (encoder_pw.hip), false
+    (encoder_fused.hip) -- test_sep_host.py reads those call sites.  So under max only the RES launch takes EPI 1 on account of
+    the max; a ReLU / max block's plain first sub-layer runs Epilogue<0>, and so does the block's own residual GEMM under every
+    activation: run_encoder builds it from pw_args' defaults (relu flag clear, no residual tensor, res_max 0).  The flag-clear
+    Epilogue<1> (bounds -inf, +inf) needs a launch that takes a max with the flag clear: the last sub-layer before an SE, or
+    the in-place gemm_max chain of a dense max residual.  Neither can be built from the blocks of this table (both have
+    float64 suites of their own to extend)."""
+    cfg = case.blocks[case.under]
+    res_max = case.residual_mode == "max"
+    p = plan(case, arith, cus)[case.under]
+    cin = case.blocks[case.under - 1]["filters"] if case.under else case.feat_in
+    own_res = cfg["residual"] and not residual_folds(cfg, cin, case.residual_mode)
+    out = []
+    for n, l in enumerate(p):
+        relu = not (own_res and n == 0)
+        if l["kind"] == "fused":
+            epi = epilogue_kind(relu, case.activation, False)
+            out.append((f"fused{l['cols']}", "+res" if l["dual"] else "plain", epi, False, "f16x2", False))
+        elif l["kind"] == "gemm":
+            mx = res_max and l["epi"] == "RES"
+            t = l["tile"] if isinstance(l["tile"], str) else "%dx%d" % SPLIT_TILES[l["tile"]]
+            out.append((t, l["epi"], epilogue_kind(relu, case.activation, mx), mx, l["arith"], l["port"]))
+    return out
+
+
 # ---- cases -------------------------------------------------------------------------------------------------------------------
 class Case:
     """blocks[under] is the block under test; blocks before it are run alone on the device first (their output is the
     reference's input), blocks after it belong to the judged chain."""
 
-    def __init__(self, name, feat_in, blocks, under, B, T=100, kind="gauss"):
+    def __init__(self, name, feat_in, blocks, under, B, T=100, kind="gauss", activation="relu", residual_mode="add"):
         self.name, self.feat_in, self.blocks, self.under, self.B, self.T, self.kind = name, feat_in, blocks, under, B, T, kind
+        self.activation, self.residual_mode = activation, residual_mode       # the encoder's: every block of the case
+        self.spread = False       # ACT_CASES: the BNs of the block under test scaled per channel (weights())
+        self.probe = False        # PROBES: the block under test is the identity, the input a sweep (weights(), inputs())
         self.seed = 100 + sum(map(ord, name)) % 97
+
+    def small(self, B):
+        """The same case at another batch, for plan() (the rows themselves are taken from this case's inputs)."""
+        c = Case(self.name, self.feat_in, self.blocks, self.under, B, self.T, self.kind, self.activation, self.residual_mode)
+        c.spread, c.probe = self.spread, self.probe
+        return c
 
     def __repr__(self):
         return self.name
@@ -300,22 +373,130 @@ BF16X2_CASE = "c512_b24"       # the opt-in reduced arithmetic: one case, held t
 FORCED = ["c256_b16_res", "c512_b16", "r512_b16", "fin_b8"]       # small batches: every forced tile applies
 
 
+# ---- hardtanh, SELU and max residuals (vasr_set_activation): tests/test_gpu_act_f64.py -------------------------------------------
+def _act(case, activation, residual_mode):
+    """The case as `<name>_<activation>_<mode>` with the encoder's options set and the spread BNs of weights()."""
+    c = Case(f"{case.name}_{activation}_{residual_mode}", case.feat_in, case.blocks, case.under, case.B, case.T, case.kind,
+             activation, residual_mode)
+    c.spread = True
+    return c
+
+
+ACT_CASES = [
+    # max: the residual is its own GEMM (masked, relu flag clear: Epilogue<0>, see act_forms), the block's first sub-layer
+    # plain and its last one RES with res_max, all three on the tile the batch picks; r512: on the port (scalar apply), the
+    # others on a padded interior buffer (apply4).  Per tile one case with EPI 1 and one with EPI 2 (SELU); the EPI 1 cases
+    # are hardtanh ones but at 128 x 64, where the ReLU / max case reaches EPI 1 in its RES launch alone and the plain
+    # hardtanh form comes from c512_b24_hardtanh_add.
+    _act(_res512("r512_b16", 16, 87, dil=2), "selu", "max"), _act(_c256("c256_b16_res", 16, 39, True, kind="relu"), "hardtanh", "max"),
+    _act(_res512("r512_b24", 24, 51, kind="relu"), "selu", "max"), _act(_c256("c256_b130_res", 130, 39, True, kind="wide"), "relu", "max"),
+    _act(Case("c768_b64", 64, [LEAD(256), blk(768, 33, 2, True), TRAIL(768)], 1, 64, kind="wide"), "selu", "max"),
+    _act(_res512("r512_b96", 96, 63, kind="wide"), "hardtanh", "max"),
+    _act(_c256("c256_b192_res", 192, 33, True, kind="relu"), "selu", "max"), _act(_res512("r512_b192", 192, 75), "hardtanh", "max"),
+    _act(Case("r512t_b218", 320, [blk(512, 51, 2, True), TRAIL(512)], 0, 218), "selu", "max"), _act(_res512("r512_b218", 218, 63, kind="relu"), "hardtanh", "max"),
+    # K = 768 has no latency form: the 64 x 32 tile in the fp16 split, plain (second of three sub-layers) and RES
+    _act(Case("c768_b8", 64, [LEAD(256), blk(768, 33, 3, True), TRAIL(768)], 1, 8), "hardtanh", "max"),
+    _act(Case("c768_b8", 64, [LEAD(256), blk(768, 33, 3, True), TRAIL(768)], 1, 8, kind="relu"), "selu", "max"),
+    # add: the residual folds as under ReLU -- the fused kernel in both widths without (first sub-layer) and with it, DUAL
+    _act(_c256("c256_b48_res", 48, 33, True), "hardtanh", "add"), _act(_c256("c256_b48_res", 48, 33, True), "selu", "add"),
+    _act(_c256("c256_b205_res", 205, 39, True), "hardtanh", "add"), _act(_c256("c256_b205_res", 205, 39, True), "selu", "add"),
+    _act(_c512("c512_b16", 16, 87, dil=2, kind="wide"), "selu", "add"), _act(_c512("c512_b24", 24, 63, trail=True), "hardtanh", "add"),
+    # the final shape on the port, the block behind the stride-2 prologue, three tiles a row
+    _act(Case("fin_b8", 64, [LEAD(512), blk(1024, 1, separable=False)], 1, 8, kind="wide"), "selu", "add"),
+    _act(Case("pro_b16_then_res", 64, [blk(256, 33, 1, False, stride=2), blk(256, 33, 2, True)], 1, 16, 201, "relu"), "relu", "max"),
+    _act(_c256("c256_t300_b16_res", 16, 33, True, T=300, kind="wide"), "hardtanh", "add"),
+]
+ACT_FORCED = ["c512_b16_selu_add", "c256_b16_res_hardtanh_max", "r512_b16_selu_max", "pro_b16_then_res_relu_max"]
+ACT_FUSED = ["c256_b48_res_hardtanh_add", "c256_b48_res_selu_add"]
+
+
+def _probe(C, B, T, activation, residual_mode, last):
+    """An identity probe: the block under test is the encoder's FIRST block, a 1x1 conv C -> C with the identity weight and the
+    identity BN (a max probe: with a residual whose conv is -I, i.e. max(x, -x)), so its pre-activation is the input itself:
+    exactly in fp32 and in 3 x bf16 (which the first block's GEMM runs in f16x2 mode too: its source has no published maxima).
+    last: the probe writes the port (scalar apply); else a TRAILING identity block follows (the probe stores through apply4,
+    and in f16x2 mode the trailing GEMM runs the fp16 split on the maxima the probe published and applies the activation once
+    more, in ITS instantiation, to act(x), on the port).  last = 2 trailing blocks ("in2"): the first of them is an interior
+    fp16-split GEMM, the float4 path of that arithmetic on the probe's values."""
+    res = residual_mode == "max"
+    trail = 2 if last == 2 else (0 if last else 1)
+    c = Case(f"probe_c{C}_b{B}_t{T}_{activation}_{residual_mode}_{('last', 'in', 'in2')[trail]}", C,
+             [blk(C, 1, 1, res, separable=False)] + [TRAIL(C)] * trail, 0, B, T, "probe", activation, residual_mode)
+    c.probe = True
+    return c
+
+
+PROBES = [
+    _probe(256, 8, 100, "selu", "add", False), _probe(256, 8, 100, "selu", "add", True),
+    _probe(512, 130, 100, "selu", "add", True), _probe(512, 8, 300, "selu", "add", False),
+    _probe(256, 130, 300, "selu", "add", False),
+    _probe(256, 8, 100, "hardtanh", "add", False), _probe(512, 8, 300, "hardtanh", "add", True),
+    _probe(512, 130, 100, "hardtanh", "add", False),
+    _probe(256, 8, 100, "relu", "max", False), _probe(512, 130, 100, "relu", "max", True),
+    _probe(512, 8, 300, "hardtanh", "max", False), _probe(256, 130, 300, "hardtanh", "max", True),
+    _probe(256, 8, 100, "selu", "max", True), _probe(512, 130, 100, "selu", "max", False),
+    _probe(256, 130, 300, "selu", "max", True),
+    _probe(256, 130, 100, "selu", "add", 2), _probe(512, 8, 100, "hardtanh", "add", 2),
+]
+BY_NAME.update({c.name: c for c in ACT_CASES + PROBES})
+
+
+def probe_values():
+    """What an identity probe's input holds: both signs of 8 magnitudes an octave from 2^-24 to 2^6, exact +-1, +-0 and
+    +-(1 +- 2^-23), and values below -88 (there expm1f is -1 exactly), with +88.5 beside them."""
+    mags = np.exp2(np.linspace(-24, 6, 241)).astype(np.float32)
+    one = np.float32(1)
+    edge = [one, -one, np.float32(0), -np.float32(0), one + np.float32(2.0 ** -23), one - np.float32(2.0 ** -23),
+            -(one + np.float32(2.0 ** -23)), -(one - np.float32(2.0 ** -23))]
+    return np.concatenate([mags, -mags, np.asarray(edge, dtype=np.float32),
+                           np.asarray([-87.5, -88.5, -89, -100, -1000, 88.5], dtype=np.float32)])
+
+
+def spread_scales(C):
+    """Per-channel factors on gamma and beta of the BNs of an ACT_CASE's block under test: powers 2^-14 ... 2^6, log-spaced
+    and permuted over the channels, so that one tensor's pre-activations lie deep inside, around and far outside every range
+    an activation treats differently (hardtanh's [-1, 1]; SELU's (-2^-10, 0) and below -10) and both arguments of a max, scaled
+    alike, win."""
+    return np.exp2(np.linspace(-14, 6, C))[(np.arange(C) * 37) % C].astype(np.float32)
+
+
 def weights(case):
     """synth's weights for the chain (BN statistics with scale != 1 and shift != 0), channel 3's taps of the block under test
-    a thousand times smaller, a trailing block the identity: weight I, BN with alpha = 1 and beta = 0 exactly in float32."""
+    a thousand times smaller, a trailing block the identity: weight I, BN with alpha = 1 and beta = 0 exactly in float32.
+    A probe's block under test is the identity too (its residual conv -I); an ACT_CASE has the BNs of its block under test
+    spread over the channels and a trailing block that halves and lifts (below)."""
     from viet_asr_amd import synth
     sd = synth.encoder_state_dict(case.blocks, case.feat_in, case.seed)
     if case.blocks[case.under]["separable"]:
         sd[f"encoder.{case.under}.mconv.0.conv.weight"][3] *= np.float32(1e-3)
     var = np.float32(1) - np.float32(1e-3)
     assert np.float32(var + np.float32(1e-3)) == np.float32(1)
-    for i in range(case.under + 1, len(case.blocks)):
-        c = case.blocks[i]["filters"]
-        pre = f"encoder.{i}.mconv."
-        assert sd[pre + "0.conv.weight"].shape == (c, c, 1)
-        sd[pre + "0.conv.weight"][...] = np.eye(c, dtype=np.float32)[:, :, None]
+
+    def identity(conv, bn, c, sign=1):
+        assert sd[conv + ".conv.weight"].shape == (c, c, 1)
+        sd[conv + ".conv.weight"][...] = np.float32(sign) * np.eye(c, dtype=np.float32)[:, :, None]
         for key, val in (("weight", 1), ("bias", 0), ("running_mean", 0), ("running_var", var)):
-            sd[pre + "1." + key][...] = np.float32(val)
+            sd[bn + "." + key][...] = np.float32(val)
+
+    for i in range(case.under + (0 if case.probe else 1), len(case.blocks)):
+        identity(f"encoder.{i}.mconv.0", f"encoder.{i}.mconv.1", case.blocks[i]["filters"])
+    if case.probe and case.blocks[case.under]["residual"]:       # max(x, -x)
+        identity(f"encoder.{case.under}.res.0.0", f"encoder.{case.under}.res.0.1", case.blocks[case.under]["filters"], -1)
+    if case.spread:
+        # Behind ReLU or hardtanh an identity block would apply the same idempotent clamp again and hide what the block under
+        # test clamped wrongly (max taken after the activation: clamp(max(clamp(y), r)) = clamp(max(y, r))).  An ACT_CASE's
+        # trailing block therefore halves and lifts, alpha = 1/2 and beta = 1/4 exactly: still one product a row.
+        for i in range(case.under + 1, len(case.blocks)):
+            sd[f"encoder.{i}.mconv.1.weight"][...] = np.float32(0.5)
+            sd[f"encoder.{i}.mconv.1.bias"][...] = np.float32(0.25)
+        s = spread_scales(case.blocks[case.under]["filters"])
+        bns = [key[:-len(".running_var")] for key in sd if key.startswith(f"encoder.{case.under}.") and key.endswith(".running_var")]
+        last = max((b for b in bns if ".mconv." in b), key=lambda b: int(b.rsplit(".", 1)[1]))
+        for bn in bns:
+            sd[bn + ".weight"] = sd[bn + ".weight"] * s
+            # (the larger of two symmetric arguments is negative a quarter of the time: both one unit down under max)
+            down = case.residual_mode == "max" and (bn == last or ".res." in bn)
+            sd[bn + ".bias"] = (sd[bn + ".bias"] - np.float32(1 if down else 0)) * s
     return sd
 
 
@@ -338,6 +519,10 @@ def inputs(case):
     lens = np.concatenate([edges, rng.integers(T // 2, T + 1, max(0, B - len(edges)))])[:B].astype(np.int64)
     lens[rng.integers(len(edges), B) if B > len(edges) else -1] = T
     rng.shuffle(lens)
+    if case.probe:       # every value of probe_values() in every row of 495 elements or more, in all channels and columns
+        vals = probe_values()
+        b, c, t = np.ogrid[:B, :case.feat_in, :T]
+        return vals[(b * 131 + c * T + t) % len(vals)], lens
     x = rng.standard_normal((B, case.feat_in, T)).astype(np.float32)
     if case.kind == "relu":
         x = np.maximum(x, 0)
@@ -397,11 +582,41 @@ def _gemm_own(arith, n, Aacc, Wabs, Asrc, Mx, Mw):
     return (n * EPS + R16) * Aacc + F16 * floor
 
 
-def chain(x, lens, sd, blocks, i0, plans):
+SELU_LAMBDA = 1.0507009873554804934193349852946       # torch's constants (nn.SELU)
+SELU_ALPHA = 1.6732632423543772848170429916717
+SELU_OWN = 4                                          # S: expm1f <= 1 ulp, the rounded constant, one multiply, one spare
+
+
+def act64(activation, y):
+    """The activation in y's dtype, as oracle.quartznet_oracle.activation_fn."""
+    if activation == "relu":
+        return torch.relu(y)
+    if activation == "hardtanh":
+        return torch.clamp(y, -1.0, 1.0)
+    if activation == "selu":
+        return torch.nn.functional.selu(y)
+    raise KeyError(activation)
+
+
+def _act_bound(activation, y, E):
+    """-> (act(y), the bound behind the activation) for one arithmetic's bound E on y (float64)."""
+    v = act64(activation, y)
+    if activation != "selu":
+        return v, E                                   # ReLU, hardtanh: 1-Lipschitz, min and max are exact
+    L = torch.where(y - E > 0, torch.full_like(y, SELU_LAMBDA),
+                    SELU_LAMBDA * SELU_ALPHA * torch.exp(torch.clamp(y + E, max=0.0)))
+    return v, L * E + SELU_OWN * EPS * v.abs()
+
+
+def chain(x, lens, sd, blocks, i0, plans, activation="relu", residual_mode="add", sparse=False, pre=None):
     """The blocks `blocks` (encoder indices i0 ...) on x [B, C, T] float64 (taken as exact), lens [B] int64.  plans:
-    {arith: plan(...)[i0:]} for the arithmetics wanted.  -> (ref [B, C', T'] float64, {arith: bound}, lens')."""
+    {arith: plan(...)[i0:]} for the arithmetics wanted.  -> (ref [B, C', T'] float64, {arith: bound}, lens').
+    activation, residual_mode: the encoder's.  sparse: a GEMM's accumulation term counts the non-zero weights of its fullest
+    row, not K (the identity probes: adding an exact zero rounds nothing).  pre: a list that receives, per sub-layer,
+    dict(block, sub, y = the pre-activation, args = the two arguments of a max residual or None, lens)."""
     ariths = list(plans)
     lens = np.asarray(lens, dtype=np.int64)
+    terms = (lambda W: int((W != 0).sum(1).max())) if sparse else (lambda W: W.shape[1])
     v = x
     E = {a: torch.zeros_like(x) for a in ariths}
     with torch.no_grad():
@@ -413,7 +628,7 @@ def chain(x, lens, sd, blocks, i0, plans):
             it = {a: iter(plans[a][bi]) for a in ariths}
             blk_in = (_mask(v, lens), _mask(v, lens).abs(), {a: _mask(E[a], lens) for a in ariths})
             blk_mx = {a: _rowmax(v.abs() + E[a], lens) for a in ariths}
-            fold = residual_folds(cfg, v.shape[1])
+            fold = residual_folds(cfg, v.shape[1], residual_mode)
             R = None
             if res and not fold:
                 W = torch.as_tensor(sd[f"encoder.{i}.res.0.0.conv.weight"][:, :, 0]).double()
@@ -429,7 +644,7 @@ def chain(x, lens, sd, blocks, i0, plans):
                 for a, Ein in zip(ariths, got[1:]):
                     l = next(it[a])
                     assert l["kind"] == "gemm" and l["epi"] == "masked"
-                    own = _gemm_own(l["arith"], W.shape[1], Aacc, W.abs(), blk_in[1], blk_mx[a], float(W.abs().max()))
+                    own = _gemm_own(l["arith"], terms(W), Aacc, W.abs(), blk_in[1], blk_mx[a], float(W.abs().max()))
                     RE[a] = al.abs() * (Ein + own) + AFFINE * EPS * RA
                 R = (rv, RA, RE)
             j = 0
@@ -510,24 +725,50 @@ def chain(x, lens, sd, blocks, i0, plans):
                             EPS * (yA + yA2)
                     else:
                         assert l["kind"] == "fused" or l["epi"] in ("plain", "masked", "RES"), (l, a)
-                        own = _gemm_own(l["arith"], W.shape[1], Aacc, W.abs(), Am, mx[a], float(W.abs().max()))
+                        own = _gemm_own(l["arith"], terms(W), Aacc, W.abs(), Am, mx[a], float(W.abs().max()))
                         yE[a] = al.abs() * (got[1 + idx] + own) + AFFINE * EPS * yA
                         if last_sub and res:
                             assert l["epi"] == "RES", (l, a)
-                            yE[a] = yE[a] + R[2][a] + EPS * (yA + R[1])
+                            if residual_mode == "max":
+                                yE[a] = torch.maximum(yE[a], R[2][a])
+                            else:
+                                yE[a] = yE[a] + R[2][a] + EPS * (yA + R[1])
+                args = None
                 if dual:
                     yA = yA + yA2
+                elif last_sub and res and residual_mode == "max":
+                    args = (yv, R[0])
+                    yv, yA = torch.maximum(yv, R[0]), torch.maximum(yA, R[1])
                 elif last_sub and res:
                     yv, yA = yv + R[0], yA + R[1]
-                v, E = torch.relu(yv), yE
+                if pre is not None:
+                    pre.append(dict(block=i, sub=r, y=yv, args=args, lens=lens))
+                if activation == "relu":
+                    v, E = torch.relu(yv), yE
+                else:
+                    E = {a: _act_bound(activation, yv, yE[a])[1] for a in ariths}
+                    v = act64(activation, yv)
     return v, {a: E[a] + TINY for a in ariths}, lens
 
 
 # ---- a device-like float32 evaluation, with defects ---------------------------------------------------------------------------
 MUTANTS = ("mask_late", "res_lens", "dw_pad", "k_chunk", "w_11bit", "shift_before_res")
+ACT_MUTANTS = ("selu_exp_minus_1", "hardtanh_as_relu", "max_as_add", "max_after_act", "clamp_without_relu_flag")
 
 
-def f32_chain(x, lens, sd, blocks, i0, under=0, mutant=None, first_lens=None):
+def act32(activation, y, mut=None):
+    """The activation in float32 as vasr_device.h writes it (SELU: lambda v, (lambda alpha) expm1f(v) with the product of the
+    two float32 constants), or one of its defects."""
+    if activation == "relu":
+        return torch.relu(y)
+    if activation == "hardtanh":
+        return torch.clamp(y, 0.0 if mut == "hardtanh_as_relu" else -1.0, 1.0)
+    lam, la = np.float32(SELU_LAMBDA), np.float32(SELU_LAMBDA) * np.float32(SELU_ALPHA)
+    neg = torch.exp(y) - 1 if mut == "selu_exp_minus_1" else torch.expm1(y)
+    return torch.where(y > 0, float(lam) * y, float(la) * neg)
+
+
+def f32_chain(x, lens, sd, blocks, i0, under=0, mutant=None, first_lens=None, activation="relu", residual_mode="add"):
     """The same blocks in plain float32 on the CPU (sequential torch), arranged as the device arranges them: BN as the
     float32 affine of bn_affine in the GEMM's epilogue, a folded residual as ONE product over both K ranges with the scaled
     weights and the sum of both shifts.  mutant (applied to block `under` of the list only):
@@ -536,7 +777,19 @@ def f32_chain(x, lens, sd, blocks, i0, under=0, mutant=None, first_lens=None):
       dw_pad            the depthwise padding off by one
       k_chunk           one 64-wide K chunk of the second source (the residual) dropped
       w_11bit           the 1x1 weights rounded to 11 bits: the low fp16 plane dropped
-      shift_before_res  a folded residual's shift left out (only the main branch's shift is applied)."""
+      shift_before_res  a folded residual's shift left out (only the main branch's shift is applied)
+    and, with an activation or residual mode of vasr_set_activation (ACT_MUTANTS):
+      selu_exp_minus_1         SELU's negative side as float32 exp(x) - 1
+      hardtanh_as_relu         hardtanh's lower bound 0 instead of -1
+      max_as_add               the max residual added
+      max_after_act            the activation applied to the branch output alone, then max with the raw residual (under
+                               ReLU the same function, max(0, y, r); under hardtanh different where r > 1)
+      clamp_without_relu_flag  the residual GEMM of a max block (Epilogue<0> with the relu flag clear: act_forms) clamping
+                               at ReLU's floor 0 anyway.  (The flag-clear Epilogue<1> itself, bounds -inf and +inf, is not
+                               reachable by this chain: it needs an SE block or a dense max residual, act_forms says why.)
+                               Only SELU + max can show it: ReLU's and hardtanh's clamps are
+                               monotone and idempotent, clamp(max(y, clamp(r))) = clamp(max(y, r)), so under those two the
+                               defect changes no output and is none."""
     lens = np.asarray(lens, dtype=np.int64)
     v = x.float()
     f32 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float32))
@@ -551,7 +804,7 @@ def f32_chain(x, lens, sd, blocks, i0, under=0, mutant=None, first_lens=None):
             if mut == "res_lens":
                 rl = np.asarray(first_lens, dtype=np.int64)
             blk_in = _mask(v, rl)
-            fold = residual_folds(cfg, v.shape[1])
+            fold = residual_folds(cfg, v.shape[1], residual_mode)
             j = 0
             for r in range(rep):
                 last_sub = r + 1 == rep
@@ -587,10 +840,16 @@ def f32_chain(x, lens, sd, blocks, i0, under=0, mutant=None, first_lens=None):
                         R = al2[None, :, None] * torch.einsum("ok,bkt->bot", W2, src2)
                         if mut != "shift_before_res":
                             R = R + be2[None, :, None]
-                        y = al[None, :, None] * torch.einsum("ok,bkt->bot", W, vm) + be[None, :, None] + R
+                        if mut == "clamp_without_relu_flag":
+                            R = torch.relu(R)
+                        y = al[None, :, None] * torch.einsum("ok,bkt->bot", W, vm) + be[None, :, None]
+                        if mut == "max_after_act":
+                            v = torch.maximum(act32(activation, y), R)
+                            continue
+                        y = y + R if residual_mode == "add" or mut == "max_as_add" else torch.maximum(y, R)
                 else:
                     y = al[None, :, None] * torch.einsum("ok,bkt->bot", W, vm) + be[None, :, None]
-                v = torch.relu(y)
+                v = act32(activation, y, mut)
     return v, lens
 
 
@@ -617,9 +876,9 @@ def lens_chain(lens, blocks):
     return lens
 
 
-def encoder(blocks, feat_in, sd):
+def encoder(blocks, feat_in, sd, activation="relu", residual_mode="add"):
     from viet_asr_amd import asr
-    enc = asr.JasperEncoder(jasper=blocks, activation="relu", feat_in=feat_in)
+    enc = asr.JasperEncoder(jasper=blocks, activation=activation, feat_in=feat_in, residual_mode=residual_mode)
     enc.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})
     return enc
 
@@ -630,8 +889,9 @@ def device_outputs(case, device, ariths=ARITHS, profile=True):
     sd = weights(case)
     x, lens = inputs(case)
     xd, ld = torch.from_numpy(x).to(device), torch.from_numpy(lens).to(device)
-    full = encoder(case.blocks, case.feat_in, sd)
-    head = encoder(case.blocks[:case.under], case.feat_in, sub_state_dict(sd, case.under)) if case.under else None
+    full = encoder(case.blocks, case.feat_in, sd, case.activation, case.residual_mode)
+    head = encoder(case.blocks[:case.under], case.feat_in, sub_state_dict(sd, case.under), case.activation,
+                   case.residual_mode) if case.under else None
     out = {}
     for a in ariths:
         h = full._get_handle()
@@ -666,7 +926,7 @@ def device_rows(case, device, rows, ariths):
     sd = weights(case)
     x, lens = inputs(case)
     xd, ld = torch.from_numpy(x[rows]).to(device), torch.from_numpy(lens[rows]).to(device)
-    enc = encoder(case.blocks, case.feat_in, sd)
+    enc = encoder(case.blocks, case.feat_in, sd, case.activation, case.residual_mode)
     out = {}
     for a in ariths:
         enc._get_handle().set_gemm_mode(a)
@@ -674,20 +934,22 @@ def device_rows(case, device, rows, ariths):
     return out
 
 
-def check_case(case, got, cus, ariths=ARITHS):
+def check_case(case, got, cus, ariths=ARITHS, fused=True):
     """got: device_outputs(case).  -> dict(failures = [...], ratios = {arith: worst |y - ref| / bound}, valid = the same
-    over the frames below each row's length only, forms = {arith: names of the launches of the block under test})."""
+    over the frames below each row's length only, forms = {arith: names of the launches of the block under test}).
+    fused: as plan()'s."""
     sd = weights(case)
     x, lens = inputs(case)
     lens_u = lens_chain(lens, case.blocks[:case.under])
-    plans = {a: plan(case, a, cus) for a in ariths}
+    plans = {a: plan(case, a, cus, fused) for a in ariths}
     bad, ratios, forms, valid = [], {}, {}, {}
     groups = {}
     for a in ariths:       # arithmetics that produced the same leading output share one reference
         groups.setdefault(got[a]["lead"].numpy().tobytes(), []).append(a)
     for members in groups.values():
         lead = got[members[0]]["lead"].double()
-        ref, bounds, lo = chain(lead, lens_u, sd, case.blocks[case.under:], case.under, {a: plans[a][case.under:] for a in members})
+        ref, bounds, lo = chain(lead, lens_u, sd, case.blocks[case.under:], case.under, {a: plans[a][case.under:] for a in members},
+                                case.activation, case.residual_mode, case.probe)
         for a in members:
             forms[a] = form_names(plans[a][case.under])
             want = launch_counts(plans[a])
