@@ -8,7 +8,7 @@ carries no published maxima can take neither the Toeplitz nor the fused form, so
 block UNDER TEST, and an optional TRAILING block that passes every channel through: a 1x1 conv C -> C whose weight is the
 identity matrix and whose BatchNorm is the identity (gamma 1, beta 0, mean 0, var chosen so that the float32 alpha is exactly
 1; weights() overwrites synth's draw).  The trailing block is there because the last sub-layer of an encoder's LAST block
-writes the port tensor and is never fused (vasr_api.cpp run_encoder: !enc_out): the fused kernel with its folded residual, and
+writes the port tensor and is never fused (encoder_run.cpp run_encoder: !enc_out): the fused kernel with its folded residual, and
 the dual-source GEMM on a padded interior buffer, are only reached by a block that is not the last one.
 
 THE REFERENCE is the float64 graph of oracle.quartznet_oracle (jasper_block_forward; chain() below restates it so that the
@@ -35,7 +35,7 @@ test_sep_host.py would then sit at 5e-5 of it.)  With u = 2^-24 (EPS), per layer
     here issues 16- or 32-deep MFMAs (32x32x16; the Toeplitz form 16x16x32), so an accumulator is rounded 3 C / 16 resp.
     6 C / 16 <= C times, not once per product.  The premise, which the test thereby holds the kernels to: the products
     inside one instruction are summed with no more error than one float32 rounding per K index.
-  BatchNorm affine y = alpha acc + beta, alpha = g / sqrt(var + 1e-3), beta = b - mean alpha in float32 (vasr_api.cpp
+  BatchNorm affine y = alpha acc + beta, alpha = g / sqrt(var + 1e-3), beta = b - mean alpha in float32 (model_build.cpp
     bn_affine): alpha carries 4 roundings (var + eps, sqrt, 1 / x, the product), beta 2 more on |b| + |mean alpha|, the
     epilogue's multiply and add one each; a folded residual rounds alpha W once more instead of multiplying in the epilogue:
                                                                                                     7 u A_y
@@ -164,7 +164,7 @@ def latency_supported(M, K, K1):
 
 
 def residual_folds(cfg, cin, residual_mode="add"):
-    """vasr_api.cpp build_encoder: the residual 1x1 conv becomes a second K range of the block's last GEMM (the fold sums:
+    """model_build.cpp build_encoder: the residual 1x1 conv becomes a second K range of the block's last GEMM (the fold sums:
     add mode only)."""
     k, stride, _ = _geo(cfg)
     if not cfg["residual"] or stride != 1 or not (cfg["separable"] or k == 1) or residual_mode == "max":
@@ -540,7 +540,7 @@ def sub_state_dict(sd, n_blocks):
 
 # ---- the float64 chain with magnitudes and bounds ------------------------------------------------------------------------------
 def bn_affine(sd, prefix):
-    """vasr_api.cpp bn_affine in float32 -> (alpha, beta) as the device holds them, and |b| + |mean alpha| (float64)."""
+    """model_build.cpp bn_affine in float32 -> (alpha, beta) as the device holds them, and |b| + |mean alpha| (float64)."""
     g, b, m, v = (np.asarray(sd[prefix + s], dtype=np.float32) for s in (".weight", ".bias", ".running_mean", ".running_var"))
     invstd = np.float32(1.0) / np.sqrt(v + np.float32(1e-3))
     alpha = g * invstd

@@ -231,7 +231,7 @@ for seed in range({n}):
     want_fused = sum(b["repeat"] for b in jas[1:] if b["separable"] and b["filters"] == 256)
     # (after a 512-channel block the first sub-block has 512 input channels and the residual comes from a 512-channel
     # tensor: neither is a fused shape -- the fuzz found the second case running through the fused kernel with garbage
-    # for a K range it does not have; vasr_api.cpp now checks the folded residual's K)
+    # for a K range it does not have; encoder_run.cpp now checks the folded residual's K)
     if not ok or fused == 0:
         bad.append((seed, err, tol, fused, want_fused, B, L))
 print("FUSED_FUZZ_OK" if not bad else "FUSED_FUZZ_BAD %r" % bad)

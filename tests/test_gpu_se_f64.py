@@ -1,4 +1,4 @@
-"""-m gpu: squeeze-and-excitation blocks (csrc/encoder_se.hip and the plan around each SE in vasr_api.cpp run_encoder) against
+"""-m gpu: squeeze-and-excitation blocks (csrc/encoder_se.hip and the plan around each SE in encoder_run.cpp run_encoder) against
 the float64 oracle (oracle.quartznet_oracle, se_mean="rows": each row's own frames, the device's documented time mean).
 
 Block level: one to three blocks through asr.JasperEncoder (vasr_encoder_f32) in f16x2, bf16x3 and fp32 on ragged batches --

@@ -478,9 +478,12 @@ def test_epilogue_kind_restated():
              for name in ("encoder_pw_split.hip", "encoder_pw_lat.hip", "encoder_pw.hip", "encoder_fused.hip")}
     assert calls == {"encoder_pw_split.hip": ["a.relu, a.act, RES && a.res_max"], "encoder_pw_lat.hip": ["a.relu, a.act, RES && a.res_max"],
                      "encoder_pw.hip": ["a.relu, a.act, a.res && a.res_max"], "encoder_fused.hip": ["a.relu, a.act, false"]}, calls
-    api = read("vasr_api.cpp")
-    # the residual GEMMs' loop: res / res_max only under gemm_max (q > 0: a dense run), relu never
-    loop = api[api.index("for (size_t q = 0; q < B.res.size() && !B.fused_res; ++q)"):api.index("for (size_t r = 0; r < B.subs.size(); ++r)")]
+    run = read("encoder_run.cpp")
+    # the residual GEMMs' loop, EncoderPass::residual_branch from its head to its closing brace: res / res_max only under
+    # gemm_max (q > 0: a dense run), relu never
+    loop = run[run.index("  int residual_branch(const Block& B) {"):]
+    loop = loop[:loop.index("\n  }\n")]
+    assert "for (size_t q = 0; q < B.res.size() && !B.fused_res; ++q)" in loop and "run_pointwise(h, a, W, st, dry)" in loop
     assert "const bool gemm_max = h->res_max && !G.se.d_w1 && q > 0;" in loop
     assert re.findall(r"a\.res_max\s*=[^;]*;", loop) == ["a.res_max = 1;"] and "if (gemm_max) { a.res = R;" in loop
     assert "a.relu" not in loop

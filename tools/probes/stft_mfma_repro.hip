@@ -41,7 +41,7 @@ template <class T> static T* up(const std::vector<T>& v) { T* d = nullptr; hipMa
 int main(int argc, char** argv) {
   const int pace_us = argc > 1 ? atoi(argv[1]) : 0;
   const int B = 64, L = 160000, hop = 160, T = 1 + L / hop;
-  // front-end tables as vasr_api.cpp build_frontend makes them: hann(320) centred in 512, the two twiddle tables, 64 triangular filters
+  // front-end tables as model_build.cpp build_frontend makes them: hann(320) centred in 512, the two twiddle tables, 64 triangular filters
   std::vector<float> win(512, 0.f), tw256(512), tw512(2 * 258, 0.f), mw(64 * vasr::kMelTaps, 0.f);
   std::vector<int32_t> lo(64);
   for (int i = 0; i < 320; ++i) win[96 + i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * i / 319.0));
@@ -52,7 +52,7 @@ int main(int argc, char** argv) {
   unsigned s = 12345u;
   for (auto& v : wav) { s = s * 1664525u + 1013904223u; v = ((int)(s >> 9) - (1 << 22)) * (0.1f / (1 << 22)); }
   // optional: the library's REAL inputs, dumped by tools/probes/stft_mfma_repro_dump.py -- <dir>/wav.bin [64][160000] f32, win.bin [320] f32,
-  // fb.bin [64][257] f32 (tables then built as vasr_api.cpp build_frontend builds them)
+  // fb.bin [64][257] f32 (tables then built as model_build.cpp build_frontend builds them)
   if (argc > 3) {
     const std::string d = argv[3];
     auto rd = [&](const char* name, float* dst, size_t n) { FILE* f = fopen((d + "/" + name).c_str(), "rb"); if (!f || fread(dst, 4, n, f) != n) { printf("cannot read %s\n", name); exit(3); } fclose(f); };

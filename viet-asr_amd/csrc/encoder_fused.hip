@@ -9,7 +9,7 @@
 //
 // Structure (numbers for the 128-frame tile; the 64-frame form of round 4 -- template parameter BN, FTile -- halves the
 // columns of every role: 8 frames per producer lane, 2 x 2 MFMA tiles per consumer, 110 KB of LDS; it is the form for
-// batches whose 128-frame tiles would leave the chip half empty, vasr_api.cpp run_encoder):
+// batches whose 128-frame tiles would leave the chip half empty, encoder_run.cpp run_encoder):
 // a workgroup owns ALL 256 input and output channels of a 128-frame time tile and is split by ROLE
 // (wave specialisation -- one kernel, two instruction streams, no compiler-interleaved software pipeline):
 //

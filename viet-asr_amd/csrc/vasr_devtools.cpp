@@ -1,18 +1,18 @@
 // What libvasr_hip_dev.so adds to the product library (include/vasr_devtools.h): the kernel-selection switches read from the
-// environment, isolated-layer launches and the weight packers.  Compiled into the devtools build only (Makefile SRCS_DEV).
+// environment, isolated-layer launches, the weight packers and the buffer plan of an encoder pass.  Compiled into the devtools
+// build only (Makefile SRCS_DEV).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <initializer_list>
+#include <memory>
 #include <string>
 #include <vector>
 
-#include "vasr.h"
 #include "vasr_devtools.h"
-#include "vasr_host.h"
-#include "vasr_internal.h"
+#include "vasr_model.h"   // vasr_plan_buffers: the one devtools entry point that needs the handle's insides
 
 using namespace vasr;
 
@@ -261,6 +261,54 @@ int vasr_bench_groupnorm(const float* d_x, const int32_t* d_lens, int batch, int
   (void)hipFree(buf);
   if (e != hipSuccess) return fail(VASR_ERR_HIP, "bench_groupnorm: %s", hipGetErrorString(e));
   return 0;
+}
+
+// include/vasr_devtools.h.  An unfinalized handle is planned on a host-side shadow: the same checks and build_encoder, with
+// upload() allocating nothing; the pass itself is run_encoder's dry form, so the plan is made by the code that runs.
+int vasr_plan_buffers(vasr_handle* h, int batch, int64_t samples, int64_t mel_frames, int32_t* out, int cap) {
+  if (!h || !h->has_encoder || batch <= 0 || (samples <= 0 && mel_frames <= 0) || cap < 0 || (cap > 0 && !out))
+    return fail(VASR_ERR_INVALID, "bad argument");
+  if (samples > 0 && !(h->has_frontend && h->has_decoder))
+    return fail(VASR_ERR_STATE, "a plan by samples is the transcribe path's: the handle needs a front end and a CTC head");
+  if (h->profiling) return fail(VASR_ERR_STATE, "profiling is active");
+  std::unique_ptr<vasr_handle> shadow;
+  vasr_handle* e = h;
+  if (!h->finalized) {
+    shadow.reset(new vasr_handle(*h));
+    e = shadow.get();
+    e->plan_only = true;
+    int rc;
+    if ((rc = check_encoder(e)) || (rc = build_encoder(e))) return rc;
+    e->weights.clear();
+  }
+  PlanRec rec;
+  char* base = reinterpret_cast<char*>(uintptr_t{1} << 40);   // (no memory behind it: a dry pass only compares addresses)
+  const int64_t T = samples > 0 ? vasr_mel_frames(e, samples) : mel_frames;
+  if (samples > 0) {   // transcribe_any: every slice of the batch through transcribe_part
+    const int n = n_slices(e, batch);
+    for (int i = 0; i < n; ++i) {
+      const int nb = slice_bounds(batch, i + 1, n) - slice_bounds(batch, i, n);
+      const WsPlan p = plan_ws(e, nb, T);
+      AmaxTab enc_amax{};
+      const int32_t* own_frames = nullptr;
+      if (int rc = run_encoder(e, reinterpret_cast<float*>(base + p.melp), p.Tp0, T, reinterpret_cast<int64_t*>(base + p.seq), nb,
+                               reinterpret_cast<float*>(base + p.encp), p.Tp1, nullptr, base, p, nullptr, &enc_amax,
+                               reinterpret_cast<const int64_t*>(base), &own_frames, true, &rec))
+        return rc;
+    }
+  } else {             // vasr_encoder_f32: port tensors outside the workspace
+    const WsPlan p = plan_ws(e, batch, T);
+    const bool in_place = port_input_in_place(e);
+    float* port_in = reinterpret_cast<float*>(base + p.total + 256);
+    float* port_out = reinterpret_cast<float*>(base + p.total + 512);
+    if (int rc = run_encoder(e, in_place ? port_in : reinterpret_cast<float*>(base + p.melp), in_place ? T : p.Tp0, T,
+                             reinterpret_cast<int64_t*>(base + p.seq), batch, port_out, p.T1, nullptr, base, p, nullptr, nullptr,
+                             nullptr, nullptr, false, &rec))
+      return rc;
+  }
+  const int n = (int)(rec.v.size() / 5);
+  if (out) std::copy_n(rec.v.begin(), (size_t)std::min(n, cap) * 5, out);
+  return n;
 }
 
 int vasr_bench_ctc_head(const float* d_logits, int batch, int64_t frames, int num_classes, float* d_logp, int64_t* d_pred,

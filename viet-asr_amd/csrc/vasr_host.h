@@ -1,4 +1,5 @@
-// Host-side helpers vasr_api.cpp shares with vasr_devtools.cpp (the kernels' launch interface is vasr_internal.h).
+// Host-side helpers every host source shares (vasr_api.cpp, model_build.cpp, encoder_run.cpp, api_stages.cpp,
+// vasr_devtools.cpp) that do not need the handle -- that is vasr_model.h; the kernels' launch interface is vasr_internal.h.
 #pragma once
 #include <vector>
 

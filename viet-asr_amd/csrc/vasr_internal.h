@@ -1,4 +1,5 @@
-// Internal launch interface between vasr_api.cpp and the gfx950 kernels.
+// Internal launch interface between the host sources (vasr_api.cpp, model_build.cpp, encoder_run.cpp, api_stages.cpp) and the
+// gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -262,7 +263,7 @@ int fused_waves_choice(int kernel, bool dual, int tile_cols, int forced);
 bool fused_dwpw_supported(int channels, int cout, int kernel, int stride, int dilation);
 // Which form a 256-channel sub-block takes for `tiles128` tiles of 128 frames (batch x padded frames / 128) on `cus` free
 // compute units: 128 or 64 = the fused kernel on tiles of that many frames, 0 = depthwise and GEMM as two kernels.
-// One workgroup per CU and tile, so a launch is whole rounds of lock-stepped workgroups (measurements: vasr_api.cpp
+// One workgroup per CU and tile, so a launch is whole rounds of lock-stepped workgroups (measurements: encoder_run.cpp
 // fused_tile_cols): 128-frame tiles from 3/4 of a round up when the last round is >= 80 % full; otherwise
 // 64-frame tiles while THOSE fit one round and occupy >= 3/8 of the chip; otherwise two kernels.
 static inline int fused_tile_choice(int64_t tiles128, int cus) {
