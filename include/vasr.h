@@ -705,6 +705,36 @@ VASR_API int vasr_convolve_f32(const float* d_in, int64_t ld_in, const int64_t* 
                                const int64_t* d_ir_len, const void* d_spectra, int R, int64_t ld_ir, float* d_out,
                                int64_t ld_out, int64_t* d_len_out, vasr_stream stream);
 
+/* ---- feature masks: SpecAugment / SpecCutout (parts/spectr_augment.py) on a [batch][feat][ld] float32 feature tensor --------
+ * `x.masked_fill(mask, 0)` for a mask that is a union of rectangles.  The host draws them (viet-asr_amd/asr.py consumes Python's
+ * generator as the reference's forward does, for exact parity) and uploads them RESOLVED: d_rects [n][4] int32 = f0, f1, t0, t1,
+ * the half-open ranges [f0, f1) of feature rows and [t0, t1) of frames; d_row_begin [batch + 1] int32: batch row b owns the
+ * rectangles d_row_begin[b] .. d_row_begin[b + 1] - 1 (a CSR list; n is never given to the call -- the entries of d_row_begin
+ * must index d_rects).  No handle, no atomics, no host synchronisation, ONE launch in either form:
+ *   in place (d_out == d_in and ld_out == ld_in): the kernel only STORES +0.0f over the rectangles; it does not read the tensor,
+ *     its work is proportional to the masked area, a row without rectangles costs two dword loads per workgroup;
+ *   out of place: one pass copies d_in to d_out with the masked cells written as +0.0f (16-byte loads and stores where both
+ *     addresses allow; a pitch or a base that is no multiple of 4 cells takes dwords for the rows it misaligns).
+ * A masked cell is exactly +0.0f whatever it held (NaN, +-inf, -0.0); every other cell of [0, feat) x [0, frames) keeps its bit
+ * pattern; columns frames .. ld are never written in either form.  The kernel clips every rectangle to [0, feat) x [0, frames)
+ * and treats lo >= hi, a non-increasing d_row_begin pair and a negative d_row_begin[b] as empty: no store leaves the tensor
+ * whatever the device arrays hold.  Rectangles may overlap (all writers store the same value).  Every refusal comes before a
+ * device is touched: NULL pointers, batch / feat / frames <= 0, ld_in or ld_out < frames, a pointer that is not 4-byte aligned,
+ * and d_in / d_out ranges that overlap without being the same tensor (same pointer and pitch) return VASR_ERR_INVALID; a tensor
+ * of more than 2^31 - 1 workgroups (8 feature rows x 1024 frames each) or frames > 2^31 - 2049 returns VASR_ERR_UNSUPPORTED.
+ * tests/specaug_reference.py is the rasteriser the kernel is held to; DESIGN section 7i has the kernels.  (added within ABI 8) */
+VASR_API int vasr_spec_mask_f32(const float* d_in, int64_t ld_in, float* d_out, int64_t ld_out, int batch, int feat, int64_t frames,
+                                const int32_t* d_rects, const int32_t* d_row_begin, vasr_stream stream);
+
+/* While set, vasr_transcribe_greedy_f32 / _pcm16 run the in-place form above on the normalised log-mel features (pitch and
+ * valid frames as the call has them, feat = n_mels), behind the normalisation launch(es) and in front of the encoder: one more
+ * launch, no more memory; the first layer's operand maxima are taken from the masked tensor.  d_row_begin has batch + 1 entries
+ * for the batch of the call; with vasr_set_slices every slice applies the rows it owns.  The pointers are BORROWED until they
+ * are cleared (NULL, NULL) and must stay valid for every call enqueued in between.  With nothing set the call is what it is
+ * without this entry point: same launches, same bits.  vasr_classify_f32 is not hooked.  A NULL handle and one pointer without
+ * the other return VASR_ERR_INVALID.  (added within ABI 8) */
+VASR_API int vasr_set_feature_masks(vasr_handle* h, const int32_t* d_rects, const int32_t* d_row_begin);
+
 /* The fused call can cut the batch into `slices` contiguous parts (1..4; default 1 = off, because on MI355X it
  * measured slower: 11.7 -> 13.5 ms at 2 slices) and run each on its own
  * internal HIP stream, forked from / joined to `stream` with events: one part's HBM-bound kernels (depthwise,

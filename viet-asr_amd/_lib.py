@@ -89,6 +89,8 @@ SIGNATURES = {
     "vasr_convolve_spectra_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
     "vasr_convolve_prepare_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, C.c_size_t, _P]),
     "vasr_convolve_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int64, _P, C.c_int64, _P, _P]),
+    "vasr_spec_mask_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int64, _P, _P, _P]),
+    "vasr_set_feature_masks": (C.c_int, [_P, _P, _P]),
     "vasr_set_gemm_mode": (C.c_int, [_P, C.c_int]),
     "vasr_get_gemm_mode": (C.c_int, [_P]),
     "vasr_set_slices": (C.c_int, [_P, C.c_int]),
@@ -310,6 +312,10 @@ class Handle:
 
     def set_slices(self, n):
         check(lib().vasr_set_slices(self.h, int(n)))
+
+    def set_feature_masks(self, rects=None, row_begin=None):
+        """Device pointers (ints) of the rectangles and their CSR row table (vasr_set_feature_masks); None, None clears."""
+        check(lib().vasr_set_feature_masks(self.h, rects, row_begin))
 
     def set_row_independent(self, on):
         check(lib().vasr_set_row_independent(self.h, int(bool(on))))

@@ -21,7 +21,8 @@ from .engine import (activation_from_config, blocks_from_config, check_dense_lay
 from .frontend_tables import frontend_description
 
 __all__ = ["AudioToMelSpectrogramPreprocessor", "CropOrPadSpectrogramAugmentation", "JasperEncoder", "JasperDecoderForCTC",
-           "JasperDecoderForClassification", "GreedyCTCDecoder", "BeamSearchDecoderWithLM", "AudioDataLayer", "CTCLossNM"]
+           "JasperDecoderForClassification", "GreedyCTCDecoder", "BeamSearchDecoderWithLM", "AudioDataLayer", "CTCLossNM",
+           "SpecAugment", "SpecCutout", "SpectrogramAugmentation", "MultiplyBatch"]
 
 
 def _no_gpu():
@@ -142,6 +143,169 @@ class CropOrPadSpectrogramAugmentation(NonTrainableNM):
         offsets = self.draw_offsets(input_signal.shape[0], input_signal.shape[-1])
         image, out_len = stages.crop_or_pad(input_signal, self.audio_length, offsets)
         return image, out_len.to(device=length.device, dtype=(length * 0 + self.audio_length).dtype)
+
+
+def _resolved(a, w, n):
+    """``[a : a + w]`` on an axis of n cells as Python (and torch) resolve it, negative starts included -> (lo, hi), lo <= hi."""
+    lo, hi, _ = slice(a, a + w).indices(n)
+    return lo, max(hi, lo)
+
+
+def _check_spec(x):
+    """Refuses anything but a contiguous float32 [B, D, T] device tensor -- before a generator is consumed."""
+    if not torch.is_tensor(x) or x.device.type != "cuda":
+        raise _lib.VasrError("viet-asr_amd kernels need HIP-resident tensors; there is no CPU fallback for this path")
+    if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous():
+        raise ValueError("the spectrogram must be a contiguous float32 [B, D, T] cuda tensor")
+
+
+def _csr(rows):
+    """Per-row rectangle lists -> (rects int32 [n, 4], row_begin int32 [len(rows) + 1]), empty rectangles dropped."""
+    import numpy as np
+    rows = [[r for r in row if r[0] < r[1] and r[2] < r[3]] for row in rows]
+    begin = np.zeros(len(rows) + 1, dtype=np.int32)
+    begin[1:] = np.cumsum([len(row) for row in rows])
+    flat = [r for row in rows for r in row]
+    return np.asarray(flat, dtype=np.int32).reshape(-1, 4), begin
+
+
+class _RowMasks(nn.Module):
+    """What SpecAugment and SpecCutout share: ``forward`` draws every batch row's rectangles (``draw_row``, the subclass's) and
+    returns a new tensor with them zeroed (stages.spec_mask, the out-of-place kernel); the input is not modified."""
+
+    @torch.no_grad()
+    def forward(self, x):
+        _check_spec(x)
+        return stages.spec_mask(x, *_csr([self.draw_row(x.shape[1], x.shape[2]) for _ in range(x.shape[0])]))
+
+
+class SpecAugment(_RowMasks):
+    """nemo/collections/asr/parts/spectr_augment.py:7-56: ``freq_masks`` bands of up to ``freq_width`` feature rows and
+    ``time_masks`` stretches of up to ``time_width`` frames set to zero, per batch row.  The draws are the reference's, call for
+    call (``int(rng.uniform(0, hi))``: truncation towards zero, ``hi`` negative where the tensor is narrower than the width,
+    negative starts resolved as slices); the zeros are written on the device."""
+
+    def __init__(self, freq_masks=0, time_masks=0, freq_width=10, time_width=10, rng=None):
+        super().__init__()
+        import random
+        self._rng = random.Random() if rng is None else rng
+        self.freq_masks, self.time_masks = freq_masks, time_masks
+        self.freq_width, self.time_width = freq_width, time_width
+
+    def draw_row(self, feat, frames):
+        """One batch row's draws -> its rectangles (f0, f1, t0, t1)."""
+        out = []
+        for _ in range(self.freq_masks):
+            x_left = int(self._rng.uniform(0, feat - self.freq_width))
+            w = int(self._rng.uniform(0, self.freq_width))
+            out.append(_resolved(x_left, w, feat) + (0, frames))
+        for _ in range(self.time_masks):
+            y_left = int(self._rng.uniform(0, frames - self.time_width))
+            w = int(self._rng.uniform(0, self.time_width))
+            out.append((0, feat) + _resolved(y_left, w, frames))
+        return out
+
+
+class SpecCutout(_RowMasks):
+    """nemo/collections/asr/parts/spectr_augment.py:59-97: ``rect_masks`` rectangles set to zero per batch row.  As in the
+    reference the two widths are swapped against their names: the feature range is ``rect_x + U(0, rect_time)`` wide, the frame
+    range ``rect_y + U(0, rect_freq)``."""
+
+    def __init__(self, rect_masks=0, rect_time=5, rect_freq=20, rng=None):
+        super().__init__()
+        import random
+        self._rng = random.Random() if rng is None else rng
+        self.rect_masks, self.rect_time, self.rect_freq = rect_masks, rect_time, rect_freq
+
+    def draw_row(self, feat, frames):
+        out = []
+        for _ in range(self.rect_masks):
+            rect_x = int(self._rng.uniform(0, feat - self.rect_freq))
+            rect_y = int(self._rng.uniform(0, frames - self.rect_time))
+            w_x = int(self._rng.uniform(0, self.rect_time))
+            w_y = int(self._rng.uniform(0, self.rect_freq))
+            out.append(_resolved(rect_x, w_x, feat) + _resolved(rect_y, w_y, frames))
+        return out
+
+
+class SpectrogramAugmentation(NonTrainableNM):
+    """nemo/collections/asr/audio_preprocessing.py:522-608: SpecCutout over the whole batch, then SpecAugment over the whole
+    batch; the cutout exists only if ``rect_masks > 0``, the augment only if ``freq_masks + time_masks > 0``; one shared
+    generator when ``rng`` is given, two independent unseeded ones when it is None.  A part that does not exist is the
+    identity callable ``lambda x: x`` in ``spec_cutout`` / ``spec_augment``, as in the reference.  The tensor's width is T
+    for every row (lengths are ignored), the input is not modified.
+
+    ``draw`` is the host half -- the reference's draws, resolved to rectangles --, ``forward`` uploads them and runs the
+    out-of-place kernel (vasr_spec_mask_f32).  The engines take an instance as ``spec_augment=`` and apply the same
+    rectangles in place between the front end and the encoder (``engine.QuartzNetCTC.forward``)."""
+
+    @property
+    def input_ports(self):
+        return {"input_spec": NeuralType(("B", "D", "T"), SpectrogramType())}
+
+    @property
+    def output_ports(self):
+        return {"augmented_spec": NeuralType(("B", "D", "T"), SpectrogramType())}
+
+    def __init__(self, freq_masks=0, time_masks=0, freq_width=10, time_width=10, rect_masks=0, rect_time=5, rect_freq=20,
+                 rng=None):
+        super().__init__()
+        self.spec_cutout = self.spec_augment = lambda x: x
+        if rect_masks > 0:
+            self.spec_cutout = SpecCutout(rect_masks=rect_masks, rect_time=rect_time, rect_freq=rect_freq, rng=rng)
+        if freq_masks + time_masks > 0:
+            self.spec_augment = SpecAugment(freq_masks=freq_masks, time_masks=time_masks, freq_width=freq_width,
+                                            time_width=time_width, rng=rng)
+
+    def draw(self, batch, feat, frames, row_frames=None):
+        """The rectangles of one ``forward`` on a [batch, feat, frames] tensor -> (rects int32 [n, 4] = (f0, f1, t0, t1), half-open
+        and resolved; row_begin int32 [batch + 1]).  Host only.  The generators are consumed exactly as the reference's forward
+        consumes them: the cutout's draws for every row, then the augment's for every row.
+
+        row_frames (a list of ``batch`` frame counts): row b is drawn as a batch-1 forward on a [1, feat, row_frames[b]] tensor
+        would draw it -- cutout then augment, row after row -- which is what ``row_independent=True`` of the engines needs."""
+        rows = [[] for _ in range(batch)]
+        parts = [mod for mod in (self.spec_cutout, self.spec_augment) if isinstance(mod, _RowMasks)]
+        if row_frames is None:
+            for mod in parts:
+                for b in range(batch):
+                    rows[b] += mod.draw_row(feat, frames)
+        else:
+            if len(row_frames) != batch:
+                raise ValueError(f"row_frames needs one frame count per row ({batch}), got {len(row_frames)}")
+            for b in range(batch):
+                for mod in parts:
+                    rows[b] += mod.draw_row(feat, int(row_frames[b]))
+        return _csr(rows)
+
+    @torch.no_grad()
+    def forward(self, input_spec):
+        _check_spec(input_spec)
+        return stages.spec_mask(input_spec, *self.draw(*input_spec.shape))
+
+
+class MultiplyBatch(NonTrainableNM):
+    """nemo/collections/asr/audio_preprocessing.py:611-663: every element of the batch ``mult_batch`` times, so that later
+    augmentations draw differently for each copy.  Four ``.repeat`` calls on the tensors where they are; no kernel."""
+
+    @property
+    def input_ports(self):
+        return {"in_x": NeuralType(("B", "D", "T"), SpectrogramType()), "in_x_len": NeuralType(tuple("B"), LengthsType()),
+                "in_y": NeuralType(("B", "D", "T"), SpectrogramType()), "in_y_len": NeuralType(tuple("B"), LengthsType())}
+
+    @property
+    def output_ports(self):
+        return {"out_x": NeuralType(("B", "D", "T"), SpectrogramType()), "out_x_len": NeuralType(tuple("B"), LengthsType()),
+                "out_y": NeuralType(("B", "D", "T"), SpectrogramType()), "out_y_len": NeuralType(tuple("B"), LengthsType())}
+
+    def __init__(self, mult_batch=1):
+        super().__init__()
+        self.mult = mult_batch
+
+    @torch.no_grad()
+    def forward(self, in_x, in_x_len, in_y, in_y_len):
+        return (in_x.repeat(self.mult, 1, 1), in_x_len.repeat(self.mult), in_y.repeat(self.mult, 1),
+                in_y_len.repeat(self.mult))
 
 
 class _MaskedConvParams(nn.Module):

@@ -75,13 +75,29 @@ def builtin(name):
         body, labels = _jasper10x5dr(), LABELS_EN
     else:
         raise ValueError(f"unknown builtin model {name!r}")
-    return {
+    d = {
         "model": name.replace(".yaml", ""),
         "AudioToTextDataLayer": {"max_duration": 16.7, "trim_silence": trim},
         "AudioToMelSpectrogramPreprocessor": dict(_PRE),
         "JasperEncoder": {"activation": "relu", "conv_mask": True, "jasper": body},
         "labels": list(labels),
     }
+    if d["model"] in _SPEC_AUGMENT:
+        d["SpectrogramAugmentation"] = dict(_SPEC_AUGMENT[d["model"]])
+    return d
+
+
+# the SpectrogramAugmentation section of every shipped YAML (quartznet15x5.yaml:28-31, quartznet12x1.yaml:25-28,
+# quartznet12x1_vi.yaml:20-23): constructor arguments of asr.SpectrogramAugmentation
+_SPEC_AUGMENT = {name: {"rect_masks": 5, "rect_time": 120, "rect_freq": 50}
+                 for name in ("quartznet15x5", "quartznet12x1", "quartznet12x1_vi")}
+
+
+def spectrogram_augmentation(name):
+    """The ``SpectrogramAugmentation`` section of the shipped config of that name (a new dict), or None where the reference
+    ships none (jasper10x5dr)."""
+    model = builtin(name)["model"]          # (unknown names: ValueError)
+    return dict(_SPEC_AUGMENT[model]) if model in _SPEC_AUGMENT else None
 
 
 def jasper_definition(jasper, labels=None):

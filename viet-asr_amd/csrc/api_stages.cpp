@@ -182,6 +182,32 @@ int vasr_crop_or_pad_f32(const float* d_in, int batch, int feat, int64_t frames,
   return 0;
 }
 
+// SpecAugment / SpecCutout rectangles (spec_augment.hip)
+int vasr_spec_mask_f32(const float* d_in, int64_t ld_in, float* d_out, int64_t ld_out, int batch, int feat, int64_t frames,
+                       const int32_t* d_rects, const int32_t* d_row_begin, vasr_stream stream) {
+  // every refusal comes before a device is touched
+  if (!d_in || !d_out || !d_rects || !d_row_begin) return fail(VASR_ERR_INVALID, "spec_mask: NULL pointer");
+  if (batch <= 0 || feat <= 0 || frames <= 0 || ld_in < frames || ld_out < frames)
+    return fail(VASR_ERR_INVALID, "spec_mask: batch %d, feat %d, frames %lld, ld_in %lld, ld_out %lld (all >= 1, ld >= frames)", batch,
+                feat, (long long)frames, (long long)ld_in, (long long)ld_out);
+  if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 3)
+    return fail(VASR_ERR_INVALID, "spec_mask: d_in and d_out must be 4-byte aligned");
+  if (d_in != d_out || ld_in != ld_out) {
+    // the bytes either tensor spans up to the last row's valid frames (in doubles: the products of refused sizes do not wrap)
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
+    const double rows = (double)batch * feat - 1.0;
+    const double ea = (double)a + 4.0 * (rows * (double)ld_in + (double)frames);
+    const double eb = (double)b + 4.0 * (rows * (double)ld_out + (double)frames);
+    if (d_in == d_out || ((double)a < eb && (double)b < ea))
+      return fail(VASR_ERR_INVALID, "spec_mask: d_in and d_out overlap without being the same tensor (same pointer and pitch)");
+  }
+  if (!spec_mask_grid_fits(batch, feat, frames))
+    return fail(VASR_ERR_UNSUPPORTED, "spec_mask: batch %d x feat %d x frames %lld needs more workgroups than one launch holds", batch,
+                feat, (long long)frames);
+  launch_spec_mask(d_in, ld_in, d_out, ld_out, batch, feat, (int)frames, d_rects, d_row_begin, static_cast<hipStream_t>(stream));
+  return check_launch("spec_mask");
+}
+
 int vasr_pcm16_to_f32(const int16_t* d_pcm, int64_t n, float* d_out, vasr_stream stream) {
   if (!d_pcm || !d_out || n < 0) return fail(VASR_ERR_INVALID, "bad argument");
   if (n == 0) return 0;

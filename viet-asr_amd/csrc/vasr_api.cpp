@@ -311,9 +311,10 @@ int vasr_decoder_logsoftmax_f32(vasr_handle* h, const float* d_enc, int batch, i
 }
 
 // One contiguous slice of the batch through the whole path on one stream.
+// row0: the slice's first row in the whole batch (the feature masks' row_begin is indexed by it).
 static int transcribe_part(vasr_handle* h, const void* d_wav, bool pcm16, const int64_t* d_len, int batch, int64_t samples,
                            int64_t* d_pred, int32_t* d_ids, int32_t* d_id_len, float* d_logp, float* d_enc_len,
-                           char* ws, hipStream_t st) {
+                           char* ws, hipStream_t st, int row0 = 0) {
   const int64_t T = vasr_mel_frames(h, samples);
   const WsPlan p = plan_ws(h, batch, T);
   int64_t* seq = reinterpret_cast<int64_t*>(ws + p.seq);
@@ -332,6 +333,13 @@ static int transcribe_part(vasr_handle* h, const void* d_wav, bool pcm16, const 
                            h->d_steps, (int)h->steps.size(), reinterpret_cast<int32_t*>(ws + p.lens_tab), d_enc_len,
                            h->row_independent ? d_len : nullptr, (int)p.T1, st);
     if (h->fe.normalize == 2) launch_normalize_all(melp, p.Tp0, seq, batch, h->fe.n_mels, (int)T, st);
+  }
+  if (h->mask_rects) {
+    // vasr_set_feature_masks: one launch that only stores zeros over this slice's rectangles, behind the normalisation (the
+    // reference masks the preprocessor's output) and in front of run_encoder, which takes the first layer's operand maxima from
+    // the tensor as it then is (launch_amax inside the pass; no kernel in front of it publishes any)
+    ProfScope ps(h, kProfFrontend, st);
+    launch_spec_mask(melp, p.Tp0, melp, p.Tp0, batch, h->fe.n_mels, (int)T, h->mask_rects, h->mask_row_begin + row0, st);
   }
   AmaxTab enc_amax{};
   const int32_t* own_frames = nullptr;
@@ -369,6 +377,9 @@ static int transcribe_any(vasr_handle* h, const void* d_wav, bool pcm16, const i
   const int64_t T = vasr_mel_frames(h, samples);
   const size_t need_bytes = sliced_workspace_bytes(h, batch, T);
   if (ws_bytes < need_bytes) return fail(VASR_ERR_WORKSPACE, "workspace %zu < %zu bytes", ws_bytes, need_bytes);
+  if (h->mask_rects && !spec_mask_grid_fits(batch, h->fe.n_mels, T))
+    return fail(VASR_ERR_UNSUPPORTED, "feature masks: batch %d x %lld frames needs more workgroups than one launch holds", batch,
+                (long long)T);
   hipStream_t user = static_cast<hipStream_t>(stream);
   char* ws = static_cast<char*>(d_ws);
   const int n = n_slices(h, batch);
@@ -395,7 +406,7 @@ static int transcribe_any(vasr_handle* h, const void* d_wav, bool pcm16, const i
                              d_pred ? d_pred + (int64_t)lo * T1 : nullptr, d_ids ? d_ids + (int64_t)lo * T1 : nullptr,
                              d_id_len ? d_id_len + lo : nullptr,
                              d_logp ? d_logp + (int64_t)lo * T1 * h->num_classes : nullptr,
-                             d_enc_len ? d_enc_len + lo : nullptr, ws + off, st);
+                             d_enc_len ? d_enc_len + lo : nullptr, ws + off, st, lo);
     if (rc) return rc;
     off += align_up(plan_ws(h, hi - lo, T).total, 256);
     HIP_TRY(hipEventRecord(h->slice_done[i], st));
@@ -521,6 +532,15 @@ int vasr_set_busy_cus(vasr_handle* h, int cus) {
 int vasr_set_row_independent(vasr_handle* h, int on) {
   if (!h) return fail(VASR_ERR_INVALID, "null handle");
   h->row_independent = on != 0;
+  return 0;
+}
+
+int vasr_set_feature_masks(vasr_handle* h, const int32_t* d_rects, const int32_t* d_row_begin) {
+  if (!h) return fail(VASR_ERR_INVALID, "null handle");
+  if ((d_rects == nullptr) != (d_row_begin == nullptr))
+    return fail(VASR_ERR_INVALID, "feature masks: d_rects and d_row_begin are set together, or both NULL to clear");
+  h->mask_rects = d_rects;
+  h->mask_row_begin = d_row_begin;
   return 0;
 }
 

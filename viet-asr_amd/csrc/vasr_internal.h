@@ -462,6 +462,20 @@ int launch_convolve_prepare(const float* ir, int64_t ld_ir, const int64_t* ir_le
 void launch_convolve(const float* in, int64_t ld_in, const int64_t* len, int batch, const int32_t* ir_row, const int64_t* ir_len,
                      const void* spectra, int R, int64_t ld_ir, float* out, int64_t ld_out, int64_t* len_out, hipStream_t st);
 
+// ---- SpecAugment / SpecCutout (spec_augment.hip): rectangles of a [B][feat][ld] tensor set to +0.0f; include/vasr.h has the
+// semantics.  in == out selects the form that only stores; the caller checks every argument (spec_mask_grid_fits too). ----
+constexpr int kSpecBlock = 256;   // threads per workgroup: kSpecRows feature rows x 32 lanes
+constexpr int kSpecRows = 8;      // feature rows per workgroup, both forms
+constexpr int kSpecTile = 1024;   // frames per workgroup of the out-of-place form: 4 per thread
+constexpr int kSpecChunk = 256;   // rectangles staged in LDS at a time (out-of-place form), at most kSpecBlock
+inline bool spec_mask_grid_fits(int batch, int feat, int64_t frames) {
+  if (frames > INT32_MAX - 2 * kSpecTile) return false;   // a thread's frame indices reach less than 2 tiles past `frames`
+  const int64_t f_tiles = ((int64_t)feat + kSpecRows - 1) / kSpecRows, t_tiles = (frames + kSpecTile - 1) / kSpecTile;
+  return (int64_t)batch * f_tiles <= INT32_MAX / t_tiles;
+}
+void launch_spec_mask(const float* in, int64_t ld_in, float* out, int64_t ld_out, int batch, int feat, int frames,
+                      const int32_t* rects, const int32_t* row_begin, hipStream_t st);
+
 // ---- beam search (beam_wave.hip, beam_group.hip) ----
 struct BeamLm {  // device-resident hashed back-off n-gram model
   const void* vocab; int vcap;    // [vcap] 16-byte entries {u64 word hash | 1, i32 word id, u32 flags}, vcap a power of two

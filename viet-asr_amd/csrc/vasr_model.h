@@ -175,6 +175,10 @@ struct vasr_handle {
   bool plan_only = false;         // vasr_plan_buffers' host-side shadow of an unfinalized handle: upload() allocates nothing
   bool row_independent = false;   // vasr_set_row_independent
   int busy_cus = 0;               // vasr_set_busy_cus
+  // vasr_set_feature_masks: borrowed device arrays, rectangles of the normalised features zeroed in front of the encoder
+  // (spec_augment.hip); nullptr: the fused call is what it is without them
+  const int32_t* mask_rects = nullptr;
+  const int32_t* mask_row_begin = nullptr;
   vasr::DevSwitches sw = vasr::dev_switches();   // kernel-selection switches of the devtools build (vasr_internal.h); defaults in the product
   int n_cu = 256;                 // compute units of the device the handle was finalized on (tile-fill decisions)
   hipStream_t slice_stream[vasr::kMaxSlices] = {};

@@ -12,6 +12,7 @@ import torch
 from . import _lib
 from .audio import pcm16_to_float, trim_silence as trim_audio
 from .frontend_tables import frontend_description
+from .stages import upload_masks
 
 
 def _stream_ptr():
@@ -225,7 +226,7 @@ class QuartzNetCTC:
         return t.to(torch.int32)
 
     def forward(self, wav, length, want_logp=False, want_pred=True, row_independent=False, trim_silence=False,
-                _trim_buffers=None, augmentor=None, _lengths_host=None):
+                _trim_buffers=None, augmentor=None, _lengths_host=None, spec_augment=None):
         """wav [B, L] f32 cuda (rows zero padded) -- or int16 PCM as it sits in a wav file: the front end scales it by 2^-15 as
         it reads it (vasr_transcribe_greedy_pcm16; the same bits as converting first) --, length [B] i64 cuda.
 
@@ -249,6 +250,15 @@ class QuartzNetCTC:
         The parameters are drawn on the host from the rows' lengths (with trim_silence they are read back from the device: one
         synchronisation).  An impulse response makes the batch wider: every frame count then follows the new width, and the dict
         carries "length" [B] i64, the perturbed lengths.
+
+        spec_augment: an ``asr.SpectrogramAugmentation`` (None: nothing changes -- the same launches, the same bits).  Its
+        rectangles are drawn on the host for the [B, n_mels, T] feature tensor of this call, T from the final padded width (after
+        the trim and ``augmentor``), uploaded without synchronising and zeroed in place between the front end's normalisation
+        and the encoder (vasr_set_feature_masks: one more launch, no more memory), which is where the reference's DAG puts the
+        module.  With row_independent=True row b is drawn as a batch-1 call on it alone would draw it -- over its own
+        ``1 + length[b] // hop`` frames, cutout then augment, row after row -- so that its transcript equals that call's with the
+        generator in the same state.  That needs the lengths on the host: where they exist only on the device (trim_silence, an
+        ``augmentor``, or a direct call of this method) it costs one read-back, the synchronisation ``augmentor`` already costs.
         """
         if wav.device.type != "cuda" or wav.dtype not in (torch.float32, torch.int16) or not wav.is_contiguous():
             raise ValueError("wav must be a contiguous float32 (or int16 PCM) cuda tensor")
@@ -275,12 +285,24 @@ class QuartzNetCTC:
         if bool(row_independent) != self._row_independent:
             self.handle.set_row_independent(row_independent)
             self._row_independent = bool(row_independent)
+        masks = None
+        if spec_augment is not None:
+            row_frames = None
+            if row_independent:
+                on_host = _lengths_host is not None and not trim_silence and augmentor is None
+                row_frames = [1 + int(n) // self.hop for n in (_lengths_host if on_host else length.cpu().tolist())]
+            masks = upload_masks(*spec_augment.draw(B, self.frontend["n_mels"], self.frames(L)[0], row_frames), dev)
+            self.handle.set_feature_masks(masks[0].data_ptr(), masks[1].data_ptr())
         entry = _lib.lib().vasr_transcribe_greedy_pcm16 if wav.dtype == torch.int16 else _lib.lib().vasr_transcribe_greedy_f32
-        _lib.check(entry(
-            self.handle.h, wav.data_ptr(), length.data_ptr(), B, L,
-            pred.data_ptr() if pred is not None else None, ids.data_ptr(), id_len.data_ptr(),
-            logp.data_ptr() if logp is not None else None, enc_len.data_ptr(),
-            ws.data_ptr(), ws.numel(), _stream_ptr()))
+        try:
+            _lib.check(entry(
+                self.handle.h, wav.data_ptr(), length.data_ptr(), B, L,
+                pred.data_ptr() if pred is not None else None, ids.data_ptr(), id_len.data_ptr(),
+                logp.data_ptr() if logp is not None else None, enc_len.data_ptr(),
+                ws.data_ptr(), ws.numel(), _stream_ptr()))
+        finally:
+            if masks is not None:       # borrowed for this call only: the next one is unmasked again
+                self.handle.set_feature_masks(None, None)
         r = dict(ids=ids, id_len=id_len, pred=pred, enc_len=enc_len, logp=logp)
         if trim_start is not None:
             r["trim_start"], r["length"] = trim_start, length
@@ -296,17 +318,19 @@ class QuartzNetCTC:
             raise _lib.VasrError("beam search reported an internal overflow (id_len = -1) for rows %s" % (n < 0).nonzero()[0].tolist())
         return ["".join(self.labels[c] for c in ids[b, : n[b]]) for b in range(ids.shape[0])]
 
-    def transcribe(self, signals, row_independent=False, trim_silence=False, augmentor=None):
+    def transcribe(self, signals, row_independent=False, trim_silence=False, augmentor=None, spec_augment=None):
         """List of 1-D arrays (model sample rate; float, or int16 PCM) -> list of strings; zero-pad-to-max collate
-        (parts/dataset.py:14-53).  row_independent, trim_silence, augmentor: see forward()."""
-        return self.launch(signals, row_independent, trim_silence=trim_silence, augmentor=augmentor).texts()
+        (parts/dataset.py:14-53).  row_independent, trim_silence, augmentor, spec_augment: see forward()."""
+        return self.launch(signals, row_independent, trim_silence=trim_silence, augmentor=augmentor,
+                           spec_augment=spec_augment).texts()
 
-    def transcribe_beam(self, signals, beam_decoder, beam_width, row_independent=True, trim_silence=False, augmentor=None):
+    def transcribe_beam(self, signals, beam_decoder, beam_width, row_independent=True, trim_silence=False, augmentor=None,
+                        spec_augment=None):
         """Batched counterpart of the reference's beam wiring (infer.py:132-139, 159-160; batch 1 there): one forward
         pass for the log-probs, then viet_asr_amd.beam.BeamSearchDecoder over every row.  row_independent=True searches
         each row over its own frames (and reflects it at its own end): the transcripts of batch-1 calls.  trim_silence: see
         forward(); the rows' own frames then come from the trimmed lengths, on the device.  augmentor: see forward(); the
-        rows' own frames come from the perturbed lengths."""
+        rows' own frames come from the perturbed lengths.  spec_augment: see forward()."""
         lens = [len(s) for s in signals]
         if row_independent and min(lens) <= self.frontend["n_fft"] // 2:
             raise ValueError(f"row-independent batching needs more than n_fft/2 = {self.frontend['n_fft'] // 2} samples "
@@ -316,7 +340,7 @@ class QuartzNetCTC:
             batch[i, : lens[i]] = _pcm_to_float(s)
         r = self.forward(torch.from_numpy(batch).to(self.device), torch.tensor(lens, device=self.device),
                          want_logp=True, want_pred=False, row_independent=row_independent, trim_silence=trim_silence,
-                         augmentor=augmentor, _lengths_host=lens)
+                         augmentor=augmentor, _lengths_host=lens, spec_augment=spec_augment)
         own = [self.frames(n)[1] for n in lens] if row_independent else None
         if row_independent and (trim_silence or augmentor is not None):
             own = self.frames_of(r["length"])
@@ -448,7 +472,8 @@ class QuartzNetCTC:
         return lf
 
     # -- pipelined host path: pinned staging, copies on their own stream, two batches in flight
-    def launch(self, signals, row_independent=False, after_forward=None, trim_silence=False, augmentor=None):
+    def launch(self, signals, row_independent=False, after_forward=None, trim_silence=False, augmentor=None,
+               spec_augment=None):
         """Enqueue one batch and return at once; ``.texts()`` of the returned PendingBatch waits for it.
 
         Two staging slots alternate: while batch k computes, batch k+1 is collated into pinned memory and its
@@ -462,6 +487,7 @@ class QuartzNetCTC:
 
         trim_silence: see forward(); the slot keeps a second device buffer for the trimmed batch and one for the starts.
         augmentor: see forward(); the staging for the ids is sized by ``augmentor.max_augmentation_length``.
+        spec_augment: see forward(); the rectangles are drawn here, on the host, while the previous batch computes.
         """
         if len(signals) == 0:
             raise ValueError("empty batch")
@@ -470,7 +496,7 @@ class QuartzNetCTC:
             self._copy_stream = torch.cuda.Stream(self.device)
         slot = self._slots[self._launched % 2]
         self._launched += 1
-        return slot.launch(signals, row_independent, after_forward, trim_silence, augmentor)
+        return slot.launch(signals, row_independent, after_forward, trim_silence, augmentor, spec_augment)
 
 
 class QuartzNetClassifier:
@@ -710,7 +736,8 @@ class _Slot:
         if self.pin_ids is None or self.pin_ids.numel() < B * t1:
             self.pin_ids = torch.empty(B * t1, dtype=torch.int32, pin_memory=True)
 
-    def launch(self, signals, row_independent=False, after_forward=None, trim_silence=False, augmentor=None):
+    def launch(self, signals, row_independent=False, after_forward=None, trim_silence=False, augmentor=None,
+               spec_augment=None):
         eng = self.eng
         if self.pending is not None:
             self.pending.texts()          # the slot's previous batch: fetch before its buffers are overwritten
@@ -755,7 +782,7 @@ class _Slot:
             # (int16 PCM goes into the front end as it is: scaled by 2^-15 in the STFT kernel's staging load)
             self.out = eng.forward(wav, self.dev_len[:B], want_pred=False, row_independent=row_independent,
                                    trim_silence=trim_silence, _trim_buffers=trim_buffers, augmentor=augmentor,
-                                   _lengths_host=lens)
+                                   _lengths_host=lens, spec_augment=spec_augment)
             t1 = self.out["ids"].shape[1]  # the width the batch got (an impulse response widens it)
             if after_forward is not None:
                 after_forward(self.out)

@@ -132,11 +132,22 @@ class VietASR:
                 return signals                      # int16 PCM goes to the device as it is (scaled there)
         return [self._to_model_rate(s, sample_rate) for s in signals]
 
+    def spectrogram_augmentation(self, rng=None):
+        """The ``asr.SpectrogramAugmentation`` of the model definition's section of that name (every shipped YAML has one:
+        ``rect_masks: 5, rect_time: 120, rect_freq: 50``, and ``configs.builtin`` carries it) -- what ``spec_augment=`` of the
+        calls below takes; no section: ValueError.
+        rng: a ``random.Random`` for reproducible draws (None: unseeded, as the reference constructs it)."""
+        from .asr import SpectrogramAugmentation
+        section = self.model_definition.get("SpectrogramAugmentation")
+        if section is None:
+            raise ValueError("the model definition has no SpectrogramAugmentation section")
+        return SpectrogramAugmentation(rng=rng, **section)
+
     def _trim(self, trim_silence):
         return resolve_trim_silence(trim_silence, self.model_definition)
 
     def transcribe_batch(self, signals, sample_rate=None, row_independent=False, decoder="greedy", trim_silence=False,
-                         augmentor=None):
+                         augmentor=None, spec_augment=None):
         """Transcripts of a list of 1-D signals through the fused one-call path.  row_independent=True: every
         transcript is what the signal alone would give (engine.QuartzNetCTC.forward); default: the reference's
         padded-batch semantics.  decoder="beam" (instances built with decoder="beam" only) runs this instance's beam
@@ -147,16 +158,20 @@ class VietASR:
         and in front of the front end, as ``AudioSegment(trim=True)`` does (segment.py:24-28; ``audio.trim_silence``).
 
         augmentor: a ``perturb.AudioAugmentor`` (None: nothing changes), applied on the device after the trim and in front of
-        the front end (``engine.QuartzNetCTC.forward``)."""
+        the front end (``engine.QuartzNetCTC.forward``).
+
+        spec_augment: an ``asr.SpectrogramAugmentation`` (None: nothing changes; ``spectrogram_augmentation()`` builds the model
+        definition's), whose rectangles are zeroed in the normalised features on the device, between the front end and the
+        encoder (``engine.QuartzNetCTC.forward``)."""
         trim = self._trim(trim_silence)
         if decoder == "greedy":
             return self._fused_engine().transcribe(self._batch_signals(signals, sample_rate), row_independent, trim_silence=trim,
-                                                   augmentor=augmentor)
+                                                   augmentor=augmentor, spec_augment=spec_augment)
         if decoder != "beam" or self.mode != "beam":
             raise ValueError("decoder must be 'greedy', or 'beam' on an instance constructed with decoder='beam'")
         sigs = [self._to_model_rate(s, sample_rate) for s in signals]
         return self._fused_engine().transcribe_beam(sigs, self.beam.decoder, self.beam.beam_width, row_independent,
-                                                    trim_silence=trim, augmentor=augmentor)
+                                                    trim_silence=trim, augmentor=augmentor, spec_augment=spec_augment)
 
     def _manifest_batches(self, manifest_filepath, batch_size):
         """-> (the entries of a NeMo JSON-lines manifest, or of several separated by commas; a generator of (idx, signals): the
@@ -180,7 +195,7 @@ class VietASR:
         return entries, batches()
 
     def _walk_manifest(self, manifest_filepath, batch_size, row_independent, after_forward=None, trim_silence=False,
-                       augmentor=None):
+                       augmentor=None, spec_augment=None):
         """The entries of a NeMo JSON-lines manifest and their greedy transcripts, in manifest order: sorted by duration, cut
         into batches of ``batch_size``, two batches in flight (engine.QuartzNetCTC.launch).  after_forward(entries, idx) -> the
         ``launch`` hook of the batch holding entries ``idx`` (or None)."""
@@ -195,14 +210,15 @@ class VietASR:
         for idx, sigs in batches:
             hook = after_forward(entries, idx) if after_forward is not None else None
             pending.append((idx, self._fused_engine().launch(sigs, row_independent, hook, trim_silence=trim_silence,
-                                                             augmentor=augmentor)))
+                                                             augmentor=augmentor, spec_augment=spec_augment)))
             if len(pending) == 2:
                 collect(pending.pop(0))
         for job in pending:
             collect(job)
         return entries, hyps
 
-    def transcribe_manifest(self, manifest_filepath, batch_size=64, row_independent=True, trim_silence=False, augmentor=None):
+    def transcribe_manifest(self, manifest_filepath, batch_size=64, row_independent=True, trim_silence=False, augmentor=None,
+                            spec_augment=None):
         """Greedy transcripts of every entry of a NeMo JSON-lines manifest (parts/manifest.py:21-94), in manifest order,
         plus the word error rate against the entries' ``text`` (None when no entry has one).
 
@@ -213,11 +229,11 @@ class VietASR:
 
         The rate is ``data_layer.word_error_rate`` on the RAW manifest text, computed on the host after the last batch.
         ``evaluate_manifest`` scores the parsed tokens on the device instead (WER and CER); the two word error rates
-        differ only where a reference contains characters outside the labels.  trim_silence, augmentor: as
+        differ only where a reference contains characters outside the labels.  trim_silence, augmentor, spec_augment: as
         ``transcribe_batch``; the rows draw their perturbations in batch order (sorted by duration)."""
         from .data_layer import word_error_rate
         entries, hyps = self._walk_manifest(manifest_filepath, batch_size, row_independent, trim_silence=self._trim(trim_silence),
-                                            augmentor=augmentor)
+                                            augmentor=augmentor, spec_augment=spec_augment)
         refs = [e.get("text") for e in entries]
         scored = [i for i, r in enumerate(refs) if r]
         wer = word_error_rate([hyps[i] for i in scored], [refs[i] for i in scored]) if scored else None
@@ -236,7 +252,7 @@ class VietASR:
         return ref, ref_len
 
     def evaluate_manifest(self, manifest_filepath, batch_size=64, row_independent=True, breakdown=False, nbest=None,
-                          eval_loss=False, trim_silence=False, augmentor=None):
+                          eval_loss=False, trim_silence=False, augmentor=None, spec_augment=None):
         """``transcribe_manifest``'s walk with WER and CER scored on the device: -> (hyps, ``ErrorRate.compute()``), the
         dict {"wer", "cer", "word_edits", "ref_words", "char_edits", "ref_chars"}.
 
@@ -267,17 +283,19 @@ class VietASR:
         ``forward(want_logp=True)``; it cannot be combined with ``nbest`` (ValueError).
 
         trim_silence: as ``transcribe_batch``, in every form; "config" scores what the reference's evaluation with this model
-        definition would have scored (quartznet15x5.yaml trims every clip).  augmentor: as ``transcribe_manifest``, in every form."""
+        definition would have scored (quartznet15x5.yaml trims every clip).  augmentor, spec_augment: as
+        ``transcribe_manifest``, in every form."""
         from .metrics import ErrorBreakdown, ErrorRate
         metric = (ErrorBreakdown if breakdown else ErrorRate)(self.labels)
         trim = self._trim(trim_silence)
         if eval_loss:
             if nbest is not None:
                 raise ValueError("eval_loss=True cannot be combined with nbest")
-            return self._evaluate_manifest_loss(manifest_filepath, batch_size, row_independent, metric, trim, augmentor)
+            return self._evaluate_manifest_loss(manifest_filepath, batch_size, row_independent, metric, trim, augmentor,
+                                                spec_augment)
         if nbest is not None:
             return self._evaluate_manifest_nbest(manifest_filepath, batch_size, row_independent, metric, int(nbest), trim,
-                                                 augmentor)
+                                                 augmentor, spec_augment)
         keep = []                   # pinned reference batches, alive until the copies that read them have run
 
         def after_forward(entries, idx):
@@ -298,11 +316,11 @@ class VietASR:
             return score
 
         _, hyps = self._walk_manifest(manifest_filepath, batch_size, row_independent, after_forward, trim_silence=trim,
-                                      augmentor=augmentor)
+                                      augmentor=augmentor, spec_augment=spec_augment)
         return hyps, metric.compute()
 
     def _evaluate_manifest_nbest(self, manifest_filepath, batch_size, row_independent, metric, nbest, trim_silence=False,
-                                 augmentor=None):
+                                 augmentor=None, spec_augment=None):
         from .engine import _pcm_to_float
         from .metrics import OracleErrorRate
         if self.mode != "beam":
@@ -320,7 +338,7 @@ class VietASR:
                 batch[k, : lens[k]] = _pcm_to_float(s)
             r = eng.forward(torch.from_numpy(batch).to(eng.device), torch.tensor(lens, device=eng.device), want_logp=True,
                             want_pred=False, row_independent=row_independent, trim_silence=trim_silence, augmentor=augmentor,
-                            _lengths_host=lens)
+                            _lengths_host=lens, spec_augment=spec_augment)
             own = [eng.frames(n)[1] for n in lens] if row_independent else None
             if row_independent and (trim_silence or augmentor is not None):
                 own = eng.frames_of(r["length"])
@@ -339,11 +357,12 @@ class VietASR:
         res["oracle_wer"], res["oracle_cer"] = best["oracle_wer"], best["oracle_cer"]
         return hyps, res
 
-    def _forward_logp(self, sigs, row_independent, trim_silence=False, augmentor=None):
+    def _forward_logp(self, sigs, row_independent, trim_silence=False, augmentor=None, spec_augment=None):
         """One zero-padded batch of signals at the model's rate through ``forward(want_logp=True)`` -> (its result dict, the
         frames of every row [B] on the device: the row's own encoded frames when row_independent, otherwise the encoder's
         lengths of the padded batch).  trim_silence: the rows are trimmed on the device first (the dict then has "trim_start"
-        and "length") and a row's own frames follow its trimmed length, computed there.  augmentor: likewise, behind the trim."""
+        and "length") and a row's own frames follow its trimmed length, computed there.  augmentor: likewise, behind the trim.
+        spec_augment: see ``engine.QuartzNetCTC.forward``."""
         from .engine import _pcm_to_float
         eng = self._fused_engine()
         lens = [len(s) for s in sigs]
@@ -354,7 +373,8 @@ class VietASR:
         for k, s in enumerate(sigs):
             batch[k, : lens[k]] = _pcm_to_float(s)
         r = eng.forward(torch.from_numpy(batch).to(eng.device), torch.tensor(lens, device=eng.device), want_logp=True,
-                        row_independent=row_independent, trim_silence=trim_silence, augmentor=augmentor, _lengths_host=lens)
+                        row_independent=row_independent, trim_silence=trim_silence, augmentor=augmentor, _lengths_host=lens,
+                        spec_augment=spec_augment)
         if row_independent and (trim_silence or augmentor is not None):
             frames = eng.frames_of(r["length"])
         elif row_independent:
@@ -364,13 +384,13 @@ class VietASR:
         return r, frames
 
     def _evaluate_manifest_loss(self, manifest_filepath, batch_size, row_independent, metric, trim_silence=False,
-                                augmentor=None):
+                                augmentor=None, spec_augment=None):
         from .metrics import CTCEvalLoss
         eng, loss = self._fused_engine(), CTCEvalLoss(len(self.labels))
         entries, batches = self._manifest_batches(manifest_filepath, batch_size)
         hyps = [None] * len(entries)
         for idx, sigs in batches:
-            r, frames = self._forward_logp(sigs, row_independent, trim_silence, augmentor)
+            r, frames = self._forward_logp(sigs, row_independent, trim_silence, augmentor, spec_augment)
             rows = [k for k, i in enumerate(idx) if entries[i].get("text")]
             if rows:
                 ref, ref_len = self._reference_tokens(entries, [idx[k] for k in rows])
@@ -387,20 +407,21 @@ class VietASR:
         res.update(loss.compute())
         return hyps, res
 
-    def score(self, signals, texts, sample_rate=None, row_independent=True, trim_silence=False, augmentor=None):
+    def score(self, signals, texts, sample_rate=None, row_independent=True, trim_silence=False, augmentor=None,
+              spec_augment=None):
         """log P(text | audio) of every (signal, text) pair -> a list of Python floats, minus the CTC loss of the row
         (``stages.ctc_loss`` on the batch's log-probs, over each row's own encoded frames): the forced score of ANY
         transcript -- a reference, or a greedy or beam hypothesis as a sequence confidence or for rescoring.  The texts go
         through the character parser the references go through (characters outside the labels are dropped).  A text that
         has no path through its audio (more tokens, counting one more per repeated character, than frames) scores -inf.
         row_independent (default): every score is what the signal alone would give.  One synchronisation.  trim_silence: as
-        ``transcribe_batch``.  augmentor: as ``transcribe_batch``."""
+        ``transcribe_batch``.  augmentor, spec_augment: as ``transcribe_batch``."""
         signals, texts = list(signals), list(texts)
         if len(signals) != len(texts) or not signals:
             raise ValueError(f"score needs as many texts as signals, and at least one (got {len(signals)} and {len(texts)})")
         eng = self._fused_engine()
         r, frames = self._forward_logp([self._to_model_rate(s, sample_rate) for s in signals], row_independent,
-                                       self._trim(trim_silence), augmentor)
+                                       self._trim(trim_silence), augmentor, spec_augment)
         ref, ref_len = self._reference_tokens([{"text": t} for t in texts], range(len(texts)))
         from . import stages
         loss = stages.ctc_loss(r["logp"], frames, ref.to(eng.device), ref_len.to(eng.device), len(self.labels))
@@ -409,7 +430,8 @@ class VietASR:
             raise RuntimeError("the CTC score came back NaN for rows %s" % [k for k, v in enumerate(host) if v != v])
         return [-v for v in host]
 
-    def align(self, signals, texts=None, sample_rate=None, row_independent=True, trim_silence=False, augmentor=None):
+    def align(self, signals, texts=None, sample_rate=None, row_independent=True, trim_silence=False, augmentor=None,
+              spec_augment=None):
         """Character and word time spans of every (signal, text) pair: the forced (Viterbi) alignment of the text to the
         batch's log-probs (``stages.ctc_align``, over each row's own encoded frames) -> per row a dict {"text", "score",
         "chars", "words"} (``alignment_entries``): "score" is the log-probability of the best single path, at most
@@ -432,7 +454,8 @@ class VietASR:
                              f"{None if texts is None else len(texts)})")
         eng = self._fused_engine()
         trim = self._trim(trim_silence)
-        r, frames = self._forward_logp([self._to_model_rate(s, sample_rate) for s in signals], row_independent, trim, augmentor)
+        r, frames = self._forward_logp([self._to_model_rate(s, sample_rate) for s in signals], row_independent, trim, augmentor,
+                                       spec_augment)
         if texts is None:
             tgt, tgt_len = r["ids"], r["id_len"]
         else:

@@ -102,6 +102,65 @@ def crop_or_pad(input_signal, audio_length, offsets=None):
     return out, out_len
 
 
+def _feature_pitch(t, what):
+    """The row pitch of a [B, D, T] float32 tensor whose feature rows are equally spaced: a contiguous tensor (pitch T) or a
+    column slice ``wide[:, :, :T]`` of one (pitch: wide's width)."""
+    if t.dtype != torch.float32 or t.dim() != 3 or 0 in t.shape:
+        raise ValueError(f"{what} must be a non-empty [B, D, T] float32 tensor")
+    B, D, T = t.shape
+    if t.is_contiguous():
+        return T
+    ld = t.stride(1)
+    if t.stride(2) != 1 or ld < T or t.stride(0) != D * ld:
+        raise ValueError(f"{what} must be contiguous, or a column slice of a contiguous [B, D, ld] tensor")
+    return ld
+
+
+def upload_masks(rects, row_begin, device):
+    """Host rectangles [n, 4] and row table [B + 1] (int32) -> the two device tensors, through ONE pinned staging buffer and one
+    asynchronous copy on the current stream: nothing synchronises."""
+    import numpy as np
+    rects = np.ascontiguousarray(rects, dtype=np.int32).reshape(-1, 4)
+    row_begin = np.ascontiguousarray(row_begin, dtype=np.int32).reshape(-1)
+    head = (row_begin.size + 3) // 4 * 4
+    host = torch.zeros(head + max(rects.size, 4), dtype=torch.int32).pin_memory()
+    host[: row_begin.size] = torch.from_numpy(row_begin)
+    host[head: head + rects.size] = torch.from_numpy(rects.reshape(-1))
+    dev = host.to(device, non_blocking=True)
+    return dev[head:].view(-1, 4), dev[: row_begin.size]
+
+
+def spec_mask(input_spec, rects, row_begin, out=None):
+    """SpecAugment / SpecCutout's ``x.masked_fill(mask, 0)`` for a mask that is a union of rectangles (vasr_spec_mask_f32): rects
+    [n, 4] int32 = (f0, f1, t0, t1), half-open and resolved; row_begin [B + 1] int32, row b owns rects[row_begin[b] :
+    row_begin[b + 1]] (both on the device already, or host arrays that are uploaded without synchronising).  -> a new
+    contiguous tensor, or ``out``: ``out=input_spec`` selects the form that only stores zeros over the rectangles (and returns
+    input_spec), any other ``out`` [B, D, T] receives the masked copy.  input_spec and out may be column slices of wider
+    contiguous tensors: the columns behind T are never written.  One launch."""
+    _need_cuda(input_spec)
+    ld_in = _feature_pitch(input_spec, "input_spec")
+    B, D, T = input_spec.shape
+    if not (torch.is_tensor(rects) and torch.is_tensor(row_begin)):
+        rects, row_begin = upload_masks(rects, row_begin, input_spec.device)
+    _need_cuda(rects, row_begin)
+    if rects.dtype != torch.int32 or row_begin.dtype != torch.int32 or not rects.is_contiguous() or not row_begin.is_contiguous():
+        raise ValueError("rects and row_begin must be contiguous int32 tensors")
+    if row_begin.numel() != B + 1 or rects.numel() % 4:
+        raise ValueError(f"row_begin needs {B + 1} entries (got {row_begin.numel()}), rects four per rectangle")
+    if out is None:
+        out = torch.empty((B, D, T), dtype=torch.float32, device=input_spec.device)
+    elif out is not input_spec:
+        _need_cuda(out)
+        if out.shape != input_spec.shape or out.device != input_spec.device:
+            raise ValueError("out must have input_spec's shape and device")
+    ld_out = _feature_pitch(out, "out")
+    # (an empty device tensor has no address; with no rectangle at all the list pointer is never followed)
+    rects_ptr = rects.data_ptr() if rects.numel() else row_begin.data_ptr()
+    _lib.check(_lib.lib().vasr_spec_mask_f32(input_spec.data_ptr(), ld_in, out.data_ptr(), ld_out, B, D, T, rects_ptr,
+                                             row_begin.data_ptr(), _st()))
+    return out
+
+
 def classifier(handle, encoder_output, softmax=False):
     """JasperDecoderForClassification.forward -> logits (or probabilities) [B,num_classes] f32."""
     _need_cuda(encoder_output)
