@@ -89,12 +89,9 @@ def host_handle(name):
     from viet_asr_amd import _lib, engine
     from viet_asr_amd.frontend_tables import frontend_description
     d = definition(name)
-    enc, jas = d["JasperEncoder"], d["JasperEncoder"]["jasper"]
-    act, res_mode = engine.activation_from_config(enc)
-    h = _lib.Handle(frontend=frontend_description(dict(d["AudioToMelSpectrogramPreprocessor"])), feat_in=64,
-                    blocks=engine.blocks_from_config(jas), dec_feat_in=jas[-1]["filters"], num_classes=len(d["labels"]) + 1,
-                    se=engine.se_from_config(jas), groups=engine.groups_from_config(jas),
-                    norm=engine.norm_from_config(enc, jas), activation=act, residual_mode=res_mode)
+    h = _lib.Handle(frontend=frontend_description(dict(d["AudioToMelSpectrogramPreprocessor"])),
+                    dec_feat_in=d["JasperEncoder"]["jasper"][-1]["filters"], num_classes=len(d["labels"]) + 1,
+                    **engine.handle_arguments(d["JasperEncoder"], 64))
     for sd in weights(d):
         h.load_state_dict(sd)
     return h

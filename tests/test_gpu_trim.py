@@ -190,6 +190,25 @@ def test_forward_and_launch_trim_like_the_host(gpu, tiny):
     assert eng.launch(rows, row_independent=True).texts() == eng.transcribe(rows, row_independent=True)   # the default: untrimmed
 
 
+def test_frames_of_and_frame_seconds_follow_the_library(gpu, tiny):
+    """``frames_of`` -- the frames of trimmed rows, whose lengths exist on the device only -- is the library's own chain
+    (vasr_mel_frames, vasr_encoded_frames), and ``frame_seconds`` divides by the same stride product.  No launch beyond the
+    engine's construction."""
+    from viet_asr_amd import geometry
+    from viet_asr_amd.engine import QuartzNetCTC, blocks_from_config
+    cfg, enc_sd, dec_sd = tiny
+    eng = QuartzNetCTC(cfg, enc_sd, dec_sd, device=gpu)
+    ns = [257, 319, 320, 321, 16000, 160077]
+    got = eng.frames_of(torch.tensor(ns))
+    assert got.dtype == torch.int32
+    assert got.tolist() == [eng.handle.encoded_frames(eng.handle.mel_frames(n)) for n in ns]
+    pre = cfg["AudioToMelSpectrogramPreprocessor"]
+    hop = int(round(pre["window_stride"] * pre["sample_rate"]))
+    stride = geometry.stride_product(blocks_from_config(cfg["JasperEncoder"]["jasper"]))
+    assert (hop, stride) == (160, 2)
+    assert eng.frame_seconds() == hop * stride / pre["sample_rate"]
+
+
 def test_align_reports_times_of_the_recording_it_was_given(gpu, tiny, tmp_path):
     from viet_asr_amd.infer import VietASR
     cfg, enc_sd, dec_sd = tiny

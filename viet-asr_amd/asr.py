@@ -16,9 +16,9 @@ from . import _lib, stages
 from .core import (AcousticEncodedRepresentation, AudioSignal, DataLayerNM, DeviceType, LabelsType, LengthsType,
                    LogitsType, LogprobsType, LossType, MelSpectrogramType, NeuralType, NonTrainableNM, PredictionsType,
                    SpectrogramType, TrainableNM)
-from .engine import (activation_from_config, blocks_from_config, check_dense_layout, norm_from_config, groups_from_config,
-                     se_from_config)
+from .engine import check_dense_layout, collate, handle_arguments
 from .frontend_tables import frontend_description
+from .geometry import odd_kernel
 
 __all__ = ["AudioToMelSpectrogramPreprocessor", "CropOrPadSpectrogramAugmentation", "JasperEncoder", "JasperDecoderForCTC",
            "JasperDecoderForClassification", "GreedyCTCDecoder", "BeamSearchDecoderWithLM", "AudioDataLayer", "CTCLossNM",
@@ -406,26 +406,22 @@ class JasperEncoder(_HipWeights, TrainableNM):
     def __init__(self, jasper, activation, feat_in, normalization_mode="batch", residual_mode="add", norm_groups=-1,
                  conv_mask=True, frame_splicing=1, init_mode="xavier_uniform"):
         super().__init__()
-        # one activation for every block, as the reference's one module (jasper.py:150); unknown names: KeyError
-        self._act, self._res_mode = activation_from_config(dict(activation=activation, residual_mode=residual_mode))
-        if not conv_mask or frame_splicing != 1:
+        if frame_splicing != 1:
             raise NotImplementedError("implemented: conv_mask=True, frame_splicing=1")
-        if self._res_mode and normalization_mode != "batch":
-            raise NotImplementedError("residual_mode='max' with group, instance or layer normalization is not implemented")
-        self._blocks = blocks_from_config(jasper)
-        # (unknown modes and group counts that do not divide a block's filters: ValueError, as the reference raises)
-        self._norm = norm_from_config(dict(normalization_mode=normalization_mode, norm_groups=norm_groups), jasper)
-        self._se = se_from_config(jasper)
-        self._groups = groups_from_config(jasper)
-        self._feat_in = feat_in * frame_splicing
-        check_dense_layout(self._blocks, self._feat_in)
-        for b in self._blocks:
+        # one activation for every block, as the reference's one module (jasper.py:150); unknown names: KeyError.  Unknown
+        # normalization modes and group counts that do not divide a block's filters: ValueError, as the reference raises
+        self._enc = enc = handle_arguments(dict(jasper=jasper, activation=activation, normalization_mode=normalization_mode,
+                                                residual_mode=residual_mode, norm_groups=norm_groups, conv_mask=conv_mask),
+                                           feat_in)
+        self._act, self._res_mode, blocks = enc["activation"], enc["residual_mode"], enc["blocks"]
+        check_dense_layout(blocks, feat_in)
+        for b in blocks:
             if b["stride"] > 1 and b["dilation"] > 1:
                 raise ValueError("Only stride OR dilation may be greater than 1")   # parts/jasper.py:61-62
-        layers, c = [], self._feat_in
+        layers, c = [], feat_in
         residual_panes = []     # ONE list shared by the dense blocks, copied by each (jasper.py:152-161, parts/jasper.py:264)
-        for b, se, (groups, heads), norm in zip(self._blocks, self._se, self._groups, self._norm):
-            k = b["kernel"] + (1 if b["kernel"] % 2 == 0 else 0)
+        for b, se, (groups, heads), norm in zip(blocks, enc["se"], enc["groups"], enc["norm"]):
+            k = odd_kernel(b["kernel"])
             dense_res = []
             if b["residual_dense"]:
                 residual_panes.append(c)
@@ -442,8 +438,7 @@ class JasperEncoder(_HipWeights, TrainableNM):
         if self._handle is None:
             if not torch.cuda.is_available():
                 raise _no_gpu()
-            h = _lib.Handle(feat_in=self._feat_in, blocks=self._blocks, se=self._se, groups=self._groups, norm=self._norm,
-                            activation=self._act, residual_mode=self._res_mode)
+            h = _lib.Handle(**self._enc)
             h.load_state_dict(self.state_dict())
             h.finalize()
             self._handle = h
@@ -641,11 +636,10 @@ class AudioDataLayer(DataLayerNM):
 
     def set_batch(self, signals):
         import numpy as np
-        lens = np.array([len(s) for s in signals], dtype=np.int64)
-        batch = np.zeros((len(signals), int(lens.max())), dtype=np.float32)
-        for i, s in enumerate(signals):
-            batch[i, : len(s)] = np.asarray(s, dtype=np.float32)
-        self.signal, self.signal_shape, self.output = batch, lens, True
+        # cast first: this layer takes samples as they are (infer.py:29-33 hands it floats) -- integer input is NOT scaled
+        # by 2^-15 here, as the engines' PCM ingest scales it
+        batch, lens = collate([np.asarray(s, dtype=np.float32) for s in signals])
+        self.signal, self.signal_shape, self.output = batch, np.array(lens, dtype=np.int64), True
 
     def __iter__(self):
         return self

@@ -152,7 +152,7 @@ def transcribe_sharded(engine, signals, group=None, balance=True, batch_size=Non
     buckets of ``batch_size`` utterances, dealt heaviest-first to the least loaded rank; batch_size=None = the whole
     shard as one padded batch per rank, utterances dealt one by one); balance=False: contiguous shards by count, in
     input order, one batch per rank (round 1-2 behaviour)."""
-    import numpy as np
+    from .engine import collate
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     if balance:
         mine = balanced_shards([len(s) for s in signals], world, batch_size)[rank]
@@ -163,11 +163,8 @@ def transcribe_sharded(engine, signals, group=None, balance=True, batch_size=Non
         mine = [list(range(lo, hi))] if hi > lo else []
     parts_ids, parts_n, parts_idx = [], [], []
     for idx in mine:
-        lens = np.array([len(signals[i]) for i in idx], dtype=np.int64)
-        batch = np.zeros((len(idx), int(lens.max())), dtype=np.float32)
-        for k, i in enumerate(idx):
-            batch[k, : lens[k]] = signals[i]
-        r = engine.forward(torch.from_numpy(batch).to(engine.device), torch.from_numpy(lens).to(engine.device))
+        batch, lens = collate([signals[i] for i in idx])
+        r = engine.forward(torch.from_numpy(batch).to(engine.device), torch.tensor(lens, dtype=torch.int64).to(engine.device))
         parts_ids.append(r["ids"]); parts_n.append(r["id_len"])
         parts_idx.append(torch.tensor(idx, dtype=torch.int32, device=engine.device))
     if parts_ids:

@@ -9,7 +9,7 @@ import threading
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, geometry
 from .audio import pcm16_to_float, trim_silence as trim_audio
 from .frontend_tables import frontend_description
 from .stages import upload_masks
@@ -27,8 +27,7 @@ def _require_gpu():
 
 def compute_new_kernel_size(kernel_size, kernel_width):
     """JasperBlock's kernel_size_factor (parts/jasper.py:52-57): max(int(K * f), 1), plus one if that is even."""
-    k = max(int(kernel_size * kernel_width), 1)
-    return k + 1 if k % 2 == 0 else k
+    return geometry.odd_kernel(max(int(kernel_size * kernel_width), 1))
 
 
 def blocks_from_config(jasper_cfg):
@@ -157,7 +156,86 @@ def _pcm_to_float(s):
     return s
 
 
-class QuartzNetCTC:
+def check_lengths(lens, n_fft, row_independent):
+    """What every batch of signals is refused for, from its lengths: an empty batch, an empty signal and, with
+    row_independent, a signal of n_fft / 2 samples or fewer (torch.stft cannot reflect it).  All ValueError."""
+    if len(lens) == 0:
+        raise ValueError("empty batch")
+    if min(lens) == 0:
+        raise ValueError("empty signal in batch")
+    if row_independent and min(lens) <= n_fft // 2:
+        raise ValueError(f"row-independent batching needs more than n_fft/2 = {n_fft // 2} samples "
+                         f"per signal (got {min(lens)}): an unbatched call refuses such input too")
+
+
+def all_int16(signals):
+    return all(getattr(s, "dtype", None) == np.int16 for s in signals)
+
+
+def collate(signals, n_fft=None, row_independent=False, keep_int16=False, out=None):
+    """List of 1-D signals (float, or integer PCM) -> (batch [B, L] on the host, rows zero padded to the longest as
+    ``seq_collate_fn`` pads them (parts/dataset.py:14-53); the lengths, a list).  L is at least 1.
+
+    n_fft: the front end's; given, the lengths go through ``check_lengths`` first.  The batch is float32 and integer PCM
+    rows are scaled as ``_pcm_to_float`` scales them -- also in a MIXED batch (the serving queue merges whatever arrives):
+    assigned raw they would sit 2^15 too loud next to the float rows (found by tests/devtools/stress_serving.py, round 6).
+    keep_int16: a batch in which EVERY row is int16 stays int16, to cross to the device at half the bytes.
+    out: a [B, L] array to fill instead of a new one (pinned staging); its dtype decides, stale contents are overwritten."""
+    lens = [len(s) for s in signals]
+    if n_fft is not None:
+        check_lengths(lens, n_fft, row_independent)
+    if out is None:
+        pcm16 = keep_int16 and all_int16(signals)
+        out = np.zeros((len(signals), max(max(lens), 1)), dtype=np.int16 if pcm16 else np.float32)
+    else:
+        pcm16 = out.dtype == np.int16
+    for i, s in enumerate(signals):
+        out[i, : lens[i]] = s if pcm16 else _pcm_to_float(s)
+        out[i, lens[i]:] = 0
+    return out, lens
+
+
+def handle_arguments(enc_cfg, feat_in):
+    """A JasperEncoder section (``jasper``, ``activation``, ``normalization_mode``, ...) -> the encoder's keyword arguments of
+    ``_lib.Handle``: feat_in, blocks, se, groups, norm, activation, residual_mode.  The block list is parsed here, once.
+    NotImplementedError for what the library does not run: conv_mask=False, and a max residual beside any GroupNorm block."""
+    jas = enc_cfg["jasper"]
+    act, res_mode = activation_from_config(enc_cfg)
+    if not enc_cfg.get("conv_mask", True):
+        raise NotImplementedError("only conv_mask=True is implemented")
+    norm = norm_from_config(enc_cfg, jas)
+    if res_mode and any(norm):
+        raise NotImplementedError("residual_mode='max' with group, instance or layer normalization is not implemented")
+    return dict(feat_in=feat_in, blocks=blocks_from_config(jas), se=se_from_config(jas), groups=groups_from_config(jas),
+                norm=norm, activation=act, residual_mode=res_mode)
+
+
+class _Engine:
+    """What the two engines share: a handle finalized from its states, a workspace that only grows, and the handle's
+    row-independent switch set only when it changes."""
+
+    def _finalize(self, handle, states, gemm):
+        self.handle = handle
+        for sd in states:
+            handle.load_state_dict(sd)
+        handle.finalize()
+        if gemm is not None:
+            handle.set_gemm_mode(gemm)
+        self._ws = None
+        self._row_independent = False
+
+    def _grow(self, need):
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _set_row_independent(self, on):
+        self.handle.set_row_independent(on)
+        self._row_independent = bool(on)
+
+
+class QuartzNetCTC(_Engine):
     def __init__(self, model_definition, encoder_state, decoder_state, device="cuda:0", gemm=None):
         """gemm: None (library default: "f16x2"), "f16x2", "bf16x3", "fp32" or the reduced-precision opt-in "bf16x2" --
         see vasr_set_gemm_mode in include/vasr.h."""
@@ -165,32 +243,14 @@ class QuartzNetCTC:
         self.device = torch.device(device)
         self.labels = list(model_definition["labels"])
         pre = dict(model_definition["AudioToMelSpectrogramPreprocessor"])
-        jas = model_definition["JasperEncoder"]["jasper"]
-        enc_cfg = model_definition["JasperEncoder"]
-        self._act, self._res_mode = activation_from_config(enc_cfg)
-        if not enc_cfg.get("conv_mask", True):
-            raise NotImplementedError("only conv_mask=True is implemented")
+        enc = handle_arguments(model_definition["JasperEncoder"], pre.get("features", 64))
+        self._blocks, self._se, self._norm = enc["blocks"], enc["se"], enc["norm"]
         self.frontend = frontend_description(pre)
         self.hop = self.frontend["hop_length"]
-        self._blocks = blocks_from_config(jas)
-        self._se = se_from_config(jas)
-        self._groups = groups_from_config(jas)
-        self._norm = norm_from_config(enc_cfg, jas)
-        if self._res_mode and any(self._norm):
-            raise NotImplementedError("residual_mode='max' with group, instance or layer normalization is not implemented")
         with torch.cuda.device(self.device):
-            self.handle = _lib.Handle(frontend=self.frontend, feat_in=pre.get("features", 64),
-                                      blocks=blocks_from_config(jas), dec_feat_in=jas[-1]["filters"],
-                                      num_classes=len(self.labels) + 1, se=self._se, groups=self._groups,
-                                      norm=self._norm, activation=self._act, residual_mode=self._res_mode)
-            self.handle.load_state_dict(encoder_state)
-            self.handle.load_state_dict(decoder_state)
-            self.handle.finalize()
-            if gemm is not None:
-                self.handle.set_gemm_mode(gemm)
-        self._ws = None
+            self._finalize(_lib.Handle(frontend=self.frontend, dec_feat_in=self._blocks[-1]["filters"],
+                                       num_classes=len(self.labels) + 1, **enc), (encoder_state, decoder_state), gemm)
         self._slots, self._copy_stream, self._launched = None, None, 0
-        self._row_independent = False
         self._beam_stream = None
         self._beam_inflight = None                         # (done event, workgroups) of the last overlapped search
 
@@ -202,28 +262,15 @@ class QuartzNetCTC:
     def frame_seconds(self):
         """Seconds of audio per encoded frame: the front end's hop times the encoder's stride product -- what ``frames``
         divides by -- over the model's sample rate."""
-        stride = 1
-        for b in self._blocks:
-            stride *= b["stride"]
-        return self.hop * stride / float(self.frontend["sample_rate"])
+        return self.hop * geometry.stride_product(self._blocks) / float(self.frontend["sample_rate"])
 
     def _workspace(self, batch, samples):
-        need = self.handle.workspace_bytes(batch, samples=samples)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self._grow(self.handle.workspace_bytes(batch, samples=samples))
 
     def frames_of(self, length):
         """``frames(n)[1]`` for a [B] int64 tensor of sample counts, on its device: the encoded frames of each row alone -- the
         conv chain of vasr_encoded_frames in integer tensor ops, for lengths that exist on the device only (trim_silence)."""
-        t = 1 + torch.div(length, self.hop, rounding_mode="floor")
-        for b in self._blocks:
-            k = b["kernel"] + (1 if b["kernel"] % 2 == 0 else 0)
-            pad = (b["dilation"] * k) // 2 - 1 if b["dilation"] > 1 else k // 2
-            for _ in range(b["repeat"]):
-                t = torch.div(t + (2 * pad - b["dilation"] * (k - 1) - 1), b["stride"], rounding_mode="floor") + 1
-        return t.to(torch.int32)
+        return geometry.frames_of(self._blocks, self.hop, length)
 
     def forward(self, wav, length, want_logp=False, want_pred=True, row_independent=False, trim_silence=False,
                 _trim_buffers=None, augmentor=None, _lengths_host=None, spec_augment=None):
@@ -283,8 +330,7 @@ class QuartzNetCTC:
         enc_len = torch.empty((B,), dtype=torch.float32, device=dev)
         logp = torch.empty((B, t1, len(self.labels) + 1), dtype=torch.float32, device=dev) if want_logp else None
         if bool(row_independent) != self._row_independent:
-            self.handle.set_row_independent(row_independent)
-            self._row_independent = bool(row_independent)
+            self._set_row_independent(row_independent)
         masks = None
         if spec_augment is not None:
             row_frames = None
@@ -331,20 +377,27 @@ class QuartzNetCTC:
         each row over its own frames (and reflects it at its own end): the transcripts of batch-1 calls.  trim_silence: see
         forward(); the rows' own frames then come from the trimmed lengths, on the device.  augmentor: see forward(); the
         rows' own frames come from the perturbed lengths.  spec_augment: see forward()."""
-        lens = [len(s) for s in signals]
-        if row_independent and min(lens) <= self.frontend["n_fft"] // 2:
-            raise ValueError(f"row-independent batching needs more than n_fft/2 = {self.frontend['n_fft'] // 2} samples "
-                             f"per signal (got {min(lens)})")
-        batch = np.zeros((len(signals), max(lens)), dtype=np.float32)
-        for i, s in enumerate(signals):
-            batch[i, : lens[i]] = _pcm_to_float(s)
+        r, own = self.forward_signals(signals, want_pred=False, row_independent=row_independent, trim_silence=trim_silence,
+                                      augmentor=augmentor, spec_augment=spec_augment)
+        # (without row_independent every frame of the padded batch is searched, as the reference searches its batch-1 tensor)
+        return beam_decoder.decode_batch(r["logp"], beam_width, frames=own if row_independent else None)
+
+    def forward_signals(self, signals, want_pred=True, row_independent=False, trim_silence=False, augmentor=None,
+                        spec_augment=None):
+        """List of 1-D signals at the model's rate (float, or integer PCM) -> (``forward(want_logp=True)``'s result dict of
+        their zero-padded batch, the frames of every row: [B] int32 on the device).  With row_independent these are the row's
+        own encoded frames, taken from the lengths where they last changed: on the device behind trim_silence or an
+        ``augmentor`` (the dict's "length"), on the host otherwise.  Without, they are the encoder's lengths of the padded
+        batch ("enc_len", truncated).  The other arguments: see forward()."""
+        batch, lens = collate(signals, self.frontend["n_fft"], row_independent)
         r = self.forward(torch.from_numpy(batch).to(self.device), torch.tensor(lens, device=self.device),
-                         want_logp=True, want_pred=False, row_independent=row_independent, trim_silence=trim_silence,
+                         want_logp=True, want_pred=want_pred, row_independent=row_independent, trim_silence=trim_silence,
                          augmentor=augmentor, _lengths_host=lens, spec_augment=spec_augment)
-        own = [self.frames(n)[1] for n in lens] if row_independent else None
-        if row_independent and (trim_silence or augmentor is not None):
-            own = self.frames_of(r["length"])
-        return beam_decoder.decode_batch(r["logp"], beam_width, frames=own)
+        if not row_independent:
+            return r, r["enc_len"].to(torch.int32)
+        if trim_silence or augmentor is not None:
+            return r, self.frames_of(r["length"])
+        return r, torch.tensor([self.frames(n)[1] for n in lens], dtype=torch.int32).to(self.device)
 
     def forward_beam(self, wav, length, beam_decoder, beam_width, frames=None, overlap=True):
         """Acoustic pass + beam search (+ LM) of one device-resident batch: the batched form of infer.py:146-160.
@@ -383,16 +436,7 @@ class QuartzNetCTC:
     def halo_mel_frames(self):
         """Half-width of the encoder's receptive field in mel frames (even): sum over the depthwise convolutions of
         (K - 1) / 2 * dilation, times the stride product in front of each."""
-        h, rate = 0, 1
-        for b in self._blocks:
-            k = b["kernel"] + (1 if b["kernel"] % 2 == 0 else 0)
-            for _ in range(b["repeat"]):
-                if b["separable"] or k > 1:
-                    h += (k - 1) // 2 * b["dilation"] * rate
-                rate *= b["stride"]
-                if b["stride"] > 1 and b["repeat"] > 1:
-                    raise NotImplementedError("strided block with repeat > 1")
-        return h + (h & 1)
+        return geometry.halo_mel_frames(self._blocks)
 
     def forward_long(self, wav, chunk_frames=4096, rows_per_pass=4, want_logp=False):
         """One long recording [L] (float32, on the device) in BOUNDED memory: the reference CLI skips files longer than
@@ -421,10 +465,7 @@ class QuartzNetCTC:
         mel, seq = stages.melspec(h, wav[None].contiguous(), torch.tensor([L], dtype=torch.int64, device=wav.device))
         T, seq0 = mel.shape[2], int(seq[0])
         T1 = h.encoded_frames(T)
-        H = self.halo_mel_frames()
-        stride = 1
-        for b in self._blocks:
-            stride *= b["stride"]
+        H, stride = self.halo_mel_frames(), geometry.stride_product(self._blocks)
         chunk_frames = max(int(chunk_frames), 1)
         jobs = []                                           # (mel lo, mel hi, mask length, first kept frame, kept frames)
         for o0 in range(0, T1, chunk_frames):
@@ -458,18 +499,7 @@ class QuartzNetCTC:
 
     def _encoded_length(self, seq):
         """MaskedConv1d.get_seq_len chain (jasper.py:108-111, quirk Q3) on the host: float result, truncated between convs."""
-        lf = float(seq)
-        first = True
-        for b in self._blocks:
-            k = b["kernel"] + (1 if b["kernel"] % 2 == 0 else 0)
-            pad = (b["dilation"] * k) // 2 - 1 if b["dilation"] > 1 else k // 2
-            for _ in range(b["repeat"]):
-                convs = [(k, b["stride"], b["dilation"], pad), (1, 1, 1, 0)] if b["separable"] else [(k, b["stride"], b["dilation"], pad)]
-                for kk, st, dl, pd in convs:
-                    li = int(lf) if not first else int(seq)
-                    first = False
-                    lf = float(np.float32(np.float32(li + 2 * pd - dl * (kk - 1) - 1) / np.float32(st)) + np.float32(1.0))
-        return lf
+        return geometry.encoded_length(self._blocks, seq)
 
     # -- pipelined host path: pinned staging, copies on their own stream, two batches in flight
     def launch(self, signals, row_independent=False, after_forward=None, trim_silence=False, augmentor=None,
@@ -489,8 +519,7 @@ class QuartzNetCTC:
         augmentor: see forward(); the staging for the ids is sized by ``augmentor.max_augmentation_length``.
         spec_augment: see forward(); the rectangles are drawn here, on the host, while the previous batch computes.
         """
-        if len(signals) == 0:
-            raise ValueError("empty batch")
+        check_lengths([len(s) for s in signals], self.frontend["n_fft"], row_independent)
         if self._slots is None:
             self._slots = [_Slot(self), _Slot(self)]
             self._copy_stream = torch.cuda.Stream(self.device)
@@ -499,7 +528,7 @@ class QuartzNetCTC:
         return slot.launch(signals, row_independent, after_forward, trim_silence, augmentor, spec_augment)
 
 
-class QuartzNetClassifier:
+class QuartzNetClassifier(_Engine):
     """The fused wav -> class fast path of the speech-command / keyword models (one C-ABI call per batch,
     vasr_classify_f32): AudioToMelSpectrogramPreprocessor -> CropOrPadSpectrogramAugmentation(audio_length) -> JasperEncoder ->
     JasperDecoderForClassification.  Lives beside QuartzNetCTC; the per-module classes in asr.py run the same kernels."""
@@ -517,14 +546,7 @@ class QuartzNetClassifier:
             raise ValueError(f"audio_length must be positive, got {audio_length!r}")
         self.labels = list(labels) if labels is not None else None
         pre = dict(model_definition["AudioToMelSpectrogramPreprocessor"])
-        enc_cfg = model_definition["JasperEncoder"]
-        jas = enc_cfg["jasper"]
-        act, res_mode = activation_from_config(enc_cfg)
-        if not enc_cfg.get("conv_mask", True):
-            raise NotImplementedError("only conv_mask=True is implemented")
-        norm = norm_from_config(enc_cfg, jas)
-        if res_mode and any(norm):
-            raise NotImplementedError("residual_mode='max' with group, instance or layer normalization is not implemented")
+        enc = handle_arguments(model_definition["JasperEncoder"], pre.get("features", 64))
         self.frontend = frontend_description(pre)
         w = np.asarray(decoder_state["decoder_layers.0.weight"].detach().cpu().numpy()
                        if hasattr(decoder_state["decoder_layers.0.weight"], "detach") else decoder_state["decoder_layers.0.weight"])
@@ -532,17 +554,8 @@ class QuartzNetClassifier:
         if self.labels is not None and len(self.labels) != self.num_classes:
             raise ValueError(f"{len(self.labels)} labels for {self.num_classes} classes")
         with torch.cuda.device(self.device):
-            self.handle = _lib.Handle(frontend=self.frontend, feat_in=pre.get("features", 64), blocks=blocks_from_config(jas),
-                                      se=se_from_config(jas), groups=groups_from_config(jas), norm=norm, activation=act,
-                                      residual_mode=res_mode,
-                                      classifier=(jas[-1]["filters"], self.num_classes, 0 if pooling_type == "avg" else 1))
-            self.handle.load_state_dict(encoder_state)
-            self.handle.load_state_dict(decoder_state)
-            self.handle.finalize()
-            if gemm is not None:
-                self.handle.set_gemm_mode(gemm)
-        self._ws = None
-        self._row_independent = False
+            head = (enc["blocks"][-1]["filters"], self.num_classes, 0 if pooling_type == "avg" else 1)
+            self._finalize(_lib.Handle(frontend=self.frontend, classifier=head, **enc), (encoder_state, decoder_state), gemm)
 
     def forward(self, wav, length, offsets=None, softmax=False, row_independent=False, want_mel=False, trim_silence=False):
         """wav [B, L] f32 cuda (rows zero padded), length [B] i64 cuda -> logits [B, num_classes] f32, or probabilities
@@ -570,19 +583,15 @@ class QuartzNetClassifier:
             off = torch.as_tensor(offsets).to(device=wav.device, dtype=torch.int64).contiguous()
             if off.shape != (B,):
                 raise ValueError(f"offsets must have shape ({B},), got {tuple(off.shape)}")
-        need = int(_lib.lib().vasr_classify_workspace_bytes(self.handle.h, B, L, self.audio_length))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._grow(int(_lib.lib().vasr_classify_workspace_bytes(self.handle.h, B, L, self.audio_length)))
         if bool(row_independent) != self._row_independent:
-            self.handle.set_row_independent(row_independent)
-            self._row_independent = bool(row_independent)
+            self._set_row_independent(row_independent)
         out = torch.empty((B, self.num_classes), dtype=torch.float32, device=wav.device)
         mel = torch.empty((B, self.frontend["n_mels"], self.audio_length), dtype=torch.float32, device=wav.device) if want_mel else None
         _lib.check(_lib.lib().vasr_classify_f32(
             self.handle.h, wav.data_ptr(), length.data_ptr(), B, L, self.audio_length, off.data_ptr() if off is not None else None,
-            int(bool(softmax)), out.data_ptr(), mel.data_ptr() if mel is not None else None, self._ws.data_ptr(),
-            self._ws.numel(), _stream_ptr()))
+            int(bool(softmax)), out.data_ptr(), mel.data_ptr() if mel is not None else None, ws.data_ptr(), ws.numel(),
+            _stream_ptr()))
         return (out, mel) if want_mel else out
 
     def classify(self, signals, offsets=None, row_independent=False, trim_silence=False):
@@ -597,17 +606,7 @@ class QuartzNetClassifier:
 
     def _collate(self, signals, row_independent):
         """classify's collate: (wav [B, L] f32, length [B] i64) on the device, rows zero padded to the longest."""
-        if len(signals) == 0:
-            raise ValueError("empty batch")
-        lens = [len(s) for s in signals]
-        if min(lens) == 0:
-            raise ValueError("empty signal in batch")
-        if row_independent and min(lens) <= self.frontend["n_fft"] // 2:
-            raise ValueError(f"row-independent batching needs more than n_fft/2 = {self.frontend['n_fft'] // 2} samples "
-                             f"per signal (got {min(lens)}): an unbatched call refuses such input too")
-        batch = np.zeros((len(signals), max(lens)), dtype=np.float32)
-        for i, s in enumerate(signals):
-            batch[i, : lens[i]] = _pcm_to_float(np.asarray(s))
+        batch, lens = collate(signals, self.frontend["n_fft"], row_independent)
         return torch.from_numpy(batch).to(self.device), torch.tensor(lens, device=self.device)
 
     def classify_topk(self, signals, k, offsets=None, row_independent=False, trim_silence=False):
@@ -655,9 +654,7 @@ class QuartzNetClassifier:
         picks, staged, pos = [], [], 0          # staged: pinned batches, alive until the copies that read them have run
         for audio, a_len, label, _ in layer.data_iterator:
             B = audio.shape[0]
-            if row_independent and int(a_len.min()) <= self.frontend["n_fft"] // 2:
-                raise ValueError(f"row-independent batching needs more than n_fft/2 = {self.frontend['n_fft'] // 2} samples "
-                                 f"per signal (got {int(a_len.min())}): an unbatched call refuses such input too")
+            check_lengths(a_len.tolist(), self.frontend["n_fft"], row_independent)
             off = None
             if offsets is not None:
                 off = torch.tensor([int(offsets[slot[i]]) for i in order[pos : pos + B]], dtype=torch.int64).pin_memory()
@@ -741,15 +738,8 @@ class _Slot:
         eng = self.eng
         if self.pending is not None:
             self.pending.texts()          # the slot's previous batch: fetch before its buffers are overwritten
-        B = len(signals)
-        lens = [len(s) for s in signals]
-        L = max(lens)
-        if min(lens) == 0:
-            raise ValueError("empty signal in batch")
-        if row_independent and min(lens) <= eng.frontend["n_fft"] // 2:
-            raise ValueError(f"row-independent batching needs more than n_fft/2 = {eng.frontend['n_fft'] // 2} samples "
-                             f"per signal (got {min(lens)}): an unbatched call refuses such input too")
-        pcm16 = all(getattr(s, "dtype", None) == np.int16 for s in signals)
+        B, L = len(signals), max(len(s) for s in signals)
+        pcm16 = all_int16(signals)
         dtype, item = (torch.int16, 2) if pcm16 else (torch.float32, 4)
         nbytes = B * L * item
         _, t1 = eng.frames(L)
@@ -762,15 +752,7 @@ class _Slot:
             if trim_silence:
                 self._reserve_trim(B, nbytes)
                 trim_buffers = (self.dev_trim[:nbytes].view(dtype).view(B, L), self.dev_start[:B])
-            host = self.pin[:nbytes].view(dtype).view(B, L).numpy()
-            for i, s in enumerate(signals):
-                if not pcm16:
-                    # a MIXED batch (the serving queue merges whatever arrives): integer PCM rows are scaled here as
-                    # AudioSegment does -- assigned raw they would sit 2^15 too loud next to the float rows (found by
-                    # tests/devtools/stress_serving.py, round 6)
-                    s = _pcm_to_float(s)
-                host[i, : lens[i]] = s
-                host[i, lens[i]:] = 0
+            _, lens = collate(signals, out=self.pin[:nbytes].view(dtype).view(B, L).numpy())
             self.pin_len[:B] = torch.tensor(lens, dtype=torch.int64)
             comp = torch.cuda.current_stream(eng.device)
             with torch.cuda.stream(eng._copy_stream):

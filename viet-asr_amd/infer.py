@@ -16,7 +16,7 @@ import torch
 from . import asr as nemo_asr
 from . import configs
 from .core import DeviceType, NeuralModuleFactory
-from .engine import QuartzNetCTC
+from .engine import QuartzNetCTC, collate
 from .helpers import post_process_predictions
 
 
@@ -194,11 +194,11 @@ class VietASR:
                 yield idx, sigs
         return entries, batches()
 
-    def _walk_manifest(self, manifest_filepath, batch_size, row_independent, after_forward=None, trim_silence=False,
-                       augmentor=None, spec_augment=None):
+    def _walk_manifest(self, manifest_filepath, batch_size, row_independent, after_forward=None, **pre):
         """The entries of a NeMo JSON-lines manifest and their greedy transcripts, in manifest order: sorted by duration, cut
         into batches of ``batch_size``, two batches in flight (engine.QuartzNetCTC.launch).  after_forward(entries, idx) -> the
-        ``launch`` hook of the batch holding entries ``idx`` (or None)."""
+        ``launch`` hook of the batch holding entries ``idx`` (or None).  pre: the public method's trim_silence (resolved),
+        augmentor and spec_augment, handed on to ``launch``."""
         entries, batches = self._manifest_batches(manifest_filepath, batch_size)
         hyps, pending = [None] * len(entries), []
 
@@ -209,8 +209,7 @@ class VietASR:
 
         for idx, sigs in batches:
             hook = after_forward(entries, idx) if after_forward is not None else None
-            pending.append((idx, self._fused_engine().launch(sigs, row_independent, hook, trim_silence=trim_silence,
-                                                             augmentor=augmentor, spec_augment=spec_augment)))
+            pending.append((idx, self._fused_engine().launch(sigs, row_independent, hook, **pre)))
             if len(pending) == 2:
                 collect(pending.pop(0))
         for job in pending:
@@ -251,6 +250,24 @@ class VietASR:
             ref[k, : len(t)] = torch.tensor(t, dtype=torch.int32)
         return ref, ref_len
 
+    def _scored_rows(self, entries, idx):
+        """The rows of the batch holding entries ``idx`` that are scored, those whose entry has a ``text`` -> None where there
+        is none, else (pick, ref, ref_len): their parsed references (``_reference_tokens``: pinned) and pick(*tensors) -> the
+        scored rows of device tensors [B, ...], the tensors themselves where every row is scored.  Nothing synchronises;
+        keep the result alive until the copies that read its pinned memory have run."""
+        rows = [k for k, i in enumerate(idx) if entries[i].get("text")]
+        if not rows:
+            return None
+        ref, ref_len = self._reference_tokens(entries, [idx[k] for k in rows])
+        sel = None if len(rows) == len(idx) else torch.tensor(rows, dtype=torch.int64).pin_memory()
+
+        def pick(*tensors):
+            if sel is None:
+                return tensors
+            rows_d = sel.to(tensors[0].device, non_blocking=True)
+            return tuple(t.index_select(0, rows_d) for t in tensors)
+        return pick, ref, ref_len
+
     def evaluate_manifest(self, manifest_filepath, batch_size=64, row_independent=True, breakdown=False, nbest=None,
                           eval_loss=False, trim_silence=False, augmentor=None, spec_augment=None):
         """``transcribe_manifest``'s walk with WER and CER scored on the device: -> (hyps, ``ErrorRate.compute()``), the
@@ -287,41 +304,31 @@ class VietASR:
         ``transcribe_manifest``, in every form."""
         from .metrics import ErrorBreakdown, ErrorRate
         metric = (ErrorBreakdown if breakdown else ErrorRate)(self.labels)
-        trim = self._trim(trim_silence)
+        pre = dict(trim_silence=self._trim(trim_silence), augmentor=augmentor, spec_augment=spec_augment)
         if eval_loss:
             if nbest is not None:
                 raise ValueError("eval_loss=True cannot be combined with nbest")
-            return self._evaluate_manifest_loss(manifest_filepath, batch_size, row_independent, metric, trim, augmentor,
-                                                spec_augment)
+            return self._evaluate_manifest_loss(manifest_filepath, batch_size, row_independent, metric, **pre)
         if nbest is not None:
-            return self._evaluate_manifest_nbest(manifest_filepath, batch_size, row_independent, metric, int(nbest), trim,
-                                                 augmentor, spec_augment)
+            return self._evaluate_manifest_nbest(manifest_filepath, batch_size, row_independent, metric, int(nbest), **pre)
         keep = []                   # pinned reference batches, alive until the copies that read them have run
 
         def after_forward(entries, idx):
-            rows = [k for k, i in enumerate(idx) if entries[i].get("text")]
-            if not rows:
+            scored = self._scored_rows(entries, idx)
+            if scored is None:
                 return None
-            ref, ref_len = self._reference_tokens(entries, [idx[k] for k in rows])
-            sel = None if len(rows) == len(idx) else torch.tensor(rows, dtype=torch.int64).pin_memory()
-            keep.append((ref, ref_len, sel))
+            keep.append(scored)
+            pick, ref, ref_len = scored
 
             def score(out):
                 dev = out["ids"].device
-                ids, id_len = out["ids"], out["id_len"]
-                if sel is not None:
-                    rows_d = sel.to(dev, non_blocking=True)
-                    ids, id_len = ids.index_select(0, rows_d), id_len.index_select(0, rows_d)
-                metric.update(ids, id_len, ref.to(dev, non_blocking=True), ref_len.to(dev, non_blocking=True))
+                metric.update(*pick(out["ids"], out["id_len"]), ref.to(dev, non_blocking=True), ref_len.to(dev, non_blocking=True))
             return score
 
-        _, hyps = self._walk_manifest(manifest_filepath, batch_size, row_independent, after_forward, trim_silence=trim,
-                                      augmentor=augmentor, spec_augment=spec_augment)
+        _, hyps = self._walk_manifest(manifest_filepath, batch_size, row_independent, after_forward, **pre)
         return hyps, metric.compute()
 
-    def _evaluate_manifest_nbest(self, manifest_filepath, batch_size, row_independent, metric, nbest, trim_silence=False,
-                                 augmentor=None, spec_augment=None):
-        from .engine import _pcm_to_float
+    def _evaluate_manifest_nbest(self, manifest_filepath, batch_size, row_independent, metric, nbest, **pre):
         from .metrics import OracleErrorRate
         if self.mode != "beam":
             raise ValueError("nbest needs an instance constructed with decoder='beam'")
@@ -329,26 +336,15 @@ class VietASR:
         entries, batches = self._manifest_batches(manifest_filepath, batch_size)
         hyps = [None] * len(entries)
         for idx, sigs in batches:
-            lens = [len(s) for s in sigs]
-            if row_independent and min(lens) <= eng.frontend["n_fft"] // 2:
-                raise ValueError(f"row-independent batching needs more than n_fft/2 = {eng.frontend['n_fft'] // 2} samples "
-                                 f"per signal (got {min(lens)})")
-            batch = np.zeros((len(sigs), max(lens)), dtype=np.float32)
-            for k, s in enumerate(sigs):
-                batch[k, : lens[k]] = _pcm_to_float(s)
-            r = eng.forward(torch.from_numpy(batch).to(eng.device), torch.tensor(lens, device=eng.device), want_logp=True,
-                            want_pred=False, row_independent=row_independent, trim_silence=trim_silence, augmentor=augmentor,
-                            _lengths_host=lens, spec_augment=spec_augment)
-            own = [eng.frames(n)[1] for n in lens] if row_independent else None
-            if row_independent and (trim_silence or augmentor is not None):
-                own = eng.frames_of(r["length"])
-            ids, id_len, count, _, _ = dec.decode_beams_ids(r["logp"], self.beam.beam_width, nbest, frames=own)
-            rows = [k for k, i in enumerate(idx) if entries[i].get("text")]
-            if rows:
-                ref, ref_len = self._reference_tokens(entries, [idx[k] for k in rows])
+            r, own = eng.forward_signals(sigs, want_pred=False, row_independent=row_independent, **pre)
+            # (without row_independent every frame of the padded batch is searched, as ``transcribe_beam`` does)
+            ids, id_len, count, _, _ = dec.decode_beams_ids(r["logp"], self.beam.beam_width, nbest,
+                                                            frames=own if row_independent else None)
+            scored = self._scored_rows(entries, idx)
+            if scored is not None:
+                pick, ref, ref_len = scored
+                s_ids, s_len, s_count = pick(ids, id_len, count)
                 ref, ref_len = ref.to(eng.device), ref_len.to(eng.device)
-                sel = torch.tensor(rows, dtype=torch.int64, device=eng.device)
-                s_ids, s_len, s_count = ids.index_select(0, sel), id_len.index_select(0, sel), count.index_select(0, sel)
                 metric.update(s_ids[:, 0], s_len[:, 0], ref, ref_len)
                 oracle.update(s_ids, s_len, s_count, ref, ref_len)
             for i, t in zip(idx, eng.texts(ids[:, 0], id_len[:, 0])):
@@ -357,48 +353,23 @@ class VietASR:
         res["oracle_wer"], res["oracle_cer"] = best["oracle_wer"], best["oracle_cer"]
         return hyps, res
 
-    def _forward_logp(self, sigs, row_independent, trim_silence=False, augmentor=None, spec_augment=None):
-        """One zero-padded batch of signals at the model's rate through ``forward(want_logp=True)`` -> (its result dict, the
-        frames of every row [B] on the device: the row's own encoded frames when row_independent, otherwise the encoder's
-        lengths of the padded batch).  trim_silence: the rows are trimmed on the device first (the dict then has "trim_start"
-        and "length") and a row's own frames follow its trimmed length, computed there.  augmentor: likewise, behind the trim.
-        spec_augment: see ``engine.QuartzNetCTC.forward``."""
-        from .engine import _pcm_to_float
-        eng = self._fused_engine()
-        lens = [len(s) for s in sigs]
-        if row_independent and min(lens) <= eng.frontend["n_fft"] // 2:
-            raise ValueError(f"row-independent batching needs more than n_fft/2 = {eng.frontend['n_fft'] // 2} samples "
-                             f"per signal (got {min(lens)})")
-        batch = np.zeros((len(sigs), max(lens)), dtype=np.float32)
-        for k, s in enumerate(sigs):
-            batch[k, : lens[k]] = _pcm_to_float(s)
-        r = eng.forward(torch.from_numpy(batch).to(eng.device), torch.tensor(lens, device=eng.device), want_logp=True,
-                        row_independent=row_independent, trim_silence=trim_silence, augmentor=augmentor, _lengths_host=lens,
-                        spec_augment=spec_augment)
-        if row_independent and (trim_silence or augmentor is not None):
-            frames = eng.frames_of(r["length"])
-        elif row_independent:
-            frames = torch.tensor([eng.frames(n)[1] for n in lens], dtype=torch.int32).to(eng.device)
-        else:
-            frames = r["enc_len"]
-        return r, frames
+    def _forward_logp(self, sigs, row_independent, **pre):
+        """One batch of signals at the model's rate -> (``forward(want_logp=True)``'s result dict, the frames of every row):
+        ``engine.QuartzNetCTC.forward_signals``.  pre: trim_silence (resolved), augmentor, spec_augment."""
+        return self._fused_engine().forward_signals(sigs, row_independent=row_independent, **pre)
 
-    def _evaluate_manifest_loss(self, manifest_filepath, batch_size, row_independent, metric, trim_silence=False,
-                                augmentor=None, spec_augment=None):
+    def _evaluate_manifest_loss(self, manifest_filepath, batch_size, row_independent, metric, **pre):
         from .metrics import CTCEvalLoss
         eng, loss = self._fused_engine(), CTCEvalLoss(len(self.labels))
         entries, batches = self._manifest_batches(manifest_filepath, batch_size)
         hyps = [None] * len(entries)
         for idx, sigs in batches:
-            r, frames = self._forward_logp(sigs, row_independent, trim_silence, augmentor, spec_augment)
-            rows = [k for k, i in enumerate(idx) if entries[i].get("text")]
-            if rows:
-                ref, ref_len = self._reference_tokens(entries, [idx[k] for k in rows])
+            r, frames = self._forward_logp(sigs, row_independent, **pre)
+            scored = self._scored_rows(entries, idx)
+            if scored is not None:
+                pick, ref, ref_len = scored
+                ids, id_len, logp, frames = pick(r["ids"], r["id_len"], r["logp"], frames)
                 ref, ref_len = ref.to(eng.device), ref_len.to(eng.device)
-                ids, id_len, logp = r["ids"], r["id_len"], r["logp"]
-                if len(rows) != len(idx):
-                    sel = torch.tensor(rows, dtype=torch.int64, device=eng.device)
-                    ids, id_len, logp, frames = (t.index_select(0, sel) for t in (ids, id_len, logp, frames))
                 metric.update(ids, id_len, ref, ref_len)
                 loss.update(logp, frames, ref, ref_len)
             for i, t in zip(idx, eng.texts(r["ids"], r["id_len"])):
@@ -421,7 +392,7 @@ class VietASR:
             raise ValueError(f"score needs as many texts as signals, and at least one (got {len(signals)} and {len(texts)})")
         eng = self._fused_engine()
         r, frames = self._forward_logp([self._to_model_rate(s, sample_rate) for s in signals], row_independent,
-                                       self._trim(trim_silence), augmentor, spec_augment)
+                                       trim_silence=self._trim(trim_silence), augmentor=augmentor, spec_augment=spec_augment)
         ref, ref_len = self._reference_tokens([{"text": t} for t in texts], range(len(texts)))
         from . import stages
         loss = stages.ctc_loss(r["logp"], frames, ref.to(eng.device), ref_len.to(eng.device), len(self.labels))
@@ -454,36 +425,48 @@ class VietASR:
                              f"{None if texts is None else len(texts)})")
         eng = self._fused_engine()
         trim = self._trim(trim_silence)
-        r, frames = self._forward_logp([self._to_model_rate(s, sample_rate) for s in signals], row_independent, trim, augmentor,
-                                       spec_augment)
+        r, frames = self._forward_logp([self._to_model_rate(s, sample_rate) for s in signals], row_independent,
+                                       trim_silence=trim, augmentor=augmentor, spec_augment=spec_augment)
         if texts is None:
             tgt, tgt_len = r["ids"], r["id_len"]
         else:
             ref, ref_len = self._reference_tokens([{"text": t} for t in texts], range(len(texts)))
             tgt, tgt_len = ref.to(eng.device, non_blocking=True), ref_len.to(eng.device, non_blocking=True)
         out = stages.ctc_align(r["logp"], frames, tgt, tgt_len, len(self.labels))
+        rows = []
+        for text, score, offset, chars, words in self._alignment_rows(out, tgt, tgt_len, r["trim_start"] if trim else None):
+            rows.append({"text": text, "score": score, "chars": chars, "words": words})
+            if trim:
+                rows[-1]["offset"] = offset
+        return rows
+
+    def _alignment_rows(self, out, tgt, tgt_len, first_sample=None, what="rows"):
+        """``stages.ctc_align``'s result ``out`` for the targets tgt / tgt_len -> per row (text, score, offset, chars, words):
+        the parsed text, the best path's log-probability, the row's start in seconds and ``alignment_entries`` shifted by it
+        (empty lists for a row without a path, score -inf).  first_sample: where every row starts in the recording it was cut
+        from, in samples at the model's rate -- a [B] device tensor, a host sequence, or None: 0.  Everything crosses
+        through pinned memory in one go: one synchronisation.  A NaN score raises RuntimeError naming the ``what``."""
+        eng = self._fused_engine()
         dev = [out["score"], out["start"], out["end"], out["token_logp"], tgt.to(torch.int32), tgt_len.to(torch.int32)]
-        if trim:
-            dev.append(r["trim_start"])
+        if torch.is_tensor(first_sample):
+            dev.append(first_sample)
         host = [torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in dev]
         for h, d in zip(host, dev):
             h.copy_(d, non_blocking=True)
         torch.cuda.current_stream(eng.device).synchronize()
         score, start, end, logp, ids, n = (h.numpy() for h in host[:6])
-        rate = float(self.model_definition["AudioToMelSpectrogramPreprocessor"]["sample_rate"])
-        offsets = [int(v) / rate for v in host[6].numpy()] if trim else None
+        if torch.is_tensor(first_sample):
+            first_sample = host[6].numpy()
         if np.isnan(score).any():
-            raise RuntimeError("the alignment score came back NaN for rows %s" % np.isnan(score).nonzero()[0].tolist())
+            raise RuntimeError(f"the alignment score came back NaN for {what} %s" % np.isnan(score).nonzero()[0].tolist())
+        rate = float(self.model_definition["AudioToMelSpectrogramPreprocessor"]["sample_rate"])
         sec = eng.frame_seconds()
         rows = []
-        for b in range(len(signals)):
+        for b in range(len(score)):
             chars = [self.labels[c] for c in ids[b, : n[b]]]
-            row = {"text": "".join(chars), "score": float(score[b]), "chars": [], "words": []}
-            if trim:
-                row["offset"] = offsets[b]
-            if score[b] != -np.inf:
-                row["chars"], row["words"] = alignment_entries(chars, start[b], end[b], logp[b], sec, offsets[b] if trim else 0.0)
-            rows.append(row)
+            offset = int(first_sample[b]) / rate if first_sample is not None else 0.0
+            cs, ws = alignment_entries(chars, start[b], end[b], logp[b], sec, offset) if score[b] != -np.inf else ([], [])
+            rows.append(("".join(chars), float(score[b]), offset, cs, ws))
         return rows
 
     def transcribe_long(self, signals, sample_rate=None, top_db=60.0, min_silence=0.3, max_seconds=None, pad=None,
@@ -513,7 +496,6 @@ class VietASR:
         align=True adds "chars" and "words" to every segment (``align``'s entries: the forced alignment of the segment's text to
         its log-probs, times shifted by the segment's start)."""
         from . import audio, stages
-        from .engine import _pcm_to_float
         if decoder not in ("greedy", "beam") or (decoder == "beam" and self.mode != "beam"):
             raise ValueError("decoder must be 'greedy', or 'beam' on an instance constructed with decoder='beam'")
         single = not isinstance(signals, (list, tuple))
@@ -530,11 +512,8 @@ class VietASR:
         pad = frame_length // 2 if pad is None else int(pad)
         min_samples = eng.frontend["n_fft"] // 2
         # upload once: int16 as it is where every recording is, float32 otherwise
-        pcm = all(s.dtype == np.int16 for s in sigs)
-        lens = [len(s) for s in sigs]
-        host = np.zeros((len(sigs), max(max(lens), 1)), dtype=np.int16 if pcm else np.float32)
-        for b, s in enumerate(sigs):
-            host[b, : lens[b]] = s if pcm else np.asarray(_pcm_to_float(s), dtype=np.float32)
+        host, lens = collate(sigs, keep_int16=True)
+        pcm = host.dtype == np.int16
         x = torch.from_numpy(host).to(eng.device)
         length = torch.tensor(lens, dtype=torch.int64, device=eng.device)
         if sample_rate is not None and int(sample_rate) != rate:
@@ -562,17 +541,9 @@ class VietASR:
                 else:
                     tgt, tgt_len = r["ids"], r["id_len"]
                 out = stages.ctc_align(r["logp"], frames, tgt, tgt_len, len(self.labels))
-                score, start, end, logp, ids, n = (t.cpu().numpy() for t in (out["score"], out["start"], out["end"],
-                                                                             out["token_logp"], tgt.to(torch.int32),
-                                                                             tgt_len.to(torch.int32)))
-                if np.isnan(score).any():
-                    raise RuntimeError("the alignment score came back NaN for segments %s" % np.isnan(score).nonzero()[0].tolist())
-                sec = eng.frame_seconds()
-                for k, e in enumerate(entries):
-                    e["chars"], e["words"] = [], []
-                    if score[k] != -np.inf:
-                        chars = [self.labels[c] for c in ids[k, : n[k]]]
-                        e["chars"], e["words"] = alignment_entries(chars, start[k], end[k], logp[k], sec, e["start"])
+                aligned = self._alignment_rows(out, tgt, tgt_len, [plan[i][1] for i in idx], "segments")
+                for e, (_, _, _, chars, words) in zip(entries, aligned):
+                    e["chars"], e["words"] = chars, words
             for i, e in zip(idx, entries):
                 results[i] = e
         out = [{"text": "", "segments": [], "dropped": int(d)} for d in dropped]

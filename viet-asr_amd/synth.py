@@ -17,6 +17,7 @@ import zlib
 
 import numpy as np
 
+from .geometry import odd_kernel
 
 # Gains chosen so that activation RMS stays O(1..10) through all 18 blocks of QuartzNet15x5 with the
 # random BN statistics below (measured: 0.85 -> 2.4 for 12x1, 0.85 -> 6 for 15x5).
@@ -53,10 +54,7 @@ def kernel_of(lcfg):
     k = lcfg["kernel"]
     k = k[0] if isinstance(k, (list, tuple)) else k
     f = float(lcfg.get("kernel_size_factor", 1.0))
-    k = max(int(k * f), 1)
-    if k % 2 == 0:
-        k += 1
-    return k
+    return odd_kernel(max(int(k * f), 1))
 
 
 def first(v):
